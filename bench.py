@@ -2,9 +2,10 @@
 """
 bench.py -- BASELINE.json's metric: megapixels/s decoded (dequantize+IDCT -> h2v2 up-sample -> RGB)
 on synthetic 4096x4096 4:2:0 baseline frames, coefficient planes resident in HBM, plus the achieved
-HBM GB/s of the fused kernel against the MI355X roofline and the CPU baseline timed beside it.
+HBM GB/s of the fused kernel against the MI355X roofline; with --full also the CPU baseline timed beside it
+and every other figure and check below (golden checksums, per-launch times, other workloads, files, counters).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--shard-frames S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--shard-frames S] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -547,6 +548,23 @@ def reference_bench(zj, ctx, reps=4):
     return out
 
 
+DUMP_SAMPLES = 12 << 20   # --dump-outputs: pixel bytes sampled over all ranks (48 MB as float32)
+
+
+def dump_outputs(out_dir, name, region, rows, row_len, row_pitch, n):
+    """`n` bytes of the pixels in `region` (a uint8 device tensor of `rows` rows `row_pitch` bytes apart, the first `row_len`
+    of each the pixels; the bytes between the rows are never written) to out_dir/name.npy as float32, at positions drawn
+    with a fixed seed from the pixel bytes alone: the same positions for the same arguments in every run and every build."""
+    import numpy as np
+    import torch
+    pos = np.sort(np.random.default_rng(1234).integers(0, rows * row_len, size=n, dtype=np.int64))
+    if row_pitch != row_len:
+        pos = pos // row_len * row_pitch + pos % row_len
+    sample = region[torch.from_numpy(pos).to(region.device)].to(torch.float32).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), sample)
+
+
 def load_golden():
     try:
         g = json.load(open(os.path.join(ROOT, "tests", "golden", "checksums_seed1234.json")))
@@ -691,11 +709,23 @@ def main():
                     help="one process on one GPU playing rank R of an N-rank run: its shard [R*S, (R+1)*S), its golden offsets; "
                          "collectives at world size 1 (virtual ranks: everything about configs[4] one GPU can prove)")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip other_workloads / reference_files / from_files / scattered_batch")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-launch and single-frame kernel times, the dense control, the copy "
+                         "yardstick, the scattered batch, the golden checksums, the counter passes, the CPU baseline, the other "
+                         "workloads and files, the end-to-end figure (each still subject to its --no-* switch); without it a run "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: a fixed, seeded sample of the pixels the last timed step decoded, as "
+                         "DIR/pixels_sample.npy (float32; DIR/pixels_sample_rank<R>.npy for ranks R > 0)")
     args = ap.parse_args()
     if args.child:
         args.no_cpu_baseline = args.no_single_frame = args.no_live_traffic = args.no_e2e = True
         # a profiler child serialises every dispatch: nothing but the shard's launches (no pre-warm passes, no control)
         args.no_prewarm = args.no_dense_control = args.no_other_workloads = True
+        args.full = False
+    elif not args.full:
+        args.no_cpu_baseline = args.no_single_frame = args.no_live_traffic = args.no_e2e = True
+        args.no_dense_control = args.no_other_workloads = True
     virt = None
     if args.as_rank:
         try:
@@ -827,11 +857,18 @@ def main():
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, world, coll_dev)
     per_rank_ms = shard.gather_values(el_local / args.steps * 1e3, world, coll_dev)
     kernel_ms_region = ev[0].elapsed_time(ev[1]) / args.steps
+    if args.dump_outputs:  # before anything below decodes into d_out again
+        k = (args.steps - 1) % nsub
+        row_len = W * ncomp_out
+        row_pitch = out_pitch or row_len
+        dump_outputs(args.dump_outputs, "pixels_sample" + (f"_rank{rank}" if rank else ""),
+                     d_out[k * B * frame_out:(k + 1) * B * frame_out], B * frame_out // row_pitch, row_len, row_pitch,
+                     DUMP_SAMPLES // world)
 
     # dominant-kernel duration for the roofline: HIP events on the launch stream over >= 100 launches WALKING THE SHARD
     # like the timed steps do (whatever --steps says: the driver's --steps 20 would average 20).  When the timed region
-    # itself has >= 100 launches its own event pair is the figure; otherwise a second, untimed run of 104+ launches.
-    kiters = args.steps if (args.steps >= 100 or args.child) else -(-100 // nsub) * nsub
+    # itself has >= 100 launches its own event pair is the figure; otherwise (--full) a second, untimed run of 104+ launches.
+    kiters = args.steps if (args.steps >= 100 or not args.full) else -(-100 // nsub) * nsub
     if kiters == args.steps:
         kernel_ms = kernel_ms_region
     else:
@@ -844,11 +881,11 @@ def main():
     # every launch bracketed by its own event pair (what a profiler reports per dispatch), a few per sub-batch
     p0 = subs[0]
     each, kname = [], None
-    for k in range(1 if args.child else nsub):
+    for k in range(1 if args.child else nsub if args.full else 0):
         pk = subs[k]
         _, e1, kname = ctx.time_decode_device(desc, B, pk[0], pk[1], pk[2], pk[3], 2 if args.child else max(2, -(-48 // nsub)), stream)
         each.append(e1)
-    kernel_ms_each = sum(each) / len(each)
+    kernel_ms_each = sum(each) / len(each) if each else None
     # every rank's own figure: the roofline fraction below is the SLOWEST rank's, not rank 0's
     per_rank_kernel_ms = shard.gather_values(kernel_ms, world, coll_dev)
     per_rank_numa = [{"device_node": int(a), "thread_node": int(b), "bound": bool(c)} for a, b, c in
@@ -971,12 +1008,13 @@ def main():
         scat_adj_ms = ev[2].elapsed_time(ev[3]) / 104
     # every frame of the shard decoded once more (untimed), then the trivial gather: per-frame checksums, computed on the
     # GPU, gathered over RCCL and compared with the oracle's (tests/golden/checksums_seed1234.json)
-    for k in range(nsub):
-        step(k)
+    if args.full or args.child:
+        for k in range(nsub):
+            step(k)
     torch.cuda.synchronize()
     sums = []
     scat_same = None
-    if not args.child:
+    if args.full:
         wts = synth.checksum_weights_t(frame_out // 8, dev)
         sums = [synth.frame_checksum_t(d_out[j * frame_out:(j + 1) * frame_out], wts) for j in range(S)]
         if scat_ms is not None:
@@ -1065,10 +1103,10 @@ def main():
                          "kernel": kname, "kernel_ms": round(kernel_ms, 4), "kernel_ms_rank0": round(kernel_ms_rank0, 4),
                          "per_rank_kernel_ms": [round(v, 4) for v in per_rank_kernel_ms],
                          "per_rank_numa": per_rank_numa,
-                         "kernel_ms_single_launch": round(kernel_ms_each, 4),
+                         "kernel_ms_single_launch": None if kernel_ms_each is None else round(kernel_ms_each, 4),
                          "kernel_launches_timed": kiters, "kernel_ms_timed_region": round(kernel_ms_region, 4),
                          "kernel_timing": f"HIP events on the launch stream; {kiters} launches walking the shard's {nsub} "
-                                          f"sub-batches of {B} frames (>= 100 whatever --steps); kernel_ms_timed_region = "
+                                          f"sub-batches of {B} frames (with --full >= 100 whatever --steps); kernel_ms_timed_region = "
                                           f"events around the {args.steps} timed steps; kernel_ms_single_launch = own event "
                                           f"pair per launch; kernel_ms (and frac) = the slowest rank's, per_rank_kernel_ms = every rank's",
                          "algorithmic_bytes_per_launch": int(algo_bytes),

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _bench(*args, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(env_extra or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args], capture_output=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -162,7 +162,7 @@ def test_two_ranks_under_torchrun_the_drivers_launch_shape():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env["ZJ_BENCH_SAME_GPU"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
                         "--min-untimed", "1", "--shard-frames", "16", "--no-live-traffic", "--no-single-frame", "--no-dense-control"],
                        capture_output=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -171,3 +171,34 @@ def test_two_ranks_under_torchrun_the_drivers_launch_shape():
     res = json.loads(lines[0])
     assert res["n_gpus"] == 2 and res["frames_checksummed"] == 32 and res["checksums_match_golden"] is True
     assert res["cpu_baseline"]["value"] > 100 and len(res["roofline"]["per_rank_kernel_ms"]) == 2
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_the_last_steps_pixels(tmp_path):
+    """Without --full the run sets up, warms up, times --steps steps and prints the line; --dump-outputs writes a seeded sample
+    of the pixels the last timed step decoded, the same with --full (whose checks come after it and pass)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+
+    def run(d, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "1", "--shard-frames", "32",
+                            "--dump-outputs", str(d), *extra], capture_output=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), np.load(os.path.join(d, "pixels_sample.npy"))
+
+    plain, px = run(tmp_path / "plain")
+    assert plain["steps"] == 7 and plain["n_gpus"] == 1 and plain["ms_per_step"] > 0 and plain["higher_is_better"] is True
+    assert abs(plain["value"] - 16 * 4096 * 4096 / 1e6 / (plain["ms_per_step"] * 1e-3)) < 1e-3 * plain["value"]
+    assert not {"cpu_baseline", "other_workloads", "reference_files", "from_files", "reference_bench", "e2e_pinned"} & set(plain)
+    rf = plain["roofline"]
+    assert plain["checksums_match_golden"] is None and rf["single_frame_launch"] is None and rf["dense_control"] is None
+    assert rf["kernel_launches_timed"] == 7
+    assert px.dtype == np.float32 and px.size == bench.DUMP_SAMPLES and px.nbytes <= 64 << 20
+    assert px.min() >= 0 and px.max() <= 255 and np.unique(px).size > 200
+    full, px_full = run(tmp_path / "full", "--full", "--no-cpu-baseline", "--no-live-traffic", "--no-e2e", "--no-other-workloads")
+    assert full["checksums_match_golden"] is True and full["roofline"]["kernel_launches_timed"] >= 100
+    assert np.array_equal(px, px_full)

@@ -31,7 +31,7 @@ def test_bench_gather_rgb_runs_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--min-untimed", "1",
                         "--shard-frames", "16", "--no-cpu-baseline", "--no-live-traffic", "--no-single-frame", "--no-e2e",
-                        "--gather-rgb"], capture_output=True, timeout=900, env=env)
+                        "--gather-rgb", "--full"], capture_output=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
     g = res["gather_rgb"]

@@ -11,20 +11,22 @@ the emulation harness, also built with the sanitizers: a damaged scan must neith
 import argparse
 import ctypes as C
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = "/tmp/libzjjpeg_asan.so"
-EMU = "/tmp/libzjemu_asan.so"
+SO = "libzjjpeg_asan.so"
+EMU = "libzjemu_asan.so"
 
 
-def build():
+def build(d):
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-pthread", "-fsanitize=address,undefined",
-                           "-fno-omit-frame-pointer", "-o", SO,
+                           "-fno-omit-frame-pointer", "-o", os.path.join(d, SO),
                            os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_jpeg.cpp"), os.path.join(ROOT, "tests", "fuzz", "jpeg_stubs.cpp")])
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-fno-strict-aliasing", "-fsanitize=address,undefined",
-                           "-fno-sanitize=alignment", "-fno-omit-frame-pointer", "-Wno-unknown-pragmas", "-o", EMU,
+                           "-fno-sanitize=alignment", "-fno-omit-frame-pointer", "-Wno-unknown-pragmas", "-o", os.path.join(d, EMU),
                            os.path.join(ROOT, "tests", "emu", "zj_emu.cpp")])
 
 
@@ -32,13 +34,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=4000)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--libdir", help="(internal) the directory the parent built the sanitizer libraries in")
     a = ap.parse_args()
     if not a.child:
-        build()
-        asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"]).decode().strip()
-        env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=1",
-                   UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--iters", str(a.iters)], env=env)
+        d = tempfile.mkdtemp(prefix="zj_fuzz_")  # one per run: no clash with another user's or run's libraries
+        try:
+            build(d)
+            asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"]).decode().strip()
+            env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=1",
+                       UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--iters", str(a.iters), "--libdir", d], env=env)
+        finally:
+            shutil.rmtree(d, ignore_errors=True)
         print("sanitizer-clean" if r.returncode == 0 else f"FAILED (exit {r.returncode})")
         sys.exit(r.returncode)
 
@@ -47,14 +54,14 @@ def main():
     import importlib
     import jpeg_enc
     synth = importlib.import_module("zune-jpeg_amd.synth")
-    L = C.CDLL(SO)
+    L = C.CDLL(os.path.join(a.libdir, SO))
     L.zj_decoder_new.restype = C.c_void_p
     L.zj_decoder_new.argtypes = [C.c_void_p]
     L.zj_decoder_free.argtypes = [C.c_void_p]
     L.zj_decoder_decode_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.zj_decoder_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.zj_decoder_scan_blob.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    E = C.CDLL(EMU)
+    E = C.CDLL(os.path.join(a.libdir, EMU))
     E.zje_huff_decode.argtypes = [C.c_void_p] * 6
     E.zje_huff_plane_len.restype = C.c_size_t
     E.zje_huff_plane_len.argtypes = [C.c_void_p, C.c_int]

@@ -31,7 +31,7 @@ if has lab; then
 fi
 if has bench; then
   echo "== bench" | tee -a $O/summary.txt
-  timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.json | tee -a $O/summary.txt; tail -3 $O/bench.err
+  timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.json | tee -a $O/summary.txt; tail -3 $O/bench.err
 fi
 if has prof; then
   echo "== rocprofv3 --kernel-trace --stats (same command as bench)" | tee -a $O/summary.txt

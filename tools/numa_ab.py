@@ -42,7 +42,7 @@ def main():
         e = dict(os.environ, **env)
         if not env:
             e.pop("ZJ_NUMA", None)
-        r = subprocess.run(prefix + [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--shard-frames", "16",
+        r = subprocess.run(prefix + [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--shard-frames", "16", "--full",
                                      "--no-cpu-baseline", "--no-live-traffic", "--no-single-frame", "--no-dense-control", "--no-other-workloads"],
                            capture_output=True, text=True, env=e, timeout=900)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -28,7 +28,7 @@ def main():
     for r in range(a.ranks):
         t0 = time.time()
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--as-rank", f"{r}/{a.ranks}", "--steps", str(a.steps),
-                            "--warmup", str(a.warmup), "--no-cpu-baseline", "--no-e2e", "--no-live-traffic", "--no-other-workloads"],
+                            "--warmup", str(a.warmup), "--full", "--no-cpu-baseline", "--no-e2e", "--no-live-traffic", "--no-other-workloads"],
                            capture_output=True, env=env, timeout=900)
         lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
         if p.returncode != 0 or len(lines) != 1:
