@@ -5,7 +5,7 @@
 //! The C side is `include/zjhip.h` (ABI version 8, checked at run time by `Decoder::new_with_options`).  Output bytes equal the reference's *scalar* arms.
 #![allow(non_camel_case_types)]
 use std::ffi::CStr;
-use std::os::raw::{c_char, c_int, c_void};
+use std::os::raw::{c_char, c_int, c_uint, c_void};
 
 pub const ZJ_ABI_VERSION: c_int = 8;
 pub const ZJ_SCATTER_MAX: usize = 32;
@@ -181,6 +181,13 @@ extern "C" {
                                    d_cb: *const *const i16, d_cr: *const *const i16, d_out: *const *mut u8,
                                    stream: *mut c_void) -> c_int;
     pub fn zj_pointer_device(p: *const c_void) -> c_int;
+    pub fn zj_crop_out_len(d: *const zj_frame_desc, crop_w: c_uint, crop_h: c_uint, out_pitch: c_uint) -> usize;
+    pub fn zj_decode_crops_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize, d_y: *const *const i16,
+                                  d_cb: *const *const i16, d_cr: *const *const i16, origins: *const c_uint, crop_w: c_uint,
+                                  crop_h: c_uint, d_out: *const *mut u8, out_pitch: c_uint, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_crop_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint, w: c_uint,
+                                                h: c_uint, d_out: *mut u8, out_cap: usize, out_pitch: c_uint,
+                                                out_len: *mut usize) -> c_int;
     pub fn zj_device_pci_bus_id(device: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zj_device_numa_node(device: c_int) -> c_int;
     pub fn zj_bind_thread_to_numa_node(node: c_int) -> c_int;

@@ -229,6 +229,24 @@ ZJ_API int zj_decode_planes_device_strided(zj_ctx *ctx, const zj_frame_desc *d, 
 #define ZJ_SCATTER_MAX 32
 ZJ_API int zj_decode_frames_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
                             const int16_t *const *d_cb, const int16_t *const *d_cr, uint8_t *const *d_out, void *stream);
+/* Crop windows (region of interest) of frames left in HBM, for consumers on the GPU (a data loader's random or centre
+ * crop).  A crop is EXACTLY the bytes zj_decode_planes_device writes inside the window: crop row r, byte b == full-frame
+ * row y + r, byte x * C + b (C = bytes per pixel; CHW: the same per plane with C = 1) -- the zeros of the full decode
+ * included (the early RGB tail, ragged rows, the rows below the last complete strip), every flag, colour space and layout.
+ * Only the tiles whose bytes the window needs are decoded.  The crop's rows lie out_pitch bytes apart (0 = tight: w * C);
+ * the padding between them and everything outside zj_crop_out_len() bytes is never written.  d->out_pitch must be 0 (the
+ * crop's pitch is its own argument); an empty window, one that leaves the frame or a pitch below a row is ZJ_ERR_ARG and
+ * nothing is launched.
+ * zj_crop_out_len: bytes of one crop (out_pitch, 0 = tight, x h; x 3 for CHW); 0 = not a valid window for d.  A
+ * single-component d with a colour output (all zeros, as zj_out_len counts them) has crops of that output's size. */
+ZJ_API size_t zj_crop_out_len(const zj_frame_desc *d, unsigned crop_w, unsigned crop_h, unsigned out_pitch);
+/* nframes frames of ONE geometry, each cut to the crop_w x crop_h window at origins[2f], origins[2f+1]; pointers as in
+ * zj_decode_frames_device (host arrays of device pointers; planes 16-byte aligned, outputs at any byte); batches larger
+ * than ZJ_SCATTER_MAX are split into several launches.  There is one crop kernel generation: zj_set_variant does not
+ * apply.  Asynchronous on `stream`. */
+ZJ_API int zj_decode_crops_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
+                                  const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *origins,
+                                  unsigned crop_w, unsigned crop_h, uint8_t *const *d_out, unsigned out_pitch, void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -331,6 +349,12 @@ ZJ_API int zj_decoder_finish_pixels(zj_decoder *d, zj_ctx *ctx, uint8_t *out, si
  * it does NOT order itself after work the caller still has in flight on other streams.  A caller whose allocator recycles
  * device memory stream-ordered (a caching tensor allocator) must synchronise the stream that last used d_out before the call. */
 ZJ_API int zj_decoder_finish_pixels_device(zj_decoder *d, zj_ctx *ctx, uint8_t *d_out, size_t out_cap, size_t *out_len);
+/* the decoder's last prepared file cut to a window (zj_decode_crops_device's contract), pixels left in HBM; stream ordering
+ * as zj_decoder_finish_pixels_device.  Planes decoded on the CPU: only the window's strips are uploaded; a scan left for
+ * the device (zj_options.entropy): the entropy stage runs on the device, the crop kernel over its planes in HBM.
+ * *out_len = zj_crop_out_len(); out_cap below it is ZJ_ERR_ARG. */
+ZJ_API int zj_decoder_finish_pixels_crop_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                                uint8_t *d_out, size_t out_cap, unsigned out_pitch, size_t *out_len);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

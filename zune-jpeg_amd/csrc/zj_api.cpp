@@ -76,6 +76,7 @@ struct zj_ctx {
     uint32_t* d_ctl = nullptr;    // the slots' control words, contiguous: one clear, one copy back per call
     uint32_t* h_ctl = nullptr;    // pinned: HUFF_CTL_WORDS per slot
 
+    bool scan_planes_only = false; // zjint_scan_to_planes: the entropy stage alone, the planes stay in the slot (crop windows)
     int huff_rounds = 0;          // synchronisation rounds of the last scan
     int huff_plane_slot = 0;
     size_t huff_plane_off[3] = {0, 0, 0}, huff_plane_len[3] = {0, 0, 0}; // the last call's first scan: its planes inside the slot (bytes / int16 elements)
@@ -623,6 +624,132 @@ int zj_decode_frames_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, c
     return decode_frames_device_impl(c, d, pl, nframes, d_y, d_cb, d_cr, d_out, s, 1);
 }
 
+/* ---- crop windows ----------------------------------------------------------- */
+size_t zj_crop_out_len(const zj_frame_desc* d, unsigned crop_w, unsigned crop_h, unsigned out_pitch)
+{
+    Plan pl;
+    CropPlan cp;
+    if (zero_output(d)) return make_zero_crop(d, crop_w, crop_h, out_pitch, cp) == ZJ_OK ? cp.out_len : 0;
+    return make_crop_plan(d, crop_w, crop_h, out_pitch, pl, cp) == ZJ_OK ? cp.out_len : 0;
+}
+
+// frames [0, nframes) of ONE geometry, each cut to its own window; launches of up to SCATTER_MAX frames (grid.z)
+static int decode_crops_impl(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, size_t nframes,
+                             const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins,
+                             uint8_t* const* out, hipStream_t s)
+{
+    const bool chroma = pl.out != OUT_GRAY;
+    for (size_t f0 = 0; f0 < nframes; f0 += SCATTER_MAX) {
+        const int n = (int)(nframes - f0 < (size_t)SCATTER_MAX ? nframes - f0 : (size_t)SCATTER_MAX);
+        CropParams p;
+        int nstrips = 0, ncols = 0;
+        fill_crop_params(d, pl, cp, y, chroma ? cb : nullptr, chroma ? cr : nullptr, out, origins, f0, n, p, nstrips, ncols);
+        // the window rows at or below rows_covered (Q6): zeros, from a launch of their own, for the frames that have any
+        CropZero z{};
+        z.rows_covered = pl.rows_covered; z.crop_h = cp.h; z.nbytes = cp.w * cp.bpp; z.out_pitch = (int)cp.out_pitch;
+        z.nplanes = cp.nplanes; z.crop_plane = (long long)cp.out_pitch * cp.h;
+        bool any = false;
+        for (int f = 0; f < n; f++) {
+            z.fptr[f] = (uint64_t)(uintptr_t)out[f0 + f];
+            z.y0[f] = origins[2 * (f0 + f) + 1];
+            any = any || (long long)z.y0[f] + cp.h > pl.rows_covered;
+        }
+        z.nframes = n;
+        if (any) ZJ_HIP(c, launch_crop_zero(z, s));
+        ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, s));
+    }
+    return ZJ_OK;
+}
+
+static int check_crop_args(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const unsigned* origins, unsigned crop_w,
+                           unsigned crop_h, unsigned out_pitch, Plan& pl, CropPlan& cp)
+{
+    if (!c || !origins || nframes == 0 || nframes > (size_t)1 << 20) return ZJ_ERR_ARG;
+    int rc = make_crop_plan(d, crop_w, crop_h, out_pitch, pl, cp);
+    if (rc) return rc;
+    for (size_t f = 0; f < nframes; f++) {
+        int s0, s1, k0, k1;
+        if ((rc = crop_window(d, pl, cp, origins[2 * f], origins[2 * f + 1], s0, s1, k0, k1))) return rc;
+    }
+    return ZJ_OK;
+}
+
+int zj_decode_crops_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                           const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* origins,
+                           unsigned crop_w, unsigned crop_h, uint8_t* const* d_out, unsigned out_pitch, void* stream)
+{
+    Plan pl;
+    CropPlan cp;
+    int rc = check_crop_args(c, d, nframes, origins, crop_w, crop_h, out_pitch, pl, cp);
+    if (rc) return rc;
+    if (!d_y || !d_out) return ZJ_ERR_ARG;
+    const bool chroma = pl.out != OUT_GRAY;
+    if (chroma && (!d_cb || !d_cr)) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < nframes; f++) {
+        if (!d_y[f] || !d_out[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
+        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return decode_crops_impl(c, d, pl, cp, nframes, d_y, d_cb, d_cr, origins, d_out, s);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_crop_device).  One frame's window on the context stream, from
+// planes in host memory -- only the strips the window needs are uploaded, each at its full-frame offset in the context's
+// scratch (strips are contiguous row ranges of a plane and no filter reads across one) -- or from planes already in HBM.
+int zjint_crop_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                     int planes_on_device, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch)
+{
+    Plan pl;
+    CropPlan cp;
+    const unsigned origin[2] = {x, yy};
+    int rc = check_crop_args(c, d, 1, origin, w, h, out_pitch, pl, cp);
+    if (rc) return rc;
+    const bool chroma = pl.out != OUT_GRAY;
+    if (!y || !d_out || (chroma && (!cb || !cr))) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    const int16_t* py = y; const int16_t* pcb = cb; const int16_t* pcr = cr;
+    if (!planes_on_device) {
+        int s0, s1, k0, k1;
+        crop_window(d, pl, cp, x, yy, s0, s1, k0, k1);
+        if ((rc = ensure_scratch(c, 0, pl.y_len * 2))) return rc;
+        if (chroma && ((rc = ensure_scratch(c, 1, pl.c_len * 2)) || (rc = ensure_scratch(c, 2, pl.c_len * 2)))) return rc;
+        // i16 elements per strip (the split of decode_device_impl's ZJ_SPLIT experiment)
+        const size_t yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8), crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+        if (s1 > s0) {
+            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[0] + s0 * yrow, y + s0 * yrow, (s1 - s0) * yrow * 2, hipMemcpyHostToDevice, c->stream));
+            if (chroma) {
+                ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[1] + s0 * crow, cb + s0 * crow, (s1 - s0) * crow * 2, hipMemcpyHostToDevice, c->stream));
+                ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[2] + s0 * crow, cr + s0 * crow, (s1 - s0) * crow * 2, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        py = (const int16_t*)c->scratch[0];
+        pcb = chroma ? (const int16_t*)c->scratch[1] : nullptr; pcr = chroma ? (const int16_t*)c->scratch[2] : nullptr;
+    }
+    if ((rc = decode_crops_impl(c, d, pl, cp, 1, &py, &pcb, &pcr, origin, &d_out, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+// Library-internal: the window of an all-zero output (zj_plan.h: make_zero_crop): zeros in the window's rows, the pitch
+// padding untouched
+int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch)
+{
+    CropPlan cp;
+    if (!c || !d_out || !zero_output(d)) return ZJ_ERR_ARG;
+    int rc = make_zero_crop(d, w, h, out_pitch, cp);
+    if (rc) return rc;
+    if ((size_t)x + w > d->width || (size_t)yy + h > d->height) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    CropZero z{};
+    z.rows_covered = 0; z.crop_h = cp.h; z.nbytes = cp.w * cp.bpp; z.out_pitch = (int)cp.out_pitch;
+    z.nplanes = cp.nplanes; z.crop_plane = (long long)cp.out_pitch * cp.h; z.nframes = 1;
+    z.fptr[0] = (uint64_t)(uintptr_t)d_out; z.y0[0] = yy;
+    ZJ_HIP(c, launch_crop_zero(z, c->stream));
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
 int zj_time_decode_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* d_y,
                           const int16_t* d_cb, const int16_t* d_cr, uint8_t* d_out, void* stream,
                           int iters, float* ms_total, float* ms_each, const char** kernel_name)
@@ -1130,7 +1257,8 @@ bool scan_header_ok(const HuffScan* h, size_t blob_bytes)
 // validates one scan, sizes its slot, fills the working-set pointers
 int scan_setup(zj_ctx* c, ScanJob& j, int slot, const zj_frame_desc* d, const void* blob, size_t blob_bytes, uint8_t* out, int out_on_device)
 {
-    if (!d || !blob || !out || blob_bytes < sizeof(HuffScan)) return ZJ_ERR_ARG;
+    // (no output at all for the entropy stage alone, zjint_scan_to_planes: nothing of j.d_out is used then)
+    if (!d || !blob || (!out && !c->scan_planes_only) || blob_bytes < sizeof(HuffScan)) return ZJ_ERR_ARG;
     const HuffScan* h = (const HuffScan*)blob;
     if (h->magic != HUFF_MAGIC || h->blob_bytes != blob_bytes || h->nsub == 0 || h->ncomp != d->in_components) return ZJ_ERR_ARG;
     if (!scan_header_ok(h, blob_bytes)) return ZJ_ERR_ARG;
@@ -1209,8 +1337,10 @@ int scan_clear_again(zj_ctx* c, ScanJob& j, hipStream_t s)
 // pixel kernel over the slot's planes, the pixels and the control words on their way back
 int scan_pixels(zj_ctx* c, ScanJob& j, hipStream_t s, int out_on_device)
 {
-    int rc = decode_device_impl(c, j.d, j.pl, 1, j.a.plane[0], j.chroma ? j.a.plane[1] : nullptr, j.chroma ? j.a.plane[2] : nullptr, j.d_out, s, 1);
-    if (rc) return rc;
+    if (!c->scan_planes_only) {
+        const int rc = decode_device_impl(c, j.d, j.pl, 1, j.a.plane[0], j.chroma ? j.a.plane[1] : nullptr, j.chroma ? j.a.plane[2] : nullptr, j.d_out, s, 1);
+        if (rc) return rc;
+    }
     if (!out_on_device) ZJ_HIP(c, hipMemcpyAsync(j.out, j.d_out, j.pl.out_len, hipMemcpyDeviceToHost, s));
     ZJ_HIP(c, hipMemcpyAsync(j.h_ctl, j.a.ctl, (size_t)HUFF_CTL_WORDS * 4, hipMemcpyDeviceToHost, s));
     return ZJ_OK;
@@ -1309,7 +1439,7 @@ static int decode_scans_impl(zj_ctx* c, size_t n, const zj_frame_desc* descs, co
     // Pixel kernel: the scans of one geometry and one set of tables go through it as the frames of ONE launch, wherever
     // their planes (arena slots) and their pixels (the staging arena, or whatever the caller's pointers are) happen to lie:
     // equally spaced frames take the strided form, anything else the scattered form (decode_frames_device_impl)
-    {
+    if (!c->scan_planes_only) {
         bool launched[ZJ_SCAN_BATCH_MAX] = {};
         for (int q = 0; q < nlive; q++) {
             if (launched[q]) continue;
@@ -1396,6 +1526,21 @@ int zj_decode_scan(zj_ctx* c, const zj_frame_desc* d, const void* blob, size_t b
     int rc1 = ZJ_OK;
     const int rc = zj_decode_scans(c, 1, d, &blob, &blob_bytes, &out, out_on_device, &rc1, status_bits);
     return rc ? rc : rc1;
+}
+
+// Library-internal (zj_jpeg.cpp): the entropy stage of one prepared scan on the device WITHOUT the pixel kernel; on ZJ_OK
+// *planes are the three coefficient planes in the context's slot (valid until the next scan on this context)
+int zjint_scan_to_planes(zj_ctx* c, const zj_frame_desc* d, const void* blob, size_t blob_bytes, const int16_t* planes[3],
+                         unsigned* status_bits)
+{
+    if (!c || !d || !planes) return ZJ_ERR_ARG;
+    c->scan_planes_only = true; // (scan_setup then takes a null output, and nothing launches a write to one)
+    const int rc = zj_decode_scan(c, d, blob, blob_bytes, nullptr, 1, status_bits);
+    c->scan_planes_only = false;
+    if (rc) return rc;
+    const uint8_t* base = (const uint8_t*)c->hslot[c->huff_plane_slot].planes;
+    for (int k = 0; k < 3; k++) planes[k] = c->huff_plane_len[k] ? (const int16_t*)(base + c->huff_plane_off[k]) : nullptr;
+    return ZJ_OK;
 }
 
 int zj_scan_planes(zj_ctx* c, int16_t* y, int16_t* cb, int16_t* cr, size_t len[3])

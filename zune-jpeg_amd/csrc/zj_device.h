@@ -1897,4 +1897,150 @@ inline bool seam_launch(const Params& p)
     return false;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Crop-window decode (zj_decode_crops_device): the bytes of the full decode inside a window
+// [x, x + w) x [y, y + h), written at the crop's own pitch.
+// ------------------------------------------------------------------------------------------------
+// A crop workgroup decodes ONE tile exactly as the generic (any-width) kernels do, but its pixel stores land in a staging
+// area in LDS laid out like the tile's rows of the frame; then it copies the part of each row it OWNS that lies inside the
+// window.  Ownership is by the bytes a tile writes, not by pixel x: tile k owns [own_lo(k), own_lo(k + 1)) of every row,
+// which is its natural range [bpp * TWY * k, bpp * TWY * (k + 1)) except at a row's end, where the two early-written units
+// of an RGB row (Q5, store_unit_generic) start up to 88 bytes left of their tile -- the staging keeps crop_margin() bytes in
+// front of the tile's natural range for them.  Every byte of a row has exactly one writer (store_unit_generic), so the
+// union of the owned ranges is the full decode's row.
+ZJ_HD constexpr int crop_bpp(const int out) { return out == OUT_RGBA ? 4 : ((out == OUT_RGB || out == OUT_YCBCR) ? 3 : 1); }
+ZJ_HD constexpr int crop_margin(const int out) { return out == OUT_RGB ? 128 : 0; }
+ZJ_HD constexpr int crop_stage_pitch(const int out, const int twy) { return crop_bpp(out) * twy + crop_margin(out); }
+
+template <int HS, int VS, int OUT>
+struct CropStage {
+    using C = Cfg<HS, VS, OUT>;
+    static constexpr int BPP = crop_bpp(OUT);
+    static constexpr int MARGIN = crop_margin(OUT);
+    static constexpr int PITCH = crop_stage_pitch(OUT, C::TWY);   // bytes per staged tile row (a multiple of 16)
+    static constexpr int NPL = OUT == OUT_RGB_CHW ? 3 : 1;
+    static constexpr int BYTES = NPL * C::SH * PITCH + 32;       // (+ the dwords the shifted reads look ahead)
+    static_assert(PITCH % 16 == 0, "staged rows keep the 16-byte alignment of the stores");
+};
+
+// The launch's arguments: the tile decode's Params (its out_pitch / plane_stride are the STAGING's, zero_fill 1, always the
+// scattered form), plus the window.  Params itself is unchanged: the fused kernels keep their code.
+struct CropParams {
+    Params p;
+    int crop_w, crop_h;           // window, pixels
+    int ncols, nstrips;           // grid: tile columns / strips per frame (the widest range over the launch's frames)
+    int out_pitch;                // bytes between crop rows (CHW: between the rows of a plane)
+    int bpp;                      // bytes per pixel of a frame row (CHW: 1, per plane)
+    int row_bytes;                // bytes of a frame row (CHW: of a plane's row)
+    int tile_bytes;               // bpp x tile width
+    int cut_tile[2], cut_lo[2];   // ownership exceptions at a row's end (zj_plan.h: make_crop_plan); tile -1 = none
+    long long crop_plane;         // CHW: bytes between the crop's planes (out_pitch x crop_h)
+    uint32_t origin[SCATTER_MAX]; // per frame: x | y << 16
+    uint32_t first[SCATTER_MAX];  // per frame: first tile column | first strip << 16
+};
+
+// first byte of a frame row that tile column k owns (k == tiles per row: the row's end)
+ZJ_HD int crop_own_lo(const int k, const int tile_bytes, const int row_bytes, const int cut_tile0, const int cut_lo0,
+                      const int cut_tile1, const int cut_lo1)
+{
+    long long lo = (long long)k * tile_bytes;
+    if (k == cut_tile0 && cut_lo0 < lo) lo = cut_lo0;
+    if (k == cut_tile1 && cut_lo1 < lo) lo = cut_lo1;
+    return lo < row_bytes ? (int)lo : row_bytes;
+}
+
+// What one crop workgroup copies: frame rows [r0, r1) of its strip, row bytes [b0, b1) (CHW: of each plane)
+struct CropSpan { int frame, strip, tile, r0, r1, b0, b1, x, y; };
+
+// the workgroup (frame fz, strip index sy, column index sx) of a crop launch; false: nothing to do (workgroup-uniform:
+// a frame whose window spans fewer strips or columns than the launch's grid leaves the rest of its workgroups idle)
+template <int HS, int VS, int OUT>
+ZJ_DEV bool crop_locate(const CropParams& cp, const int fz, const int sy, const int sx, CropSpan& s)
+{
+    using C = Cfg<HS, VS, OUT>;
+    const uint32_t o = cp.origin[fz], f = cp.first[fz];
+    s.frame = fz; s.x = (int)(o & 0xffffu); s.y = (int)(o >> 16);
+    s.strip = (int)(f >> 16) + sy; s.tile = (int)(f & 0xffffu) + sx;
+    if (s.strip >= cp.p.n_strips || s.tile >= cp.p.tiles_per_row) return false;
+    s.r0 = s.strip * C::SH > s.y ? s.strip * C::SH : s.y;
+    int r1 = s.strip * C::SH + C::SH;
+    if (r1 > s.y + cp.crop_h) r1 = s.y + cp.crop_h;
+    if (r1 > cp.p.height) r1 = cp.p.height;
+    s.r1 = r1;
+    if (s.r0 >= s.r1) return false;
+    const int lo = crop_own_lo(s.tile, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]);
+    const int hi = crop_own_lo(s.tile + 1, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]);
+    const int wb0 = s.x * cp.bpp, wb1 = (s.x + cp.crop_w) * cp.bpp;
+    s.b0 = lo > wb0 ? lo : wb0;
+    s.b1 = hi < wb1 ? hi : wb1;
+    return s.b0 < s.b1;
+}
+
+// where the tile decode's stores go: the staging, addressed the way the frame's rows are (phase_color writes frame row
+// `row` at out + row * out_pitch + byte, out_pitch == the staging pitch)
+template <int HS, int VS, int OUT>
+ZJ_DEV uint8_t* crop_stage_base(uint8_t* stage, const CropSpan& s)
+{
+    using S = CropStage<HS, VS, OUT>;
+    using C = Cfg<HS, VS, OUT>;
+    return stage - (long long)s.strip * C::SH * S::PITCH - ((long long)s.tile * C::TWY * S::BPP - S::MARGIN);
+}
+
+// Copy-out of the owned window bytes, one lane per 16 bytes of a crop row.  A window row starts at any byte: the lanes
+// store dwords aligned in the DESTINATION (four at a time), each assembled from two staged dwords with v_alignbyte_b32;
+// the bytes up to the row segment's first dword boundary and after its last go out singly from one extra lane per segment.
+template <int HS, int VS, int OUT>
+ZJ_DEV void crop_copyout(const CropParams& cp, const CropSpan& s, const int tid, const int nthreads, const uint8_t* stage, uint8_t* out)
+{
+    using S = CropStage<HS, VS, OUT>;
+    using C = Cfg<HS, VS, OUT>;
+    const int n = s.b1 - s.b0, nr = s.r1 - s.r0;
+    // stage offset of (row r0, byte b0) and crop offset of the same byte
+    const int sbase = (s.r0 - s.strip * C::SH) * S::PITCH + (s.b0 - (s.tile * C::TWY * S::BPP - S::MARGIN));
+    const long long obase = (long long)(s.r0 - s.y) * cp.out_pitch + (s.b0 - s.x * cp.bpp);
+    // per segment: head bytes to the destination's first dword boundary, ndw dwords, tail bytes.  (The crop rows lie at
+    // out_pitch apart, so the head differs between rows unless the pitch is a multiple of 4.)
+    const int nq_max = ((n >> 2) + 3) >> 2;      // 16-byte items of a segment, at most
+    const int per = nq_max + 1;                   // + the lane of the single bytes
+    const int total = S::NPL * nr * per;
+    for (int i = tid; i < total; i += nthreads) {
+        const int seg = i / per, q = i - seg * per;
+        const int pl = seg / nr, r = seg - pl * nr;
+        const int so = pl * C::SH * S::PITCH + sbase + r * S::PITCH;
+        uint8_t* const d = out + pl * cp.crop_plane + obase + (long long)r * cp.out_pitch;
+        int h = (int)((4u - ((unsigned)reinterpret_cast<uintptr_t>(d) & 3u)) & 3u);
+        if (h > n) h = n;
+        const int ndw = (n - h) >> 2;
+        if (q == nq_max) {
+            for (int b = 0; b < h; b++) d[b] = stage[so + b];
+            for (int b = h + 4 * ndw; b < n; b++) d[b] = stage[so + b];
+            continue;
+        }
+        const int j0 = 4 * q;
+        if (j0 >= ndw) continue;
+        const int sp = so + h + 4 * j0;
+        const uint32_t* const a = reinterpret_cast<const uint32_t*>(stage + (sp & ~3));
+        const uint32_t sh = (uint32_t)sp & 3u;
+        uint32_t w[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) w[k] = a[k];
+        const U4 v = {alignbyte(w[1], w[0], sh), alignbyte(w[2], w[1], sh), alignbyte(w[3], w[2], sh), alignbyte(w[4], w[3], sh)};
+        uint8_t* const dq = d + h + 4 * j0;
+        if (j0 + 4 <= ndw) store16(dq, v);
+        else {
+            const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+            for (int k = 0; k < ndw - j0; k++) *reinterpret_cast<uint32_t*>(dq + 4 * k) = vv[k];
+        }
+    }
+}
+
+// Zeros for the window rows at or below rows_covered (Q6): blockIdx.y = frame * planes + plane, blockIdx.x = crop row
+struct CropZero {
+    uint64_t fptr[SCATTER_MAX];
+    uint32_t y0[SCATTER_MAX];     // per frame: the window's first frame row
+    int rows_covered, crop_h, nbytes, out_pitch, nplanes, nframes;
+    long long crop_plane;
+};
+
 } // namespace zj
+

@@ -2661,6 +2661,14 @@ int zj_decoder_scan_blob(const zj_decoder* d, const void** blob, size_t* len)
     return ZJ_OK;
 }
 
+// library-internal (zj_api.cpp): crop windows from host or device planes, the entropy stage alone, an all-zero window.
+// Weak: the front-end's CPU-only builds (the sanitizer and fuzz harnesses, which stub the GPU calls) link without them.
+__attribute__((weak)) int zjint_crop_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                     int planes_on_device, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch);
+__attribute__((weak)) int zjint_scan_to_planes(zj_ctx* c, const zj_frame_desc* d, const void* blob, size_t blob_bytes,
+                                              const int16_t* planes[3], unsigned* status_bits);
+__attribute__((weak)) int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch);
+
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
     if (!d || !ctx || !out) return ZJ_ERR_ARG;
@@ -2763,6 +2771,55 @@ int zj_decoder_finish_pixels_batch(zj_decoder* const* ds, size_t n, zj_ctx* ctx,
 int zj_decoder_finish_pixels_device(zj_decoder* d, zj_ctx* ctx, uint8_t* d_out, size_t out_cap, size_t* out_len)
 {
     return finish_impl(d, ctx, d_out, out_cap, out_len, 1);
+}
+
+int zj_decoder_finish_pixels_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                         uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!zjint_crop_frame || !zjint_scan_to_planes || !zjint_crop_zeros) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    // a single-component file asked for a colour output: zeros, as finish_impl writes them (worker.rs:131)
+    const bool zeros = fd.in_components == 1 && fd.out_colorspace != ZJ_CS_GRAYSCALE;
+    // zj_crop_out_len's arithmetic, which is zj_out_len's for the window (the crop functions check the window in full)
+    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
+    const int ncomp = fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : ((fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : 4);
+    const size_t row = (size_t)w * (chw ? 1 : ncomp), pitch = out_pitch ? (size_t)out_pitch : row;
+    const size_t need = pitch * h * (chw ? 3 : 1);
+    if (out_len) *out_len = need;
+    if (w == 0 || h == 0 || pitch < row || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    if (zeros) {
+        if (d->scan_ready) { // as finish_impl: the scan is decoded all the same, a damaged one is an error here too
+            const uint8_t* src = d->src;
+            const size_t src_len = d->src_len;
+            const int rc2 = decode_all(d, src, src_len, false, false);
+            if (rc2) return rc2;
+        }
+        const int rc = zjint_crop_zeros(ctx, &fd, x, y, w, h, d_out, out_pitch);
+        return rc ? fail(d, rc, "crop zeros") : ZJ_OK;
+    }
+    if (d->scan_ready) {
+        const int16_t* planes[3] = {nullptr, nullptr, nullptr};
+        unsigned status = 0;
+        const int rc = zjint_scan_to_planes(ctx, &fd, d->blob_store.p, d->blob_len, planes, &status);
+        d->gpu_status = status;
+        if (rc == ZJ_OK) {
+            const int rc2 = zjint_crop_frame(ctx, &fd, planes[0], planes[1], planes[2], 1, x, y, w, h, d_out, out_pitch);
+            return rc2 ? fail(d, rc2, std::string("crop: ") + zj_strerror(rc2) + " " + zj_last_error(ctx)) : ZJ_OK;
+        }
+        if (rc != ZJ_RETRY_CPU) return fail(d, rc, std::string("GPU entropy stage: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+        // handed back: the CPU walker decodes the file, the planes go up strip by strip below
+        const uint8_t* src = d->src;
+        const size_t src_len = d->src_len;
+        const int rc2 = decode_all(d, src, src_len, false, false);
+        if (rc2) return rc2;
+    }
+    const int rc = zjint_crop_frame(ctx, &fd, d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr,
+                                    d->ncomp == 3 ? d->comps[2].coef : nullptr, 0, x, y, w, h, d_out, out_pitch);
+    return rc ? fail(d, rc, std::string("crop: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 
 unsigned zj_decoder_gpu_status(const zj_decoder* d) { return d ? d->gpu_status : 0; }

@@ -22,6 +22,9 @@ struct ZeroRows {
     int nr, nframes;
 };
 hipError_t launch_zero_rows(const ZeroRows& z, hipStream_t s);
+// crop windows (zj_decode_crops_device): the tile kernel over a launch's frames, and the window rows below rows_covered
+hipError_t launch_crop(int hs, int vs, int out, const CropParams& cp, hipStream_t s);
+hipError_t launch_crop_zero(const CropZero& z, hipStream_t s);
 int fused_slots_per_cu(int hs, int vs, int out, int variant, int fast, const Params& p); // 0: unknown
 const char* fused_kernel_name(int hs, int vs, int out, int variant, int fast, const Params& p);
 hipError_t launch_idct_strip(const int16_t* coeff, const int32_t qt[64], int16_t* out, long long nblocks,

@@ -206,4 +206,136 @@ inline void set_scatter(Params& p, const int16_t* const* y, const int16_t* const
     }
 }
 
+// ---- crop windows (zj_decode_crops_device; zj_device.h: CropParams) -------------------------------------------------
+struct CropPlan {
+    int w, h;             // window, pixels
+    int bpp;              // bytes per pixel of a frame row (CHW: 1, per plane)
+    int nplanes;          // 3 for CHW, else 1
+    int twy, sh;          // tile width (pixels) and strip height of the crop kernel (the generic fused kernel's tiles)
+    int row_bytes;        // bytes of a frame row (CHW: of one plane's row)
+    int tile_bytes;       // bpp x twy: a tile column's natural byte range in a row
+    int cut_tile[2], cut_lo[2]; // ownership exceptions: the tiles holding the row's two early-written RGB units (Q5)
+    size_t out_pitch;     // bytes between crop rows (CHW: of a plane)
+    size_t out_len;       // bytes of one crop (x 3 planes for CHW)
+};
+
+template <int HS, int VS>
+inline void crop_geo(CropPlan& cp, bool chroma)
+{
+    if (chroma) { using C = Cfg<HS, VS, OUT_RGB>; cp.twy = C::TWY; cp.sh = C::SH; }
+    else { using C = Cfg<HS, VS, OUT_GRAY>; cp.twy = C::TWY; cp.sh = C::SH; }
+}
+
+// The crop's geometry for a window of w x h pixels whose rows lie out_pitch bytes apart (0: tight).  The frame's own
+// out_pitch must be 0: a crop's layout is its own.
+inline int make_crop_plan(const zj_frame_desc* d, unsigned w, unsigned h, unsigned out_pitch, Plan& pl, CropPlan& cp)
+{
+    int rc = make_plan(d, pl);
+    if (rc) return rc;
+    if (d->out_pitch != 0 || w == 0 || h == 0 || w > d->width || h > d->height) return ZJ_ERR_ARG;
+    cp.w = (int)w; cp.h = (int)h;
+    cp.nplanes = pl.out == OUT_RGB_CHW ? 3 : 1;
+    cp.bpp = pl.out == OUT_RGB_CHW ? 1 : pl.ncomp_out;
+    if (pl.hs == 1 && pl.vs == 1) crop_geo<1, 1>(cp, pl.out != OUT_GRAY);
+    else if (pl.hs == 2 && pl.vs == 1) crop_geo<2, 1>(cp, pl.out != OUT_GRAY);
+    else if (pl.hs == 1 && pl.vs == 2) crop_geo<1, 2>(cp, pl.out != OUT_GRAY);
+    else crop_geo<2, 2>(cp, pl.out != OUT_GRAY);
+    cp.row_bytes = (int)pl.row_bytes;
+    cp.tile_bytes = cp.bpp * cp.twy;
+    const size_t tight = (size_t)w * cp.bpp;
+    cp.out_pitch = out_pitch ? (size_t)out_pitch : tight;
+    if (cp.out_pitch < tight || cp.out_pitch > (1u << 20)) return ZJ_ERR_ARG;
+    cp.out_len = cp.out_pitch * h * cp.nplanes;
+    // Who writes the end of a row (store_unit_generic, the rules of the crop kernel's stores): the last two 8-pixel units
+    // of an RGB row under the early-tail quirk (Q5) are written at p' and p' + 24, up to 88 bytes left of their own tile,
+    // and the zeros after them (Q6) by the last unit's tile.  Every other byte belongs to the tile its pixel lies in.
+    cp.cut_tile[0] = cp.cut_tile[1] = -1;
+    cp.cut_lo[0] = cp.cut_lo[1] = 0;
+    const int W = (int)d->width;
+    if (pl.out == OUT_RGB && !pl.plain && W >= 16) {
+        const long long P = (long long)pl.mcu_x * 8 * pl.hs, units = P >> 3;
+        long long elems = P / 16 - 1; if (elems < 0) elems = 0;
+        const long long position = 48 * elems;
+        long long diff = 64 - (3ll * W - position); if (diff < 0) diff = 0;
+        const long long pp = position > diff ? position - diff : 0;
+        cp.cut_tile[0] = (int)(8 * (units - 2) / cp.twy); cp.cut_lo[0] = (int)pp;
+        cp.cut_tile[1] = (int)(8 * (units - 1) / cp.twy); cp.cut_lo[1] = (int)(pp + 24);
+    }
+    return ZJ_OK;
+}
+
+// The window of an ALL-ZERO output: a single-component frame asked for a colour output, which the reference converts
+// nothing of and returns as zeros (worker.rs:131; the decoder's finish path).  No tile is decoded: the crop is zeros, laid
+// out by zj_out_len's arithmetic -- rows of w x ncomp_of(out_colorspace) bytes, CHW RGB: w bytes in each of 3 planes.
+inline bool zero_output(const zj_frame_desc* d) { return d && d->in_components == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE; }
+inline int make_zero_crop(const zj_frame_desc* d, unsigned w, unsigned h, unsigned out_pitch, CropPlan& cp)
+{
+    const int nc = d ? ncomp_of(d->out_colorspace) : 0;
+    if (!nc || d->width == 0 || d->height == 0 || d->width > 65535 || d->height > 65535) return ZJ_ERR_ARG;
+    if (d->out_pitch != 0 || w == 0 || h == 0 || w > d->width || h > d->height) return ZJ_ERR_ARG;
+    const bool chw = d->out_layout == ZJ_LAYOUT_CHW && d->out_colorspace == ZJ_CS_RGB;
+    cp = CropPlan{};
+    cp.w = (int)w; cp.h = (int)h;
+    cp.bpp = chw ? 1 : nc;
+    cp.nplanes = chw ? 3 : 1;
+    cp.row_bytes = (int)d->width * cp.bpp;
+    cp.cut_tile[0] = cp.cut_tile[1] = -1;
+    const size_t tight = (size_t)w * cp.bpp;
+    cp.out_pitch = out_pitch ? (size_t)out_pitch : tight;
+    if (cp.out_pitch < tight || cp.out_pitch > (1u << 20)) return ZJ_ERR_ARG;
+    cp.out_len = cp.out_pitch * h * cp.nplanes;
+    return ZJ_OK;
+}
+
+inline int crop_own(const CropPlan& cp, int k) { return crop_own_lo(k, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]); }
+
+// A window at (x, y) of a frame of plan pl: is it inside the frame, and which strips [s0, s1) and tile columns [k0, k1)
+// does it need (strips clipped to the ones that exist: the window's rows at or below rows_covered are zeros, Q6)
+inline int crop_window(const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, unsigned x, unsigned y, int& s0, int& s1, int& k0, int& k1)
+{
+    if ((size_t)x + cp.w > d->width || (size_t)y + cp.h > d->height) return ZJ_ERR_ARG;
+    s0 = (int)(y / cp.sh);
+    s1 = (int)((y + cp.h + cp.sh - 1) / cp.sh);
+    if (s1 > pl.n_strips) s1 = pl.n_strips;
+    if (s0 > s1) s0 = s1;
+    const int wb0 = (int)x * cp.bpp, wb1 = ((int)x + cp.w) * cp.bpp;
+    k0 = 0;
+    while (k0 < pl.tiles_per_row && crop_own(cp, k0 + 1) <= wb0) k0++;
+    k1 = k0;
+    while (k1 < pl.tiles_per_row && crop_own(cp, k1) < wb1) k1++;
+    return ZJ_OK;
+}
+
+// the launch's arguments for frames [f0, f0 + n) of a crop batch; strips / columns: the grid (the largest ranges)
+inline void fill_crop_params(const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, const int16_t* const* y,
+                             const int16_t* const* cb, const int16_t* const* cr, uint8_t* const* out, const unsigned* origins,
+                             size_t f0, int n, CropParams& c, int& nstrips, int& ncols)
+{
+    fill_params(d, pl, (size_t)n, nullptr, nullptr, nullptr, nullptr, 1, c.p);
+    set_scatter(c.p, y, cb, cr, out, f0, n);
+    // the tile decode writes the staging (zj_device.h: CropStage), rows at the staging's pitch
+    const int pitch = crop_stage_pitch(pl.out, cp.twy);
+    c.p.out_pitch = pitch;
+    c.p.plane_stride = (long long)pitch * cp.sh;
+    c.p.out_frame_stride = 0;
+    c.crop_w = cp.w; c.crop_h = cp.h;
+    c.out_pitch = (int)cp.out_pitch;
+    c.bpp = cp.bpp; c.row_bytes = cp.row_bytes; c.tile_bytes = cp.tile_bytes;
+    for (int i = 0; i < 2; i++) { c.cut_tile[i] = cp.cut_tile[i]; c.cut_lo[i] = cp.cut_lo[i]; }
+    c.crop_plane = (long long)cp.out_pitch * cp.h;
+    nstrips = ncols = 0;
+    for (int f = 0; f < SCATTER_MAX; f++) {
+        c.origin[f] = c.first[f] = 0;
+        if (f >= n) continue;
+        const unsigned x = origins[2 * (f0 + f)], yy = origins[2 * (f0 + f) + 1];
+        int s0 = 0, s1 = 0, k0 = 0, k1 = 0;
+        crop_window(d, pl, cp, x, yy, s0, s1, k0, k1); // (checked by the caller)
+        c.origin[f] = x | (yy << 16);
+        c.first[f] = (uint32_t)k0 | ((uint32_t)s0 << 16);
+        if (s1 - s0 > nstrips) nstrips = s1 - s0;
+        if (k1 - k0 > ncols) ncols = k1 - k0;
+    }
+    c.nstrips = nstrips; c.ncols = ncols;
+}
+
 } // namespace zj

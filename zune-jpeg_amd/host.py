@@ -160,6 +160,7 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_device_pci_bus_id", "zj_device_numa_node", "zj_bind_thread_to_numa_node", "zj_bind_thread_near_device",
     "zj_thread_numa_node", "zj_pool_slot_numa", "zj_multi_slot_numa",
     "zj_multi_decode_planes_batch", "zj_multi_decode_frames", "zj_multi_decode_frames_device",
+    "zj_crop_out_len", "zj_decode_crops_device", "zj_decoder_finish_pixels_crop_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -287,6 +288,11 @@ def lib():
     L.zj_decode_planes_device_strided.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, sz, sz, sz, vp]
     L.zj_decode_frames_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, vp]
     L.zj_pointer_device.argtypes = [vp]
+    L.zj_crop_out_len.restype = sz
+    L.zj_crop_out_len.argtypes = [C.POINTER(FrameDesc), C.c_uint, C.c_uint, C.c_uint]
+    L.zj_decode_crops_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, vp]
+    L.zj_decoder_finish_pixels_crop_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, sz, C.c_uint,
+                                                       C.POINTER(sz)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -319,6 +325,11 @@ def lib():
         L.zj_set_ablation.argtypes = [vp, C.c_int]
     _LIB = L
     return L
+
+
+def crop_out_len(desc, w, h, out_pitch=0):
+    """bytes of one w x h crop of frames of `desc` (zj_crop_out_len); 0: not a valid window"""
+    return lib().zj_crop_out_len(C.byref(desc), w, h, out_pitch)
 
 
 def device_count():
@@ -465,6 +476,18 @@ class Context:
         arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
         _check(lib().zj_decode_frames_device(self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), arr(d_out), stream),
                "zj_decode_frames_device", self._h)
+
+    def decode_crops_device(self, desc, d_y, d_cb, d_cr, origins, crop_w, crop_h, d_out, out_pitch=0, stream=None):
+        """Crop windows (zj_decode_crops_device): lists of device pointers as in decode_frames_device, origins = one (x, y)
+        per frame, every window crop_w x crop_h; each output gets crop_out_len(desc, crop_w, crop_h, out_pitch) bytes.
+        Asynchronous on `stream`."""
+        n = len(d_y)
+        if len(origins) != n or len(d_out) != n:
+            raise ValueError("one origin and one output per frame")
+        arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
+        org = (C.c_uint * (2 * n))(*[int(v) for xy in origins for v in xy])
+        _check(lib().zj_decode_crops_device(self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), org, crop_w, crop_h,
+                                            arr(d_out), out_pitch, stream), "zj_decode_crops_device", self._h)
 
     def decode_frames(self, desc, frames_planes, outs=None):
         """Host frames that are independent allocations (zj_decode_frames): frames_planes[f] = [y, cb, cr] arrays of frame
@@ -699,6 +722,17 @@ class Decoder:
         if rc:
             self._raise(rc)
         return out[: n.value]
+
+    def finish_pixels_crop_device(self, x, y, w, h, d_out, cap, out_pitch=0):
+        """Stage 2 cut to the w x h window at (x, y), pixels left in HBM at device pointer d_out (the contract of
+        zj_decode_crops_device); returns the crop's length in bytes."""
+        if self._ctx is None:
+            self._ctx = Context()
+        n = C.c_size_t(0)
+        rc = lib().zj_decoder_finish_pixels_crop_device(self._d, self._ctx.handle, x, y, w, h, d_out, cap, out_pitch, C.byref(n))
+        if rc:
+            self._raise(rc)
+        return n.value
 
     def finish_pixels_device(self, d_out, cap):
         """Stage 2 with the pixels left in HBM at device pointer d_out; returns their length in bytes."""

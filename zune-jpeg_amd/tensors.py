@@ -74,3 +74,44 @@ def decode_to_tensor(ctx, desc, planes, nframes=1, stream=None):
             p.record_stream(s)
     ctx.decode_planes_device(desc, nframes, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), storage.data_ptr(), s.cuda_stream)
     return view
+
+
+def crop_view_of(desc, storage, nframes, w, h):
+    """the dense [N, h, w, C] / [N, 3, h, w] / [N, h, w] view of nframes tight w x h crops back to back"""
+    ncomp = ColorSpace(desc.out_colorspace).num_components()
+    if desc.out_layout == LAYOUT_CHW and ncomp == 3:
+        return storage.view(nframes, 3, h, w)
+    if ncomp == 1:
+        return storage.view(nframes, h, w)
+    return storage.view(nframes, h, w, ncomp)
+
+
+def decode_crops_to_tensor(ctx, desc, frames, origins, size, stream=None):
+    """Crop windows as one dense uint8 tensor (zj_decode_crops_device): frames = a list of (Y, Cb, Cr) int16 CUDA tensors,
+    one frame each (Cb / Cr may be None for GRAYSCALE output), origins = one (x, y) per frame, size = (w, h) of every
+    window.  Returns [N, h, w, C], [N, 3, h, w] or [N, h, w]; crop n equals view[n, ..., y:y+h, x:x+w] of the full decode.
+    Stream and allocator rules as decode_to_tensor."""
+    import torch
+    w, h = size
+    n = len(frames)
+    if n == 0 or len(origins) != n:
+        raise ValueError("one origin per frame, at least one frame")
+    crop_len = lib().zj_crop_out_len(C.byref(desc), w, h, 0)
+    if crop_len == 0:
+        raise ValueError(f"{w}x{h} is not a valid crop of this frame descriptor")
+    dev = frames[0][0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        storage = torch.empty(n * crop_len, dtype=torch.uint8, device=dev)
+    if s != cur:
+        s.wait_stream(cur)
+        for fr in frames:
+            for p in fr:
+                if p is not None:
+                    p.record_stream(s)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    base = storage.data_ptr()
+    ctx.decode_crops_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames], [ptr(fr[2]) for fr in frames],
+                            origins, w, h, [base + i * crop_len for i in range(n)], 0, s.cuda_stream)
+    return crop_view_of(desc, storage, n, w, h)
