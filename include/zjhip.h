@@ -247,6 +247,41 @@ ZJ_API size_t zj_crop_out_len(const zj_frame_desc *d, unsigned crop_w, unsigned 
 ZJ_API int zj_decode_crops_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
                                   const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *origins,
                                   unsigned crop_w, unsigned crop_h, uint8_t *const *d_out, unsigned out_pitch, void *stream);
+/* Resize + normalise into a dense tensor: images of their own sizes to ONE out_w x out_h (1..8192), bilinear
+ * with half-pixel centres (align_corners=False, no antialiasing: strong downscales alias), in integer arithmetic with the
+ * source position truncated to 1/256 pixel.  Per channel c, v = the interpolated value x 65536 (0 .. 255 x 65536):
+ *   ZJ_DTYPE_F32   fl32(fl32(v * (scale[c] / 65536)) + bias[c]), two separately rounded float32 operations;
+ *                  scale = 1 / (255 std), bias = -mean / std is (x / 255 - mean) / std, the usual normalisation
+ *   ZJ_DTYPE_F16 / ZJ_DTYPE_BF16   that float32 rounded to nearest-even
+ *   ZJ_DTYPE_U8    (v + 32768) >> 16 (scale and bias unused)
+ * scale / bias: `channels` floats each (NULL: 1 / 0); one that is not finite is ZJ_ERR_ARG.  flip: one byte per image
+ * (NULL: none), non-zero mirrors the image's output columns.  The output is [N, C, out_h, out_w] (ZJ_TENSOR_NCHW) or
+ * [N, out_h, out_w, C] (ZJ_TENSOR_NHWC) of the dtype, image i at d_out + i * zj_resized_out_len's bytes.  Asynchronous on
+ * `stream` (NULL: the context's); nothing is launched after an argument error. */
+#define ZJ_DTYPE_F32 0
+#define ZJ_DTYPE_F16 1
+#define ZJ_DTYPE_BF16 2
+#define ZJ_DTYPE_U8 3
+#define ZJ_TENSOR_NCHW 0
+#define ZJ_TENSOR_NHWC 1
+/* bytes of one resized output of a frame of d (channels: 3 for RGB / YCbCr, 1 for GRAYSCALE); 0: not supported (RGBA /
+ * RGBX) or not a valid descriptor, size or dtype */
+ZJ_API size_t zj_resized_out_len(const zj_frame_desc *d, unsigned out_w, unsigned out_h, int dtype);
+/* n u8 images in device memory: d_in[i] its first byte, in_wh[2i], in_wh[2i + 1] its width and height (1..65535),
+ * in_pitch[i] the bytes between its rows (NULL or 0: tight); channels 1 or 3, in_layout ZJ_LAYOUT_HWC (interleaved) or
+ * ZJ_LAYOUT_CHW (3 planes, pitch x height bytes apart) */
+ZJ_API int zj_resize_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                            int channels, int in_layout, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                            const float *scale, const float *bias, const uint8_t *flip, void *d_out, void *stream);
+/* crop windows resized: frame f's window windows[4f .. 4f + 3] = x, y, w, h (each its own size, checked as in
+ * zj_decode_crops_device) and its output is zj_resize_device applied to EXACTLY the u8 crop zj_decode_crops_device writes
+ * for that window, in d's layout.  Planes and pointers as zj_decode_crops_device; RGBA / RGBX outputs are
+ * ZJ_ERR_UNSUPPORTED.  The crops pass through a device buffer of the context (launch groups of at most 256 MB of crops),
+ * whose reuse is ordered on the caller's stream.  Asynchronous on `stream`. */
+ZJ_API int zj_decode_crops_resized_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
+                                          const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *windows,
+                                          unsigned out_w, unsigned out_h, int dtype, int out_layout, const float *scale,
+                                          const float *bias, const uint8_t *flip, void *d_out, void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -355,6 +390,13 @@ ZJ_API int zj_decoder_finish_pixels_device(zj_decoder *d, zj_ctx *ctx, uint8_t *
  * *out_len = zj_crop_out_len(); out_cap below it is ZJ_ERR_ARG. */
 ZJ_API int zj_decoder_finish_pixels_crop_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y, unsigned w, unsigned h,
                                                 uint8_t *d_out, size_t out_cap, unsigned out_pitch, size_t *out_len);
+/* the decoder's last prepared file: the w x h window at (x, y) resized (zj_decode_crops_resized_device's contract; the crop
+ * is zj_decoder_finish_pixels_crop_device's), pixels left in HBM; stream ordering as zj_decoder_finish_pixels_device.
+ * *out_len = zj_resized_out_len(); out_cap below it is ZJ_ERR_ARG. */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y, unsigned w,
+                                                        unsigned h, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                        const float *scale, const float *bias, int flip, void *d_out,
+                                                        size_t out_cap, size_t *out_len);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

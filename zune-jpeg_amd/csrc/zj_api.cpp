@@ -15,9 +15,13 @@
 #include "../../include/zjhip.h"
 #include "zj_launch.h"
 #include "zj_plan.h"
+#include "zj_resize_launch.h"
 
 using namespace zj;
 static_assert(SCATTER_MAX == ZJ_SCATTER_MAX, "include/zjhip.h and zj_device.h disagree");
+static_assert(sizeof(CropParams) <= 4096 && sizeof(CropZero) <= 4096 && sizeof(ResizeParams) <= 4096, "kernel arguments: 4 KB");
+static_assert(RZ_F32 == ZJ_DTYPE_F32 && RZ_F16 == ZJ_DTYPE_F16 && RZ_BF16 == ZJ_DTYPE_BF16 && RZ_U8 == ZJ_DTYPE_U8,
+              "include/zjhip.h and zj_resize.h disagree");
 
 namespace {
 constexpr int N_SCRATCH = 4;
@@ -76,6 +80,10 @@ struct zj_ctx {
     uint32_t* d_ctl = nullptr;    // the slots' control words, contiguous: one clear, one copy back per call
     uint32_t* h_ctl = nullptr;    // pinned: HUFF_CTL_WORDS per slot
 
+    // the u8 crops of the resized crop decode (zj_decode_crops_resized_device): their buffer, and the event after the last
+    // resize that read it, recorded on whichever stream that call ran on (the next user waits for it on ITS stream)
+    void* rz_buf = nullptr; size_t rz_cap = 0;
+    hipEvent_t rz_done = nullptr; bool rz_used = false;
     bool scan_planes_only = false; // zjint_scan_to_planes: the entropy stage alone, the planes stay in the slot (crop windows)
     int huff_rounds = 0;          // synchronisation rounds of the last scan
     int huff_plane_slot = 0;
@@ -211,6 +219,8 @@ void zj_ctx_destroy(zj_ctx* c)
     if (c->hout) (void)hipFree(c->hout);
     if (c->d_ctl) (void)hipFree(c->d_ctl);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
+    if (c->rz_done) { if (c->rz_used) (void)hipEventSynchronize(c->rz_done); (void)hipEventDestroy(c->rz_done); }
+    if (c->rz_buf) (void)hipFree(c->rz_buf);
 
     for (hipStream_t st : {c->s_up, c->s_run, c->s_down})
         if (st) (void)hipStreamSynchronize(st);
@@ -746,6 +756,242 @@ int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy,
     z.nplanes = cp.nplanes; z.crop_plane = (long long)cp.out_pitch * cp.h; z.nframes = 1;
     z.fptr[0] = (uint64_t)(uintptr_t)d_out; z.y0[0] = yy;
     ZJ_HIP(c, launch_crop_zero(z, c->stream));
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+/* ---- resize + normalise ---------------------------------------------------------- */
+namespace {
+constexpr size_t RZ_GROUP_CAP = (size_t)256 << 20; // u8 crop bytes per launch group of zj_decode_crops_resized_device
+
+// channels of the resized output of descriptor d: 3 (RGB, YCbCr), 1 (GRAYSCALE), 0 (no such output: RGBA / RGBX)
+int resize_channels(const zj_frame_desc* d)
+{
+    if (!d) return 0;
+    if (d->out_colorspace == ZJ_CS_RGB || d->out_colorspace == ZJ_CS_YCBCR) return 3;
+    return d->out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0;
+}
+
+bool finite_f32(float v) { return v - v == 0.f; }
+
+// the output's arguments; s[] / b[]: the per-channel factors of the kernel (s_c = scale_c * 2^-16)
+int resize_out_args(unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                    int channels, float s[3], float b[3])
+{
+    if (out_w == 0 || out_h == 0 || out_w > (unsigned)RESIZE_MAX_OUT || out_h > (unsigned)RESIZE_MAX_OUT) return ZJ_ERR_ARG;
+    if (dtype < ZJ_DTYPE_F32 || dtype > ZJ_DTYPE_U8) return ZJ_ERR_ARG;
+    if (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC) return ZJ_ERR_ARG;
+    for (int k = 0; k < 3; k++) {
+        const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
+        if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
+        s[k] = sc * (1.f / 65536.f); // (exact: a power of two, above float32's smallest normal for every |scale| >= 2^-110)
+        b[k] = bi;
+    }
+    return ZJ_OK;
+}
+
+// images [0, n) -> the dense tensor at out, launches of up to RESIZE_BATCH images; wh[2i], wh[2i + 1]: image i's size,
+// pitch[i] (bytes between its rows) already resolved
+int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, int channels,
+                    int in_chw, unsigned out_w, unsigned out_h, int dtype, int nhwc, const float s[3], const float b[3],
+                    const uint8_t* flip, uint8_t* out, hipStream_t st)
+{
+    const size_t img_bytes = (size_t)channels * out_w * out_h * resize_elem_bytes(dtype);
+    ResizeParams p{};
+    p.out_w = (int)out_w; p.out_h = (int)out_h;
+    for (int k = 0; k < 3; k++) { p.scale[k] = s[k]; p.bias[k] = b[k]; }
+    p.groups = (int)((out_w + RESIZE_GROUP - 1) / RESIZE_GROUP);
+    p.rows = RESIZE_ITEMS / p.groups;
+    if (p.rows < 1) p.rows = 1;
+    if (p.rows > (int)out_h) p.rows = (int)out_h;
+    for (size_t f0 = 0; f0 < n; f0 += RESIZE_BATCH) {
+        const int m = (int)(n - f0 < (size_t)RESIZE_BATCH ? n - f0 : (size_t)RESIZE_BATCH);
+        p.nimg = m;
+        p.out = (uint64_t)(uintptr_t)(out + f0 * img_bytes);
+        for (int k = 0; k < RESIZE_BATCH / 32; k++) p.flip[k] = 0;
+        for (int i = 0; i < RESIZE_BATCH; i++) {
+            const size_t f = f0 + i;
+            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
+            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
+            p.pitch[i] = i < m ? pitch[f] : 0;
+            if (i < m && flip && flip[f]) p.flip[i >> 5] |= 1u << (i & 31);
+        }
+        ZJ_HIP(c, launch_resize(channels, in_chw, dtype, nhwc, p, st));
+    }
+    return ZJ_OK;
+}
+
+// the crop buffer, at least `bytes`, free for writing on stream st: st waits for the last resize that read it (whichever
+// stream that ran on); growing it waits for that resize on the host first
+int resize_scratch(zj_ctx* c, size_t bytes, hipStream_t st, uint8_t** p)
+{
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if (bytes > c->rz_cap) {
+        if (c->rz_used) ZJ_HIP(c, hipEventSynchronize(c->rz_done));
+        if (c->rz_buf) { ZJ_HIP(c, hipFree(c->rz_buf)); c->rz_buf = nullptr; c->rz_cap = 0; }
+        const size_t cap = bytes + bytes / 4 + 4096;
+        ZJ_HIP(c, hipMalloc(&c->rz_buf, cap));
+        c->rz_cap = cap;
+    } else if (c->rz_used) {
+        ZJ_HIP(c, hipStreamWaitEvent(st, c->rz_done, 0));
+    }
+    *p = (uint8_t*)c->rz_buf;
+    return ZJ_OK;
+}
+
+int resize_scratch_done(zj_ctx* c, hipStream_t st)
+{
+    ZJ_HIP(c, hipEventRecord(c->rz_done, st));
+    c->rz_used = true;
+    return ZJ_OK;
+}
+
+size_t crop_bytes(unsigned w, unsigned h, int channels) { return ((size_t)w * h * channels + 15) & ~(size_t)15; }
+} // namespace
+
+size_t zj_resized_out_len(const zj_frame_desc* d, unsigned out_w, unsigned out_h, int dtype)
+{
+    Plan pl;
+    CropPlan cp;
+    const int ch = resize_channels(d);
+    if (!ch) return 0;
+    if (zero_output(d) ? make_zero_crop(d, 1, 1, 0, cp) : make_crop_plan(d, 1, 1, 0, pl, cp)) return 0;
+    float s[3], b[3];
+    if (resize_out_args(out_w, out_h, dtype, ZJ_TENSOR_NCHW, nullptr, nullptr, ch, s, b)) return 0;
+    return (size_t)ch * out_w * out_h * resize_elem_bytes(dtype);
+}
+
+int zj_resize_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch,
+                     int channels, int in_layout, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                     const float* scale, const float* bias, const uint8_t* flip, void* d_out, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
+    if (channels != 1 && channels != 3) return ZJ_ERR_ARG;
+    if (in_layout != ZJ_LAYOUT_HWC && in_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    float s[3], b[3];
+    int rc = resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, channels, s, b);
+    if (rc) return rc;
+    const bool chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
+    std::vector<unsigned> pitch(n);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_in[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        const size_t row = (size_t)w * (chw ? 1 : channels);
+        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : (unsigned)row;
+        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
+        if (chw && (size_t)pitch[f] * h * 3 > ((size_t)1 << 31)) return ZJ_ERR_ARG; // (the kernel's plane offsets)
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return resize_launches(c, n, d_in, in_wh, pitch.data(), channels, chw, out_w, out_h, dtype, out_layout == ZJ_TENSOR_NHWC,
+                           s, b, flip, (uint8_t*)d_out, st);
+}
+
+int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                   const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                   unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                   const float* bias, const uint8_t* flip, void* d_out, void* stream)
+{
+    if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
+    const int ch = resize_channels(d);
+    if (!ch) return ZJ_ERR_UNSUPPORTED;
+    Plan pl;
+    CropPlan cp;
+    int rc = make_crop_plan(d, 1, 1, 0, pl, cp);
+    if (rc) return rc;
+    float s[3], b[3];
+    if ((rc = resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, ch, s, b))) return rc;
+    const bool chroma = pl.out != OUT_GRAY;
+    if (chroma && (!d_cb || !d_cr)) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < nframes; f++) {
+        const unsigned* w = windows + 4 * f;
+        if (w[2] == 0 || w[3] == 0) return ZJ_ERR_ARG;
+        CropPlan cw = cp;
+        cw.w = (int)w[2]; cw.h = (int)w[3];
+        int s0, s1, k0, k1;
+        if ((size_t)w[2] > d->width || (size_t)w[3] > d->height) return ZJ_ERR_ARG;
+        if ((rc = crop_window(d, pl, cw, w[0], w[1], s0, s1, k0, k1))) return rc;
+        if (!d_y[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
+        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const bool chw = pl.out == OUT_RGB_CHW;
+    const size_t img_bytes = (size_t)ch * out_w * out_h * resize_elem_bytes(dtype);
+    // launch groups: frames whose crops fit RZ_GROUP_CAP together (a larger window alone); the buffer sized for the largest
+    size_t need = 0;
+    for (size_t f = 0, g = 0; f < nframes; f++) {
+        const size_t cb = crop_bytes(windows[4 * f + 2], windows[4 * f + 3], ch);
+        g = g && g + cb > RZ_GROUP_CAP ? cb : g + cb;
+        if (g > need) need = g;
+    }
+    uint8_t* buf = nullptr;
+    if ((rc = resize_scratch(c, need, st, &buf))) return rc;
+    std::vector<uint8_t*> crops(nframes);
+    std::vector<unsigned> pitch(nframes), wh(2 * nframes);
+    for (size_t g0 = 0; g0 < nframes;) {
+        size_t g1 = g0, off = 0;
+        while (g1 < nframes) {
+            const size_t cb = crop_bytes(windows[4 * g1 + 2], windows[4 * g1 + 3], ch);
+            if (g1 > g0 && off + cb > RZ_GROUP_CAP) break;
+            crops[g1] = buf + off;
+            pitch[g1] = windows[4 * g1 + 2] * (chw ? 1 : ch);
+            wh[2 * g1] = windows[4 * g1 + 2]; wh[2 * g1 + 1] = windows[4 * g1 + 3];
+            off += cb;
+            g1++;
+        }
+        // the crops of the group, each tight at its own size (CropParams.out_pitch 0); the group before it has been read by
+        // then (the same stream)
+        for (size_t f0 = g0; f0 < g1; f0 += SCATTER_MAX) {
+            const int n = (int)(g1 - f0 < (size_t)SCATTER_MAX ? g1 - f0 : (size_t)SCATTER_MAX);
+            CropParams p;
+            int nstrips = 0, ncols = 0;
+            fill_crop_params_win(d, pl, cp, d_y, chroma ? d_cb : nullptr, chroma ? d_cr : nullptr, crops.data(), windows, 4,
+                                 f0, n, p, nstrips, ncols);
+            CropZero z{};
+            z.rows_covered = pl.rows_covered; z.out_pitch = 0; z.nplanes = cp.nplanes; z.bpp = cp.bpp;
+            bool any = false;
+            for (int f = 0; f < n; f++) {
+                const unsigned* w = windows + 4 * (f0 + f);
+                z.fptr[f] = (uint64_t)(uintptr_t)crops[f0 + f];
+                z.y0[f] = w[1];
+                z.size[f] = w[2] | (w[3] << 16);
+                if ((int)w[3] > z.crop_h) z.crop_h = (int)w[3];
+                if ((int)(w[2] * cp.bpp) > z.nbytes) z.nbytes = (int)(w[2] * cp.bpp);
+                any = any || (long long)w[1] + w[3] > pl.rows_covered;
+            }
+            z.nframes = n;
+            if (any) ZJ_HIP(c, launch_crop_zero(z, st));
+            ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, st));
+        }
+        if ((rc = resize_launches(c, g1 - g0, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h,
+                                  dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr,
+                                  (uint8_t*)d_out + g0 * img_bytes, st)))
+            return rc;
+        if ((rc = resize_scratch_done(c, st))) return rc;
+        g0 = g1;
+    }
+    return ZJ_OK;
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_resized_crop_device): the crop buffer for one crop of `bytes` on
+// the context stream, and the resize of that crop into d_out (on the context stream, synchronised)
+int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t** p)
+{
+    if (!c || !p) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    return resize_scratch(c, bytes, c->stream, p);
+}
+
+int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, unsigned out_w,
+                     unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, void* d_out)
+{
+    const unsigned wh[2] = {w, h};
+    const uint8_t fl = flip ? 1 : 0;
+    int rc = zj_resize_device(c, 1, &in, wh, nullptr, channels, in_layout, out_w, out_h, dtype, out_layout, scale, bias, &fl,
+                              d_out, nullptr);
+    if (rc) return rc;
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }

@@ -96,9 +96,13 @@ __global__ __launch_bounds__((Cfg<HS, VS, OUT>::NT), (CropOccupancy<HS, VS, OUT>
 __global__ __launch_bounds__(256) void zj_crop_zero_kernel(const CropZero z)
 {
     const int fr = (int)blockIdx.y / z.nplanes, pl = (int)blockIdx.y - fr * z.nplanes, r = (int)blockIdx.x;
-    if ((int)z.y0[fr] + r < z.rows_covered) return;
-    uint8_t* const p = ZJ_GLOBAL_PTR(uint8_t, z.fptr[fr]) + (long long)pl * z.crop_plane + (long long)r * z.out_pitch;
-    const unsigned n = (unsigned)z.nbytes;
+    const uint32_t wh = z.size[fr];
+    const int h = wh ? (int)(wh >> 16) : z.crop_h, nbytes = wh ? (int)(wh & 0xffffu) * z.bpp : z.nbytes;
+    if (r >= h || (int)z.y0[fr] + r < z.rows_covered) return;
+    const int pitch = z.out_pitch ? z.out_pitch : nbytes;
+    const long long plane = z.out_pitch ? z.crop_plane : (long long)pitch * h;
+    uint8_t* const p = ZJ_GLOBAL_PTR(uint8_t, z.fptr[fr]) + (long long)pl * plane + (long long)r * pitch;
+    const unsigned n = (unsigned)nbytes;
     unsigned head = (16u - ((unsigned)reinterpret_cast<uintptr_t>(p) & 15u)) & 15u;
     if (head > n) head = n;
     const unsigned nq = (n - head) >> 4, tail = head + (nq << 4);

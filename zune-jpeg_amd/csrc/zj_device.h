@@ -1924,19 +1924,20 @@ struct CropStage {
 };
 
 // The launch's arguments: the tile decode's Params (its out_pitch / plane_stride are the STAGING's, zero_fill 1, always the
-// scattered form), plus the window.  Params itself is unchanged: the fused kernels keep their code.
+// scattered form), plus the windows.  Params itself is unchanged: the fused kernels keep their code.
 struct CropParams {
     Params p;
-    int crop_w, crop_h;           // window, pixels
+    int crop_w, crop_h;           // window, pixels, of a uniform launch (zj_decode_crops_device); the kernel reads size[]
     int ncols, nstrips;           // grid: tile columns / strips per frame (the widest range over the launch's frames)
-    int out_pitch;                // bytes between crop rows (CHW: between the rows of a plane)
+    int out_pitch;                // bytes between crop rows (CHW: between the rows of a plane); 0: each crop tight (w x bpp)
     int bpp;                      // bytes per pixel of a frame row (CHW: 1, per plane)
     int row_bytes;                // bytes of a frame row (CHW: of a plane's row)
     int tile_bytes;               // bpp x tile width
     int cut_tile[2], cut_lo[2];   // ownership exceptions at a row's end (zj_plan.h: make_crop_plan); tile -1 = none
-    long long crop_plane;         // CHW: bytes between the crop's planes (out_pitch x crop_h)
+    long long crop_plane;         // CHW: bytes between the crop's planes (out_pitch x crop_h; out_pitch 0: pitch x h)
     uint32_t origin[SCATTER_MAX]; // per frame: x | y << 16
     uint32_t first[SCATTER_MAX];  // per frame: first tile column | first strip << 16
+    uint32_t size[SCATTER_MAX];   // per frame: the window, w | h << 16
 };
 
 // first byte of a frame row that tile column k owns (k == tiles per row: the row's end)
@@ -1950,7 +1951,8 @@ ZJ_HD int crop_own_lo(const int k, const int tile_bytes, const int row_bytes, co
 }
 
 // What one crop workgroup copies: frame rows [r0, r1) of its strip, row bytes [b0, b1) (CHW: of each plane)
-struct CropSpan { int frame, strip, tile, r0, r1, b0, b1, x, y; };
+// (pitch / plane: the crop's bytes between rows and between planes)
+struct CropSpan { int frame, strip, tile, r0, r1, b0, b1, x, y, pitch; long long plane; };
 
 // the workgroup (frame fz, strip index sy, column index sx) of a crop launch; false: nothing to do (workgroup-uniform:
 // a frame whose window spans fewer strips or columns than the launch's grid leaves the rest of its workgroups idle)
@@ -1958,19 +1960,22 @@ template <int HS, int VS, int OUT>
 ZJ_DEV bool crop_locate(const CropParams& cp, const int fz, const int sy, const int sx, CropSpan& s)
 {
     using C = Cfg<HS, VS, OUT>;
-    const uint32_t o = cp.origin[fz], f = cp.first[fz];
+    const uint32_t o = cp.origin[fz], f = cp.first[fz], wh = cp.size[fz];
+    const int cw = (int)(wh & 0xffffu), ch = (int)(wh >> 16);
     s.frame = fz; s.x = (int)(o & 0xffffu); s.y = (int)(o >> 16);
+    s.pitch = cp.out_pitch ? cp.out_pitch : cw * cp.bpp;
+    s.plane = cp.out_pitch ? cp.crop_plane : (long long)s.pitch * ch;
     s.strip = (int)(f >> 16) + sy; s.tile = (int)(f & 0xffffu) + sx;
     if (s.strip >= cp.p.n_strips || s.tile >= cp.p.tiles_per_row) return false;
     s.r0 = s.strip * C::SH > s.y ? s.strip * C::SH : s.y;
     int r1 = s.strip * C::SH + C::SH;
-    if (r1 > s.y + cp.crop_h) r1 = s.y + cp.crop_h;
+    if (r1 > s.y + ch) r1 = s.y + ch;
     if (r1 > cp.p.height) r1 = cp.p.height;
     s.r1 = r1;
     if (s.r0 >= s.r1) return false;
     const int lo = crop_own_lo(s.tile, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]);
     const int hi = crop_own_lo(s.tile + 1, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]);
-    const int wb0 = s.x * cp.bpp, wb1 = (s.x + cp.crop_w) * cp.bpp;
+    const int wb0 = s.x * cp.bpp, wb1 = (s.x + cw) * cp.bpp;
     s.b0 = lo > wb0 ? lo : wb0;
     s.b1 = hi < wb1 ? hi : wb1;
     return s.b0 < s.b1;
@@ -1997,7 +2002,7 @@ ZJ_DEV void crop_copyout(const CropParams& cp, const CropSpan& s, const int tid,
     const int n = s.b1 - s.b0, nr = s.r1 - s.r0;
     // stage offset of (row r0, byte b0) and crop offset of the same byte
     const int sbase = (s.r0 - s.strip * C::SH) * S::PITCH + (s.b0 - (s.tile * C::TWY * S::BPP - S::MARGIN));
-    const long long obase = (long long)(s.r0 - s.y) * cp.out_pitch + (s.b0 - s.x * cp.bpp);
+    const long long obase = (long long)(s.r0 - s.y) * s.pitch + (s.b0 - s.x * cp.bpp);
     // per segment: head bytes to the destination's first dword boundary, ndw dwords, tail bytes.  (The crop rows lie at
     // out_pitch apart, so the head differs between rows unless the pitch is a multiple of 4.)
     const int nq_max = ((n >> 2) + 3) >> 2;      // 16-byte items of a segment, at most
@@ -2007,7 +2012,7 @@ ZJ_DEV void crop_copyout(const CropParams& cp, const CropSpan& s, const int tid,
         const int seg = i / per, q = i - seg * per;
         const int pl = seg / nr, r = seg - pl * nr;
         const int so = pl * C::SH * S::PITCH + sbase + r * S::PITCH;
-        uint8_t* const d = out + pl * cp.crop_plane + obase + (long long)r * cp.out_pitch;
+        uint8_t* const d = out + pl * s.plane + obase + (long long)r * s.pitch;
         int h = (int)((4u - ((unsigned)reinterpret_cast<uintptr_t>(d) & 3u)) & 3u);
         if (h > n) h = n;
         const int ndw = (n - h) >> 2;
@@ -2038,8 +2043,10 @@ ZJ_DEV void crop_copyout(const CropParams& cp, const CropSpan& s, const int tid,
 struct CropZero {
     uint64_t fptr[SCATTER_MAX];
     uint32_t y0[SCATTER_MAX];     // per frame: the window's first frame row
-    int rows_covered, crop_h, nbytes, out_pitch, nplanes, nframes;
+    int rows_covered, crop_h, nbytes, out_pitch, nplanes, nframes; // crop_h: the grid (the tallest window)
     long long crop_plane;
+    uint32_t size[SCATTER_MAX];   // per frame: the window, w | h << 16 (0: crop_h rows of nbytes)
+    int bpp;                      // bytes per pixel of a crop row (CHW: 1)
 };
 
 } // namespace zj

@@ -2668,6 +2668,11 @@ __attribute__((weak)) int zjint_crop_frame(zj_ctx* c, const zj_frame_desc* d, co
 __attribute__((weak)) int zjint_scan_to_planes(zj_ctx* c, const zj_frame_desc* d, const void* blob, size_t blob_bytes,
                                               const int16_t* planes[3], unsigned* status_bits);
 __attribute__((weak)) int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch);
+// ... and the resized crop's buffer and resize
+__attribute__((weak)) int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t** p);
+__attribute__((weak)) int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout,
+                                           unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                           const float* bias, int flip, void* d_out);
 
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
@@ -2820,6 +2825,38 @@ int zj_decoder_finish_pixels_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x,
     const int rc = zjint_crop_frame(ctx, &fd, d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr,
                                     d->ncomp == 3 ? d->comps[2].coef : nullptr, 0, x, y, w, h, d_out, out_pitch);
     return rc ? fail(d, rc, std::string("crop: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+}
+
+int zj_decoder_finish_pixels_resized_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                                 unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                                 const float* bias, int flip, void* d_out, size_t out_cap, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int ch = (fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : (fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0);
+    if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
+    // zj_resized_out_len's arithmetic (this file links without the device half of the library in its CPU-only builds)
+    const int esz = dtype == ZJ_DTYPE_F32 ? 4 : (dtype == ZJ_DTYPE_F16 || dtype == ZJ_DTYPE_BF16) ? 2 : (dtype == ZJ_DTYPE_U8 ? 1 : 0);
+    const bool size_ok = out_w >= 1 && out_h >= 1 && out_w <= 8192 && out_h <= 8192;
+    const size_t need = esz && size_ok ? (size_t)ch * out_w * out_h * esz : 0;
+    if (out_len) *out_len = need;
+    if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    // the crop in the context's buffer (zj_decoder_finish_pixels_crop_device checks the window), then the resize
+    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
+    const size_t crop_len = (size_t)w * h * ch;
+    if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
+    uint8_t* crop = nullptr;
+    int rc = zjint_resize_scratch(ctx, crop_len, &crop);
+    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    size_t got = 0;
+    if ((rc = zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, crop_len, 0, &got))) return rc;
+    rc = zjint_resize_one(ctx, crop, w, h, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype, out_layout, scale, bias,
+                          flip, d_out);
+    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 
 unsigned zj_decoder_gpu_status(const zj_decoder* d) { return d ? d->gpu_status : 0; }

@@ -306,10 +306,12 @@ inline int crop_window(const zj_frame_desc* d, const Plan& pl, const CropPlan& c
     return ZJ_OK;
 }
 
-// the launch's arguments for frames [f0, f0 + n) of a crop batch; strips / columns: the grid (the largest ranges)
-inline void fill_crop_params(const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, const int16_t* const* y,
-                             const int16_t* const* cb, const int16_t* const* cr, uint8_t* const* out, const unsigned* origins,
-                             size_t f0, int n, CropParams& c, int& nstrips, int& ncols)
+// the launch's arguments for frames [f0, f0 + n) of a crop batch; strips / columns: the grid (the largest ranges).
+// win: per frame x, y (stride 2: every window cp.w x cp.h, the crop's pitch cp.out_pitch) or x, y, w, h (stride 4: each
+// crop tight at its own size, CropParams.out_pitch 0)
+inline void fill_crop_params_win(const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, const int16_t* const* y,
+                                 const int16_t* const* cb, const int16_t* const* cr, uint8_t* const* out, const unsigned* win,
+                                 const int stride, size_t f0, int n, CropParams& c, int& nstrips, int& ncols)
 {
     fill_params(d, pl, (size_t)n, nullptr, nullptr, nullptr, nullptr, 1, c.p);
     set_scatter(c.p, y, cb, cr, out, f0, n);
@@ -319,23 +321,35 @@ inline void fill_crop_params(const zj_frame_desc* d, const Plan& pl, const CropP
     c.p.plane_stride = (long long)pitch * cp.sh;
     c.p.out_frame_stride = 0;
     c.crop_w = cp.w; c.crop_h = cp.h;
-    c.out_pitch = (int)cp.out_pitch;
+    c.out_pitch = stride == 4 ? 0 : (int)cp.out_pitch;
     c.bpp = cp.bpp; c.row_bytes = cp.row_bytes; c.tile_bytes = cp.tile_bytes;
     for (int i = 0; i < 2; i++) { c.cut_tile[i] = cp.cut_tile[i]; c.cut_lo[i] = cp.cut_lo[i]; }
     c.crop_plane = (long long)cp.out_pitch * cp.h;
     nstrips = ncols = 0;
     for (int f = 0; f < SCATTER_MAX; f++) {
-        c.origin[f] = c.first[f] = 0;
+        c.origin[f] = c.first[f] = c.size[f] = 0;
         if (f >= n) continue;
-        const unsigned x = origins[2 * (f0 + f)], yy = origins[2 * (f0 + f) + 1];
+        const unsigned* const wf = win + (size_t)stride * (f0 + f);
+        const unsigned x = wf[0], yy = wf[1];
+        CropPlan cw = cp;
+        if (stride == 4) { cw.w = (int)wf[2]; cw.h = (int)wf[3]; }
         int s0 = 0, s1 = 0, k0 = 0, k1 = 0;
-        crop_window(d, pl, cp, x, yy, s0, s1, k0, k1); // (checked by the caller)
+        crop_window(d, pl, cw, x, yy, s0, s1, k0, k1); // (checked by the caller)
         c.origin[f] = x | (yy << 16);
         c.first[f] = (uint32_t)k0 | ((uint32_t)s0 << 16);
+        c.size[f] = (uint32_t)cw.w | ((uint32_t)cw.h << 16);
         if (s1 - s0 > nstrips) nstrips = s1 - s0;
         if (k1 - k0 > ncols) ncols = k1 - k0;
     }
     c.nstrips = nstrips; c.ncols = ncols;
+}
+
+// ... every window cp.w x cp.h at origins[2f], origins[2f + 1] (zj_decode_crops_device)
+inline void fill_crop_params(const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, const int16_t* const* y,
+                             const int16_t* const* cb, const int16_t* const* cr, uint8_t* const* out, const unsigned* origins,
+                             size_t f0, int n, CropParams& c, int& nstrips, int& ncols)
+{
+    fill_crop_params_win(d, pl, cp, y, cb, cr, out, origins, 2, f0, n, c, nstrips, ncols);
 }
 
 } // namespace zj

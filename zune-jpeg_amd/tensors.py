@@ -13,7 +13,7 @@ lines -- DESIGN.md 4.0) the view is simply strided over the padding; `.contiguou
 import copy
 import ctypes as C
 
-from .host import LAYOUT_CHW, ColorSpace, lib
+from .host import DTYPE_BF16, DTYPE_F16, DTYPE_F32, DTYPE_U8, LAYOUT_CHW, LAYOUT_HWC, TENSOR_NCHW, TENSOR_NHWC, ColorSpace, lib
 
 
 def row_bytes(desc):
@@ -115,3 +115,117 @@ def decode_crops_to_tensor(ctx, desc, frames, origins, size, stream=None):
     ctx.decode_crops_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames], [ptr(fr[2]) for fr in frames],
                             origins, w, h, [base + i * crop_len for i in range(n)], 0, s.cuda_stream)
     return crop_view_of(desc, storage, n, w, h)
+
+
+def _resize_dtype(dtype):
+    import torch
+    codes = {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16, torch.uint8: DTYPE_U8}
+    if dtype not in codes:
+        raise ValueError(f"resized outputs are float32, float16, bfloat16 or uint8, not {dtype}")
+    return codes[dtype]
+
+
+def normalize_factors(channels, mean=None, std=None):
+    """torchvision-style mean / std (of the [0, 1] image) -> the float32 scale and bias of zj_resize_device:
+    y = x * scale + bias for x in [0, 255] units, scale = 1 / (255 std), bias = -mean / std (None: 0 and 1)"""
+    import numpy as np
+    m = np.broadcast_to(np.asarray(0.0 if mean is None else mean, np.float64), (channels,))
+    sd = np.broadcast_to(np.asarray(1.0 if std is None else std, np.float64), (channels,))
+    return [float(v) for v in np.float32(1.0 / (255.0 * sd))], [float(v) for v in np.float32(-m / sd)]
+
+
+def _resized_out(n, channels, size, dtype, layout, dev, s):
+    import torch
+    ow, oh = size
+    if layout not in ("NCHW", "NHWC"):
+        raise ValueError("layout is 'NCHW' or 'NHWC'")
+    shape = (n, channels, oh, ow) if layout == "NCHW" else (n, oh, ow, channels)
+    with torch.cuda.stream(s):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+
+def _on_stream(s, cur, tensors):
+    if s != cur:
+        s.wait_stream(cur)
+        for t in tensors:
+            if t is not None:
+                t.record_stream(s)
+
+
+def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
+                                   flips=None, stream=None):
+    """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
+    (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
+    per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
+    ("NHWC") of `dtype` (default bfloat16); C = 3 for RGB / YCbCr, 1 for GRAYSCALE.  mean / std: torchvision's Normalize
+    of the [0, 1] image (None: the [0, 1] image itself); unused for uint8.  flips: one bool per frame (horizontal).
+    Stream and allocator rules as decode_to_tensor."""
+    import torch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(frames)
+    if n == 0 or len(windows) != n:
+        raise ValueError("one window per frame, at least one frame")
+    ow, oh = size
+    if lib().zj_resized_out_len(C.byref(desc), ow, oh, code) == 0:
+        raise ValueError(f"{ow}x{oh} {dtype} is not a supported resized output of this frame descriptor")
+    channels = ColorSpace(desc.out_colorspace).num_components()
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = frames[0][0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    _on_stream(s, cur, [p for fr in frames for p in fr])
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
+                                    [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
+                                    TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
+                                    s.cuda_stream)
+    return out
+
+
+def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
+                     stream=None):
+    """u8 CUDA images of their own sizes resized and normalised into ONE dense tensor (zj_resize_device): images =
+    [H, W, C] or [H, W] tensors (in_layout "HWC"), or [3, H, W] ("CHW"); rows may be strided, pixels not.  Output,
+    mean / std, flips and streams as decode_resized_crops_to_tensor."""
+    import torch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(images)
+    if n == 0:
+        raise ValueError("at least one image")
+    imgs, sizes, pitches = [], [], []
+    for im in images:
+        if im.dtype != torch.uint8 or not im.is_cuda:
+            raise ValueError("images are uint8 CUDA tensors")
+        if in_layout == "CHW":
+            if im.dim() != 3 or im.shape[0] != 3:
+                raise ValueError("CHW images are [3, H, W]")
+            if im.stride(2) != 1 or im.stride(0) != im.stride(1) * im.shape[1]:
+                im = im.contiguous()
+            h, w, pitch = im.shape[1], im.shape[2], im.stride(1)
+        else:
+            im3 = im if im.dim() == 3 else im.unsqueeze(-1)
+            if im3.dim() != 3 or im3.shape[2] not in (1, 3):
+                raise ValueError("HWC images are [H, W, 3], [H, W, 1] or [H, W]")
+            if im3.stride(2) != 1 or im3.stride(1) != im3.shape[2]:
+                im3 = im3.contiguous()
+            im = im3
+            h, w, pitch = im.shape[0], im.shape[1], im.stride(0)
+        imgs.append(im)
+        sizes.append((w, h))
+        pitches.append(pitch)
+    channels = 3 if in_layout == "CHW" else imgs[0].shape[2]
+    if any((3 if in_layout == "CHW" else im.shape[2]) != channels for im in imgs):
+        raise ValueError("every image has the same channels")
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    _on_stream(s, cur, imgs)
+    ctx.resize_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
+                      size[0], size[1], code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias,
+                      flips, pitches, s.cuda_stream)
+    return out
