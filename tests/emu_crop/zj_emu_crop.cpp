@@ -74,7 +74,13 @@ static void run_crop(const CropParams& cp, uint8_t stage_poison)
                 t.y = (const int16_t*)p.fptr[fz][0]; t.cb = (const int16_t*)p.fptr[fz][1]; t.cr = (const int16_t*)p.fptr[fz][2];
                 t.out = crop_stage_base<HS, VS, OUT>(stage, s);
                 tile_to_stage<HS, VS, OUT>(p, t, lds);
-                for (int tid = 0; tid < C::NT; tid++) crop_copyout<HS, VS, OUT>(cp, s, tid, C::NT, stage, (uint8_t*)p.fptr[fz][3]);
+                uint8_t* const out = (uint8_t*)p.fptr[fz][3];
+                if (s.b0 < s.b1)
+                    for (int tid = 0; tid < C::NT; tid++) crop_copyout<HS, VS, OUT>(cp, s, tid, C::NT, stage, out);
+                if (s.c0 < s.c1) {
+                    s.b0 = s.c0; s.b1 = s.c1;
+                    for (int tid = 0; tid < C::NT; tid++) crop_copyout<HS, VS, OUT>(cp, s, tid, C::NT, stage, out);
+                }
             }
 }
 
@@ -152,10 +158,13 @@ extern "C" int zjec_crop_window(const zj_frame_desc* d, unsigned x, unsigned y, 
 }
 
 // Brute force for the plan tests: which tile column writes each byte of a frame row (strip 0, frame 0), found by decoding
-// every column of strip 0 into the staging twice, over two different poisons (a byte is written where both agree).
-// owner[b] = column, -1 = nobody, -2 = more than one column.  Returns the number of columns.
+// every column k >= k_lo of strip 0 into the staging twice, over two different poisons (a byte is written where both agree).
+// owner[b] = column, -1 = nobody, -2 = more than one column, -3 = not examined: b left of column k_lo's natural range.  (A
+// column writes nothing right of its own natural range, so the writers of every byte from there on are among the columns
+// decoded, k_lo - 1 on.)
+// Returns the number of columns.
 template <int HS, int VS, int OUT>
-static void owners_t(const Params& p, const Plan& pl, int* owner)
+static void owners_t(const Params& p, const Plan& pl, int k_lo, int* owner)
 {
     using C = Cfg<HS, VS, OUT>;
     using S = CropStage<HS, VS, OUT>;
@@ -163,8 +172,8 @@ static void owners_t(const Params& p, const Plan& pl, int* owner)
     char* lds = (char*)(((uintptr_t)lds_mem.data() + 15) & ~(uintptr_t)15);
     std::vector<uint8_t> a(S::BYTES + 32), b(S::BYTES + 32);
     const int rb = (int)pl.row_bytes;
-    for (int i = 0; i < rb; i++) owner[i] = -1;
-    for (int k = 0; k < pl.tiles_per_row; k++) {
+    for (int i = 0; i < rb; i++) owner[i] = i < k_lo * C::TWY * S::BPP ? -3 : -1;
+    for (int k = k_lo > 0 ? k_lo - 1 : 0; k < pl.tiles_per_row; k++) {
         CropSpan s{};
         s.frame = 0; s.strip = 0; s.tile = k;
         uint8_t* st[2] = {(uint8_t*)(((uintptr_t)a.data() + 15) & ~(uintptr_t)15), (uint8_t*)(((uintptr_t)b.data() + 15) & ~(uintptr_t)15)};
@@ -179,13 +188,13 @@ static void owners_t(const Params& p, const Plan& pl, int* owner)
         const int base = k * C::TWY * S::BPP - S::MARGIN;
         for (int i = 0; i < S::PITCH; i++) {
             const int bb = base + i;
-            if (bb < 0 || bb >= rb || st[0][i] != st[1][i]) continue; // (row 0 of the staging)
+            if (bb < 0 || bb >= rb || owner[bb] == -3 || st[0][i] != st[1][i]) continue; // (row 0 of the staging)
             owner[bb] = owner[bb] == -1 ? k : -2;
         }
     }
 }
 
-extern "C" int zjec_row_owners(const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr, int* owner)
+extern "C" int zjec_row_owners(const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr, int k_lo, int* owner)
 {
     Plan pl;
     int rc = make_plan(d, pl);
@@ -193,7 +202,7 @@ extern "C" int zjec_row_owners(const zj_frame_desc* d, const int16_t* y, const i
     if (pl.n_strips < 1) return ZJ_ERR_ARG;
     Params p;
     fill_params(d, pl, 1, y, cb, cr, nullptr, 1, p);
-#define ZJ_CASE(H, V, O) if (pl.hs == H && pl.vs == V && pl.out == O) { using S = CropStage<H, V, O>; p.out_pitch = S::PITCH; p.plane_stride = (long long)S::PITCH * Cfg<H, V, O>::SH; owners_t<H, V, O>(p, pl, owner); return pl.tiles_per_row; }
+#define ZJ_CASE(H, V, O) if (pl.hs == H && pl.vs == V && pl.out == O) { using S = CropStage<H, V, O>; p.out_pitch = S::PITCH; p.plane_stride = (long long)S::PITCH * Cfg<H, V, O>::SH; owners_t<H, V, O>(p, pl, k_lo, owner); return pl.tiles_per_row; }
     ZJ_CASE(1, 1, OUT_RGB) ZJ_CASE(1, 1, OUT_GRAY) ZJ_CASE(1, 1, OUT_YCBCR)
     ZJ_CASE(2, 1, OUT_RGB) ZJ_CASE(2, 1, OUT_GRAY) ZJ_CASE(2, 1, OUT_YCBCR)
     ZJ_CASE(1, 2, OUT_RGB) ZJ_CASE(1, 2, OUT_GRAY) ZJ_CASE(1, 2, OUT_YCBCR)
@@ -202,4 +211,22 @@ extern "C" int zjec_row_owners(const zj_frame_desc* d, const int16_t* y, const i
     ZJ_CASE(1, 1, OUT_RGB_CHW) ZJ_CASE(2, 1, OUT_RGB_CHW) ZJ_CASE(1, 2, OUT_RGB_CHW) ZJ_CASE(2, 2, OUT_RGB_CHW)
 #undef ZJ_CASE
     return ZJ_ERR_UNSUPPORTED;
+}
+
+// The plan's side of the write map: owner[b] = the tile column whose owned bytes (zj_plan.h: crop_spans) hold byte b
+// of a frame row, -1 = no column, -2 = more than one.  Returns the number of columns.
+extern "C" int zjec_plan_owners(const zj_frame_desc* d, int* owner)
+{
+    Plan pl;
+    CropPlan cp;
+    int rc = make_crop_plan(d, 1, 1, 0, pl, cp);
+    if (rc) return rc;
+    for (int b = 0; b < cp.row_bytes; b++) owner[b] = -1;
+    for (int k = 0; k < pl.tiles_per_row; k++) {
+        int a0, a1, c0, c1;
+        crop_spans(cp, k, a0, a1, c0, c1);
+        for (int b = a0; b < a1; b++) owner[b] = owner[b] == -1 ? k : -2;
+        for (int b = c0; b < c1; b++) owner[b] = owner[b] == -1 ? k : -2;
+    }
+    return pl.tiles_per_row;
 }

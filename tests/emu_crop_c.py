@@ -79,11 +79,23 @@ def crop_window(d, x, y, w, h):
     return rc, tuple(out4), list(own[:rc + 1]) if rc > 0 else []
 
 
-def row_owners(d, planes):
-    arrs = [np.ascontiguousarray(p, np.int16) for p in planes] + [np.zeros(8, np.int16)] * (3 - len(planes))
+def _row_bytes(d):
     ncomp = {0: 3, 1: 1, 2: 3, 5: 4, 6: 4}[d.out_colorspace]
-    rb = d.width if (d.out_layout == 1 and ncomp == 3) else d.width * ncomp
-    owner = np.zeros(rb, np.int32)
+    return d.width if (d.out_layout == 1 and ncomp == 3) else d.width * ncomp
+
+
+def row_owners(d, planes, k_lo=0):
+    """the brute-force write map of a frame row: (tiles or rc, owner[b] = the column that writes byte b, -1 nobody, -2 more
+    than one, -3 not examined: left of column k_lo, whose columns are not decoded)"""
+    arrs = [np.ascontiguousarray(p, np.int16) for p in planes] + [np.zeros(8, np.int16)] * (3 - len(planes))
+    owner = np.zeros(_row_bytes(d), np.int32)
     rc = lib().zjec_row_owners(C.byref(d), C.c_void_p(arrs[0].ctypes.data), C.c_void_p(arrs[1].ctypes.data),
-                               C.c_void_p(arrs[2].ctypes.data), C.c_void_p(owner.ctypes.data))
+                               C.c_void_p(arrs[2].ctypes.data), C.c_int(k_lo), C.c_void_p(owner.ctypes.data))
+    return rc, owner
+
+
+def plan_owners(d):
+    """the crop plan's owner of every byte of a frame row: (tiles or rc, owner[b], -1 no column, -2 more than one)"""
+    owner = np.zeros(_row_bytes(d), np.int32)
+    rc = lib().zjec_plan_owners(C.byref(d), C.c_void_p(owner.ctypes.data))
     return rc, owner

@@ -225,3 +225,144 @@ def test_crop_out_len_of_an_all_zero_output(synth):
         assert zj.crop_out_len(d, 101, 4) == 0 and zj.crop_out_len(d, 10, 4, 10 * per_px - 1) == 0
     dg = zj.FrameDesc.make(100, 40, 1, 1, 1, zj.ColorSpace.GRAYSCALE, qts)
     assert zj.crop_out_len(dg, 10, 4) == 40
+
+
+# ---- ownership at every row-end width ---------------------------------------------------------------------------------
+# The early RGB tail (Q5, zj_device.h: store_unit_generic) writes the row's last two 8-pixel units at p' = position - diff.
+# Where 3W - position is 1..15 the tail ends BEFORE position, and the bytes [p' + 48, position) between them belong to the
+# column of the ordinary unit they lie in: with 4:2:2 / 4:2:0 and the tail starting on a column boundary (W = 1..5 mod 256,
+# W > 256) that is the PREVIOUS column, which then owns two pieces of the row.
+
+def tail_geometry(W, hs):
+    """(p', position) of an RGB row of width W (store_unit_generic)"""
+    P = -(-W // (8 * hs)) * 8 * hs
+    position = 48 * max(P // 16 - 1, 0)
+    diff = max(64 - (3 * W - position), 0)
+    return (position - diff if position > diff else 0), position
+
+
+def tile_width(hs, vs, kind):
+    return one_group_width(hs, vs, kind) - 16
+
+
+def zero_planes(W, H, hs, vs):
+    """all-zero coefficients: which bytes a column writes does not depend on the pixels"""
+    mx, my = -(-W // (8 * hs)), -(-H // (8 * vs))
+    return [np.zeros(mx * my * 64 * hs * vs, np.int16), np.zeros(mx * my * 64, np.int16), np.zeros(mx * my * 64, np.int16)]
+
+
+def sweep_widths():
+    """every width up to 1100; the row ends at each tile width T: W = kT + r, r in 0..17 and T-17..T-1, up to ~16400 for
+    T = 512 and 1024, up to ~4400 for T = 256 (beyond that its even k are T = 512's and its odd k differ from them only in
+    the row's end: r = 0..6 there, where the tail starts on a column boundary); the same at the last column below 65535"""
+    ws = set(range(1, 1101))
+    for T, top in ((256, 4400), (512, 16400), (1024, 16400)):
+        for k in range(1, top // T + 1):
+            ws.update(k * T + r for r in list(range(18)) + list(range(T - 17, T)))
+    ws.update(k * 256 + r for k in range(1, 16400 // 256 + 1) for r in range(7))
+    ws.update([65280 + r for r in range(18)] + list(range(65519, 65536)))
+    return sorted(ws)
+
+
+SWEEP_FLAGS = [0, 1, 6, 7]
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_plan_owner_of_every_byte_equals_brute_force_writer(kind, mode, synth):
+    """every byte of a row has exactly one writer, and the crop plan's owner of it is that writer, at every width of
+    sweep_widths().  Rows wider than 1100 pixels are examined from their last two columns on (their first columns are
+    those of the narrower rows).  RGB HWC, whose row end depends on ZJ_FLAG_PLAIN_TAIL, runs every width with and without
+    it: flags 0 and 1, or 6 and 7, in turn; the other kinds, whose writes the flags do not move, take one of 0, 1, 6, 7."""
+    hs, vs = MODES[mode]
+    out_cs, layout = KINDS[kind]
+    _, qts = synth.make_frame(16, 16, 1, 1, 3, seed=1)
+    H = 16 * vs
+    descs = {f: ec.desc(16, H, hs, vs, 3, out_cs, qts, flags=f, out_layout=layout) for f in SWEEP_FLAGS}
+    bad = []
+    for i, W in enumerate(sweep_widths()):
+        planes = zero_planes(W, H, hs, vs)
+        for flags in (SWEEP_FLAGS[2 * (i % 2):2 * (i % 2) + 2] if kind == "rgb" else [SWEEP_FLAGS[i % 4]]):
+            d = descs[flags]
+            d.width = W
+            ntiles, plan = ec.plan_owners(d)
+            k_lo = max(ntiles - 2, 0) if W > 1100 else 0
+            nt, brute = ec.row_owners(d, planes, k_lo)
+            assert nt == ntiles, (W, flags, nt, ntiles)  # (both refuse a frame the reference panics on, ZJ_ERR_PANIC)
+            if nt < 0:
+                continue
+            seen = brute != -3
+            assert seen.sum() == len(brute) - k_lo * tile_width(hs, vs, kind) * (len(brute) // W), (W, k_lo)
+            assert (brute[seen] >= 0).all(), (W, flags, "bytes with no writer or two", np.nonzero(seen & (brute < 0))[0][:8])
+            if not np.array_equal(plan[seen], brute[seen]):
+                b = np.nonzero(seen & (plan != brute))[0]
+                bad.append((W, flags, len(b), int(b[0]), int(plan[b[0]]), int(brute[b[0]])))
+    assert not bad, f"{len(bad)} (width, flags) where the plan's owner != the writer: (W, flags, bytes, first, plan, writer) {bad[:12]}"
+
+
+def affected_widths():
+    return [k * 256 + r for k in (1, 2, 3) for r in range(1, 6)] + [1029, 1281, 2053, 4101, 65281, 65285]
+
+
+@pytest.mark.parametrize("mode", ["h", "hv"])
+@pytest.mark.parametrize("flags", [0, 6, 1])
+def test_window_columns_equal_brute_force_writers_at_the_tail(mode, flags, synth):
+    """crop_window's [k0, k1) == the columns that write a byte of the window, for windows at the row's end of the widths
+    whose tail starts on a column boundary: random ones, windows wholly inside [p' + 48, position) (only the previous
+    column writes them), and windows that start or end at p' - 1, p', p' + 48, position and the row's last byte"""
+    hs, vs = MODES[mode]
+    _, qts = synth.make_frame(16, 16, 1, 1, 3, seed=1)
+    rng = np.random.default_rng(flags + 10 * hs * vs)
+    for W in affected_widths():
+        d = ec.desc(W, 16 * vs, hs, vs, 3, oc.RGB, qts, flags=flags)
+        ntiles = ec.plan_owners(d)[0]
+        k_lo = max(ntiles - 3, 0)
+        nt, owner = ec.row_owners(d, zero_planes(W, 16 * vs, hs, vs), k_lo)
+        assert nt == ntiles and (owner[owner != -3] >= 0).all()
+        pp, position = tail_geometry(W, hs)
+        x_lo = 3 * tile_width(hs, vs, "rgb") * k_lo // 3 + 1  # windows right of the bytes not examined
+        wins = []
+        for _ in range(40):
+            x = int(rng.integers(x_lo, W))
+            wins.append((x, int(rng.integers(1, W - x + 1))))
+        hole = [x for x in range(x_lo, W) if pp + 48 <= 3 * x and 3 * x + 3 <= position]
+        if flags == 0 or flags == 6:
+            assert len(hole) == (position - pp - 48) // 3, (W, pp, position)
+        wins += [(x, n) for x in hole for n in range(1, len(hole) + 1) if x + n - 1 <= hole[-1]]
+        for b in (pp - 1, pp, pp + 48, position, 3 * W - 1):
+            q = min(max(b // 3, x_lo), W - 1)
+            wins += [(q, W - q), (q, 1), (q, min(W - q, 16)), (x_lo, q - x_lo + 1), (max(q - 15, x_lo), min(q, 15) + 1)]
+        for (x, w) in wins:
+            rc, (s0, s1, k0, k1), _ = ec.crop_window(d, x, 0, w, 1)
+            assert rc == ntiles
+            brute = sorted(set(owner[3 * x:3 * (x + w)].tolist()))
+            assert list(range(k0, k1)) == brute, (W, flags, x, w, k0, k1, brute, pp, position)
+
+
+@pytest.mark.parametrize("W", [256, 257, 258, 261, 262, 513, 517, 1029, 1281, 2053, 4101])
+@pytest.mark.parametrize("mode", ["h", "hv"])
+def test_crop_at_the_tail_widths_equals_sliced_full_decode(W, mode, synth):
+    """the emulated crop (over poisoned staging: a byte the copy-out takes from a column that never wrote it shows) == the
+    sliced full decode, at the widths whose tail starts on a column boundary and their unaffected neighbours: the whole
+    frame, every right-aligned window 1 to 48 pixels wide, windows that start or end at p' - 1, p', p' + 48, position and
+    the row's last byte, and a batch of origins"""
+    hs, vs = MODES[mode]
+    H = 16 * vs
+    planes, qts = synth.make_frame(W, H, hs, vs, 3, seed=W)
+    pp, position = tail_geometry(W, hs)
+    rng = np.random.default_rng(W * hs * vs)
+    for kind in ("rgb", "rgba", "chw"):
+        out_cs, layout = KINDS[kind]
+        for flags in (0, 6, 7):
+            d = ec.desc(W, H, hs, vs, 3, out_cs, qts, flags=flags, out_layout=layout)
+            rc, full = full_frame(d, planes, kind, flags)
+            assert rc == 0
+            wins = [(W, H, [(0, 0)])]
+            wins += [(w, H, [(W - w, 0)]) for w in range(1, min(W, 48) + 1)]
+            for b in (pp - 1, pp, pp + 48, position, 3 * W - 1):
+                q = min(max(b // 3, 0), W - 1)
+                wins += [(W - q, H, [(q, 0)]), (q + 1, H, [(0, 0)]), (min(W - q, 20), 3, [(q, 5)]), (min(q + 1, 20), 2, [(max(q - 19, 0), 7)])]
+            w = 40
+            wins.append((w, H // 2, [(W - w, 0), (W - w - 1, H // 2), (W - w - 5, 3)] +
+                         [(int(rng.integers(W - w + 1)), int(rng.integers(H // 2 + 1))) for _ in range(5)]))
+            check_windows(d, planes, kind, flags, full, wins)

@@ -274,3 +274,59 @@ def test_decode_crops_to_tensor(zj, ctx, torch, synth):
             else:
                 exp = view[0, ..., y:y + 224, x:x + 224]
             assert torch.equal(out[i], exp), (kind, i)
+
+
+# ---- the row ends where the early RGB tail starts on a column boundary --------------------------------------------------
+# 4:2:2 / 4:2:0 widths W = 1..5 mod 256, W > 256: the bytes [p' + 48, position) of every RGB row are the previous column's
+# (zj_plan.h: make_crop_plan's hole).  256 and 262 are unaffected neighbours.
+TAIL_WIDTHS = [256, 257, 258, 261, 262, 513, 517, 1029, 1281, 2053, 4101]
+
+
+def tail_geometry(W, hs):
+    """(p', position) of an RGB row of width W (zj_device.h: store_unit_generic)"""
+    P = -(-W // (8 * hs)) * 8 * hs
+    position = 48 * max(P // 16 - 1, 0)
+    diff = max(64 - (3 * W - position), 0)
+    return (position - diff if position > diff else 0), position
+
+
+def tail_windows(W, H, hs):
+    """(w, h, origins) launches of many windows each: the whole frame; every right-aligned width 1..48; windows that start
+    or end at the pixels of bytes p' - 1, p', p' + 48, position and 3W - 1"""
+    pp, position = tail_geometry(W, hs)
+    h = 8
+    rows = list(range(H - h + 1))[:64]
+    wins = [(W, H, [(0, 0)])]
+    wins += [(w, h, [(W - w, y) for y in rows]) for w in range(1, min(W, 48) + 1)]
+    for b in (pp - 1, pp, pp + 48, position, 3 * W - 1):
+        q = min(max(b // 3, 0), W - 1)
+        wins += [(W - q, h, [(q, y) for y in rows]), (q + 1, h, [(0, y) for y in rows]),
+                 (min(W - q, 20), h, [(q, y) for y in rows]), (min(q + 1, 20), h, [(max(q - 19, 0), y) for y in rows])]
+    return wins
+
+
+@pytest.mark.parametrize("W", TAIL_WIDTHS)
+@pytest.mark.parametrize("mode", ["h", "hv"])
+def test_tail_width_crops_equal_sliced_full_decode(zj, ctx, torch, synth, W, mode):
+    """crops at the tail widths == the sliced full device decode, byte for byte.  Before every launch the same kernel crops
+    another frame whole, so that staging a workgroup reads without having written holds that frame's bytes, not these."""
+    hs, vs = MODES[mode]
+    H = 64
+    for kind in ("rgb", "rgba", "chw"):
+        for flags in (0, 6, 7):
+            d, dev, planes, qts = frame_on_device(zj, torch, synth, W, H, hs, vs, kind, flags, seed=W)
+            _, other, _, _ = frame_on_device(zj, torch, synth, W, H, hs, vs, kind, flags, seed=W + 1, index=1)
+            full = full_device(zj, ctx, torch, d, dev)
+            if kind == "rgb" and flags == 0:
+                rc, exp = oc.decode_planes(oc.make_frame(W, H, hs, vs, 3, oc.RGB, qts), planes)
+                assert rc == 0 and np.array_equal(full.reshape(-1), exp), "full device decode != oracle"
+            scratch = torch.empty(zj.crop_out_len(d, W, H), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            for (w, h, origins) in tail_windows(W, H, hs):
+                ctx.decode_crops_device(d, [other[0].data_ptr()], [other[1].data_ptr()], [other[2].data_ptr()], [(0, 0)], W, H,
+                                        [scratch.data_ptr()])  # (the context's stream: before the launch below)
+                crops = run_crops(zj, ctx, torch, d, [dev] * len(origins), origins, w, h)
+                try:
+                    check(zj, d, full, crops, origins, w, h)
+                except AssertionError as e:
+                    raise AssertionError(f"{kind} {mode} flags {flags}: {e}") from None

@@ -174,6 +174,20 @@ def own_crop(zj, ctx, torch, d, frame, x, y, w, h):
     return a.reshape(3, h, w) if is_chw(zj, d) else a.reshape(h, w, 3).transpose(2, 0, 1)
 
 
+def full_image(zj, ctx, torch, d, frame):
+    """the full device decode of one frame, as [C, H, W] uint8"""
+    n = zj.lib().zj_out_len(C.byref(d))
+    buf = torch.full((n,), 0xAA, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ctx.decode_planes_device(d, 1, frame[0].data_ptr(), frame[1].data_ptr(), frame[2].data_ptr(), buf.data_ptr())
+    ctx.sync()
+    a = buf.cpu().numpy()
+    c, W, H = channels_of(zj, d), d.width, d.height
+    if c == 1:
+        return a.reshape(1, H, W)
+    return a.reshape(3, H, W) if is_chw(zj, d) else a.reshape(H, W, c).transpose(2, 0, 1)
+
+
 def run_resized(zj, ctx, torch, d, frames, windows, ow, oh, dtype, layout, scale, bias, flips, stream=None):
     c = channels_of(zj, d)
     per = zj.resized_out_len(d, ow, oh, dtype)
@@ -212,14 +226,66 @@ def test_crops_resized_equal_the_model_of_the_crop(zj, ctx, torch, synth, mode, 
     wins = windows_of(rng, W, H, 12)
     flips = [bool(i % 3 == 1) for i in range(len(wins))]
     crops = [own_crop(zj, ctx, torch, d, dev, *w) for w in wins]
+    img = full_image(zj, ctx, torch, d, dev)
     dtype = int(rng.integers(4))
     layout = "NHWC" if rng.integers(2) else "NCHW"
     scale, bias = random_factors(rng, c)
     for (ow, oh) in [(64, 48), (7, 300)]:
         outs = run_resized(zj, ctx, torch, d, [dev] * len(wins), wins, ow, oh, dtype, layout, scale, bias, flips)
         for i, w in enumerate(wins):
+            what = f"{kind} {mode} flags {flags} window {w} -> {ow}x{oh} dtype {dtype} {layout}"
             exp = rm.resize(crops[i], ow, oh, dtype, scale, bias, flips[i], layout)
-            check_image(outs[i], exp, dtype, f"{kind} {mode} flags {flags} window {w} -> {ow}x{oh} dtype {dtype} {layout}")
+            check_image(outs[i], exp, dtype, what)
+            # (and of the full decode's window: a wrong crop would make a wrong expectation above)
+            x, y, ww, hh = w
+            exp = rm.resize(img[:, y:y + hh, x:x + ww], ow, oh, dtype, scale, bias, flips[i], layout)
+            check_image(outs[i], exp, dtype, what + " (full decode's window)")
+
+
+def tail_geometry(W, hs):
+    """(p', position) of an RGB row of width W (zj_device.h: store_unit_generic)"""
+    P = -(-W // (8 * hs)) * 8 * hs
+    position = 48 * max(P // 16 - 1, 0)
+    diff = max(64 - (3 * W - position), 0)
+    return (position - diff if position > diff else 0), position
+
+
+def tail_windows(W, H, hs, rng):
+    """windows at a row's end: the whole frame, right-aligned ones, ones that start or end at the pixels of bytes p' - 1,
+    p', p' + 48, position and 3W - 1, random ones"""
+    pp, position = tail_geometry(W, hs)
+    out = [(0, 0, W, H)] + [(W - w, int(rng.integers(H - 7)), w, 7) for w in (1, 2, 5, 8, 16, 17, 31, 48) if w <= W]
+    for b in (pp - 1, pp, pp + 48, position, 3 * W - 1):
+        q = min(max(b // 3, 0), W - 1)
+        out += [(q, 0, W - q, H), (0, 3, q + 1, H - 3), (q, 1, min(W - q, 20), 9), (max(q - 19, 0), 2, min(q + 1, 20), 11)]
+    while len(out) < 40:
+        w, h = int(rng.integers(1, W + 1)), int(rng.integers(1, H + 1))
+        out.append((int(rng.integers(W - w + 1)), int(rng.integers(H - h + 1)), w, h))
+    return out
+
+
+@pytest.mark.parametrize("W", [256, 257, 258, 261, 262, 513, 517, 1029, 1281, 2053, 4101])
+@pytest.mark.parametrize("mode", ["h", "hv"])
+def test_tail_width_resized_crops_equal_the_model_of_the_full_decode(zj, ctx, torch, synth, W, mode):
+    """4:2:2 / 4:2:0 widths W = 1..5 mod 256 (the early RGB tail starts on a column boundary) and neighbours: the resized
+    crops == the model of the full device decode's window (not of the crop, which would share a wrong crop's bytes)"""
+    hs, vs = MODES[mode]
+    H = 64
+    rng = np.random.default_rng(W * hs * vs)
+    for kind in ("rgb", "chw"):
+        for flags in (0, 6, 7):
+            d, dev = frame_on_device(zj, torch, synth, W, H, hs, vs, kind, flags, seed=W)
+            img = full_image(zj, ctx, torch, d, dev)
+            wins = tail_windows(W, H, hs, rng)
+            flips = [bool(i % 3 == 1) for i in range(len(wins))]
+            dtype = (flags + hs) % 4
+            layout = "NHWC" if flags % 2 else "NCHW"
+            scale, bias = random_factors(rng, 3)
+            for (ow, oh) in [(32, 24), (5, 70)]:
+                outs = run_resized(zj, ctx, torch, d, [dev] * len(wins), wins, ow, oh, dtype, layout, scale, bias, flips)
+                for i, (x, y, w, h) in enumerate(wins):
+                    exp = rm.resize(img[:, y:y + h, x:x + w], ow, oh, dtype, scale, bias, flips[i], layout)
+                    check_image(outs[i], exp, dtype, f"{kind} {W} {mode} flags {flags} window {(x, y, w, h)} -> {ow}x{oh}")
 
 
 def test_crops_resized_scattered_frames_and_every_dtype(zj, ctx, torch, synth):
@@ -376,6 +442,57 @@ def test_file_path_equals_the_planes_path(zj, torch, entropy):
         ref_ctx.close()
         crop_ctx.close()
     assert checked >= 10
+
+
+@pytest.mark.parametrize("entropy", ["cpu", "gpu"])
+def test_file_path_at_a_tail_width(zj, torch, synth, entropy):
+    """a 4:2:0 baseline file 517 pixels wide (tools/jpeg_enc.py; its RGB rows end 1 byte past `position`, the tail on a
+    column boundary): finish_pixels_crop_device == finish_pixels_device sliced, and finish_pixels_resized_crop_device ==
+    the model of that slice"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
+    import jpeg_enc
+    W, H = 517, 100
+    data = jpeg_enc.encode_baseline(jpeg_enc.small_planes(W, H, 2, 2, 3, seed=5), synth.quant_tables(85), W, H, 2, 2, 3)
+    rng = np.random.default_rng(zlib.crc32(entropy.encode()))
+    ctx = zj.Context(zj.BACKEND_HIP, 0)
+
+    def opts():
+        o = zj.ZuneJpegOptions()
+        if entropy == "gpu":
+            o.entropy = zj.ENTROPY_GPU_ALWAYS
+        return o
+    try:
+        dec = zj.Decoder(opts(), ctx)
+        desc, _ = dec.prepare(data)
+        assert (desc.width, desc.height, desc.h_max, desc.v_max) == (W, H, 2, 2)
+        n = zj.lib().zj_out_len(C.byref(desc))
+        full = torch.full((n,), 0xAA, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        assert dec.finish_pixels_device(full.data_ptr(), n) == n
+        ref = full.cpu().numpy().reshape(H, W * 3)
+        img = ref.reshape(H, W, 3).transpose(2, 0, 1)
+        for k, (x, y, w, h) in enumerate(tail_windows(W, H, 2, rng)):
+            dec.prepare(data)
+            ln = zj.crop_out_len(desc, w, h)
+            buf = out_buffer(torch, ln)
+            assert dec.finish_pixels_crop_device(x, y, w, h, buf.data_ptr() + GUARD, ln) == ln
+            got = read_out(buf, ln)
+            assert np.array_equal(got, ref[y:y + h, 3 * x:3 * (x + w)].reshape(-1)), (entropy, x, y, w, h)
+            dtype, layout = k % 4, ("NHWC" if k % 2 else "NCHW")
+            ow, oh = (224, 224) if k % 5 == 0 else (31, 17)
+            scale, bias = random_factors(rng, 3)
+            dec.prepare(data)
+            per = zj.resized_out_len(desc, ow, oh, dtype)
+            buf = out_buffer(torch, per)
+            assert dec.finish_pixels_resized_crop_device(x, y, w, h, ow, oh, dtype,
+                                                         zj.TENSOR_NHWC if layout == "NHWC" else zj.TENSOR_NCHW,
+                                                         buf.data_ptr() + GUARD, per, scale, bias, flip=bool(k % 3)) == per
+            exp = rm.resize(img[:, y:y + h, x:x + w], ow, oh, dtype, scale, bias, bool(k % 3), layout)
+            check_image(read_out(buf, per), exp, dtype, f"{entropy} window {(x, y, w, h)} -> {ow}x{oh}")
+        dec.close()
+    finally:
+        ctx.close()
 
 
 # ---- tensors --------------------------------------------------------------------------------------------------------------

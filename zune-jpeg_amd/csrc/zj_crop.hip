@@ -21,7 +21,8 @@ namespace zj {
 // One workgroup per (frame, strip, tile column) the window needs: blockIdx.z = frame of the launch, blockIdx.y / x = strip
 // / column counted from the frame's first.  The tile is decoded by the packed generation with the generic stores (any
 // width, every flag, the early tail and its zeros), into a staging area in LDS laid out like the frame's rows; the
-// workgroup then copies the window's part of the bytes it owns.  One instantiation per (HS, VS, OUT).
+// workgroup then copies the window's part of the bytes it owns (one or two intervals of a row, zj_device.h:
+// crop_own_spans).  One instantiation per (HS, VS, OUT).
 // The launch bound follows from the LDS a workgroup holds (tile + staging, 30-62 KB: 2 to 5 workgroups on the 160 KB of a
 // CU): the waves per SIMD that can actually be resident, so that the register budget is that occupancy's, not the full
 // kernels' six.
@@ -89,7 +90,12 @@ __global__ __launch_bounds__((Cfg<HS, VS, OUT>::NT), (CropOccupancy<HS, VS, OUT>
         phase_color<C, HS, VS, OUT, GEN_PACKED, false, false, false>(p, t, tid, lds);
     }
     __syncthreads();
-    crop_copyout<HS, VS, OUT>(cp, s, tid, C::NT, stage, ZJ_GLOBAL_PTR(uint8_t, p.fptr[s.frame][3]));
+    uint8_t* const out = ZJ_GLOBAL_PTR(uint8_t, p.fptr[s.frame][3]);
+    if (s.b0 < s.b1) crop_copyout<HS, VS, OUT>(cp, s, tid, C::NT, stage, out); // (both uniform)
+    if (s.c0 < s.c1) {                                                       // the second interval the tile owns
+        s.b0 = s.c0; s.b1 = s.c1;
+        crop_copyout<HS, VS, OUT>(cp, s, tid, C::NT, stage, out);
+    }
 }
 
 // zeros for the window rows at or below rows_covered (Q6); only the window's bytes of each row, never the pitch padding

@@ -1903,11 +1903,15 @@ inline bool seam_launch(const Params& p)
 // ------------------------------------------------------------------------------------------------
 // A crop workgroup decodes ONE tile exactly as the generic (any-width) kernels do, but its pixel stores land in a staging
 // area in LDS laid out like the tile's rows of the frame; then it copies the part of each row it OWNS that lies inside the
-// window.  Ownership is by the bytes a tile writes, not by pixel x: tile k owns [own_lo(k), own_lo(k + 1)) of every row,
-// which is its natural range [bpp * TWY * k, bpp * TWY * (k + 1)) except at a row's end, where the two early-written units
-// of an RGB row (Q5, store_unit_generic) start up to 88 bytes left of their tile -- the staging keeps crop_margin() bytes in
-// front of the tile's natural range for them.  Every byte of a row has exactly one writer (store_unit_generic), so the
-// union of the owned ranges is the full decode's row.
+// window.  Ownership is by the bytes a tile writes, not by pixel x.  Tile k's range of every row is [own_lo(k),
+// own_lo(k + 1)): its natural range [bpp * TWY * k, bpp * TWY * (k + 1)) except at a row's end, where the two early-written
+// units of an RGB row (Q5, store_unit_generic) start up to 88 bytes left of their tile -- the staging keeps crop_margin()
+// bytes in front of the tile's natural range for them.  Those two units cover [p', p' + 48).  When the row ends 1 to 15
+// bytes past `position`, they end before `position`, and the bytes [p' + 48, position) between them are written by the
+// ordinary unit they lie in.  Where that unit is in the previous tile (the tail starts on a tile boundary), the bytes are
+// a hole in the tail tile's range that the previous tile owns: that tile owns two intervals of the row, its range and the
+// hole, and the tail tile two, its range on either side of the hole (crop_own_spans).  Every byte of a row has exactly
+// one writer (store_unit_generic), so the owned intervals of all tiles partition the full decode's row.
 ZJ_HD constexpr int crop_bpp(const int out) { return out == OUT_RGBA ? 4 : ((out == OUT_RGB || out == OUT_YCBCR) ? 3 : 1); }
 ZJ_HD constexpr int crop_margin(const int out) { return out == OUT_RGB ? 128 : 0; }
 ZJ_HD constexpr int crop_stage_pitch(const int out, const int twy) { return crop_bpp(out) * twy + crop_margin(out); }
@@ -1934,6 +1938,7 @@ struct CropParams {
     int row_bytes;                // bytes of a frame row (CHW: of a plane's row)
     int tile_bytes;               // bpp x tile width
     int cut_tile[2], cut_lo[2];   // ownership exceptions at a row's end (zj_plan.h: make_crop_plan); tile -1 = none
+    int hole_tile, hole_lo, hole_hi; // ... and the bytes [hole_lo, hole_hi) tile hole_tile owns inside a later range (-1: none)
     long long crop_plane;         // CHW: bytes between the crop's planes (out_pitch x crop_h; out_pitch 0: pitch x h)
     uint32_t origin[SCATTER_MAX]; // per frame: x | y << 16
     uint32_t first[SCATTER_MAX];  // per frame: first tile column | first strip << 16
@@ -1950,9 +1955,19 @@ ZJ_HD int crop_own_lo(const int k, const int tile_bytes, const int row_bytes, co
     return lo < row_bytes ? (int)lo : row_bytes;
 }
 
-// What one crop workgroup copies: frame rows [r0, r1) of its strip, row bytes [b0, b1) (CHW: of each plane)
-// (pitch / plane: the crop's bytes between rows and between planes)
-struct CropSpan { int frame, strip, tile, r0, r1, b0, b1, x, y, pitch; long long plane; };
+// The bytes of a frame row that tile column k owns: [a0, a1) and [c0, c1), either of them possibly empty.  Tile k's range
+// [own_lo(k), own_lo(k + 1)) less the hole, and for hole_tile the hole.  (No hole: hole_lo == hole_hi == row_bytes.)
+ZJ_HD void crop_own_spans(const int k, const int lo, const int hi, const int hole_tile, const int hole_lo, const int hole_hi,
+                          int& a0, int& a1, int& c0, int& c1)
+{
+    a0 = lo; a1 = hi < hole_lo ? hi : hole_lo;
+    if (k == hole_tile) { c0 = hole_lo; c1 = hole_hi; }
+    else { c0 = lo > hole_hi ? lo : hole_hi; c1 = hi; }
+}
+
+// What one crop workgroup copies: frame rows [r0, r1) of its strip, row bytes [b0, b1) and [c0, c1) (CHW: of each plane;
+// either may be empty) (pitch / plane: the crop's bytes between rows and between planes)
+struct CropSpan { int frame, strip, tile, r0, r1, b0, b1, c0, c1, x, y, pitch; long long plane; };
 
 // the workgroup (frame fz, strip index sy, column index sx) of a crop launch; false: nothing to do (workgroup-uniform:
 // a frame whose window spans fewer strips or columns than the launch's grid leaves the rest of its workgroups idle)
@@ -1975,10 +1990,14 @@ ZJ_DEV bool crop_locate(const CropParams& cp, const int fz, const int sy, const 
     if (s.r0 >= s.r1) return false;
     const int lo = crop_own_lo(s.tile, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]);
     const int hi = crop_own_lo(s.tile + 1, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]);
+    int a0, a1, c0, c1;
+    crop_own_spans(s.tile, lo, hi, cp.hole_tile, cp.hole_lo, cp.hole_hi, a0, a1, c0, c1);
     const int wb0 = s.x * cp.bpp, wb1 = (s.x + cw) * cp.bpp;
-    s.b0 = lo > wb0 ? lo : wb0;
-    s.b1 = hi < wb1 ? hi : wb1;
-    return s.b0 < s.b1;
+    s.b0 = a0 > wb0 ? a0 : wb0;
+    s.b1 = a1 < wb1 ? a1 : wb1;
+    s.c0 = c0 > wb0 ? c0 : wb0;
+    s.c1 = c1 < wb1 ? c1 : wb1;
+    return s.b0 < s.b1 || s.c0 < s.c1;
 }
 
 // where the tile decode's stores go: the staging, addressed the way the frame's rows are (phase_color writes frame row
@@ -1991,9 +2010,10 @@ ZJ_DEV uint8_t* crop_stage_base(uint8_t* stage, const CropSpan& s)
     return stage - (long long)s.strip * C::SH * S::PITCH - ((long long)s.tile * C::TWY * S::BPP - S::MARGIN);
 }
 
-// Copy-out of the owned window bytes, one lane per 16 bytes of a crop row.  A window row starts at any byte: the lanes
-// store dwords aligned in the DESTINATION (four at a time), each assembled from two staged dwords with v_alignbyte_b32;
-// the bytes up to the row segment's first dword boundary and after its last go out singly from one extra lane per segment.
+// Copy-out of the window bytes [s.b0, s.b1) (b0 < b1), one lane per 16 bytes of a crop row.  A window row starts at any
+// byte: the lanes store dwords aligned in the DESTINATION (four at a time), each assembled from two staged dwords with
+// v_alignbyte_b32; the bytes up to the row segment's first dword boundary and after its last go out singly from one extra
+// lane per segment.
 template <int HS, int VS, int OUT>
 ZJ_DEV void crop_copyout(const CropParams& cp, const CropSpan& s, const int tid, const int nthreads, const uint8_t* stage, uint8_t* out)
 {

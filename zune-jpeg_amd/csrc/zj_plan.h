@@ -215,9 +215,13 @@ struct CropPlan {
     int row_bytes;        // bytes of a frame row (CHW: of one plane's row)
     int tile_bytes;       // bpp x twy: a tile column's natural byte range in a row
     int cut_tile[2], cut_lo[2]; // ownership exceptions: the tiles holding the row's two early-written RGB units (Q5)
+    int hole_tile, hole_lo, hole_hi; // ... and the bytes [hole_lo, hole_hi) that tile writes inside a later tile's range
     size_t out_pitch;     // bytes between crop rows (CHW: of a plane)
     size_t out_len;       // bytes of one crop (x 3 planes for CHW)
 };
+
+// first byte of a frame row that tile column k owns (zj_device.h: crop_own_lo)
+inline int crop_own(const CropPlan& cp, int k) { return crop_own_lo(k, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]); }
 
 template <int HS, int VS>
 inline void crop_geo(CropPlan& cp, bool chroma)
@@ -249,8 +253,13 @@ inline int make_crop_plan(const zj_frame_desc* d, unsigned w, unsigned h, unsign
     // Who writes the end of a row (store_unit_generic, the rules of the crop kernel's stores): the last two 8-pixel units
     // of an RGB row under the early-tail quirk (Q5) are written at p' and p' + 24, up to 88 bytes left of their own tile,
     // and the zeros after them (Q6) by the last unit's tile.  Every other byte belongs to the tile its pixel lies in.
+    // Where the row ends 1 to 15 bytes past `position` (diff > 48), the two units end before `position`: the bytes
+    // [p' + 48, position) are the ordinary unit's below `position`.  When that unit's tile ends at or before p' (the tail
+    // starts on a tile boundary: 4:2:2 / 4:2:0 widths W = 1..5 mod 256, W > 256), they are a hole in the tail tile's
+    // range [p', ...) that the previous tile owns.
     cp.cut_tile[0] = cp.cut_tile[1] = -1;
     cp.cut_lo[0] = cp.cut_lo[1] = 0;
+    cp.hole_tile = -1; cp.hole_lo = cp.hole_hi = cp.row_bytes;
     const int W = (int)d->width;
     if (pl.out == OUT_RGB && !pl.plain && W >= 16) {
         const long long P = (long long)pl.mcu_x * 8 * pl.hs, units = P >> 3;
@@ -260,6 +269,10 @@ inline int make_crop_plan(const zj_frame_desc* d, unsigned w, unsigned h, unsign
         const long long pp = position > diff ? position - diff : 0;
         cp.cut_tile[0] = (int)(8 * (units - 2) / cp.twy); cp.cut_lo[0] = (int)pp;
         cp.cut_tile[1] = (int)(8 * (units - 1) / cp.twy); cp.cut_lo[1] = (int)(pp + 24);
+        const int k = (int)((pp + 48) / cp.tile_bytes); // the tile of the ordinary unit under [p' + 48, position)
+        if (pp + 48 < position && crop_own(cp, k + 1) <= pp + 48) {
+            cp.hole_tile = k; cp.hole_lo = (int)(pp + 48); cp.hole_hi = (int)position;
+        }
     }
     return ZJ_OK;
 }
@@ -280,6 +293,7 @@ inline int make_zero_crop(const zj_frame_desc* d, unsigned w, unsigned h, unsign
     cp.nplanes = chw ? 3 : 1;
     cp.row_bytes = (int)d->width * cp.bpp;
     cp.cut_tile[0] = cp.cut_tile[1] = -1;
+    cp.hole_tile = -1; cp.hole_lo = cp.hole_hi = cp.row_bytes;
     const size_t tight = (size_t)w * cp.bpp;
     cp.out_pitch = out_pitch ? (size_t)out_pitch : tight;
     if (cp.out_pitch < tight || cp.out_pitch > (1u << 20)) return ZJ_ERR_ARG;
@@ -287,7 +301,11 @@ inline int make_zero_crop(const zj_frame_desc* d, unsigned w, unsigned h, unsign
     return ZJ_OK;
 }
 
-inline int crop_own(const CropPlan& cp, int k) { return crop_own_lo(k, cp.tile_bytes, cp.row_bytes, cp.cut_tile[0], cp.cut_lo[0], cp.cut_tile[1], cp.cut_lo[1]); }
+// the bytes of a frame row tile column k owns: [a0, a1) and [c0, c1) (zj_device.h: crop_own_spans)
+inline void crop_spans(const CropPlan& cp, int k, int& a0, int& a1, int& c0, int& c1)
+{
+    crop_own_spans(k, crop_own(cp, k), crop_own(cp, k + 1), cp.hole_tile, cp.hole_lo, cp.hole_hi, a0, a1, c0, c1);
+}
 
 // A window at (x, y) of a frame of plan pl: is it inside the frame, and which strips [s0, s1) and tile columns [k0, k1)
 // does it need (strips clipped to the ones that exist: the window's rows at or below rows_covered are zeros, Q6)
@@ -298,11 +316,18 @@ inline int crop_window(const zj_frame_desc* d, const Plan& pl, const CropPlan& c
     s1 = (int)((y + cp.h + cp.sh - 1) / cp.sh);
     if (s1 > pl.n_strips) s1 = pl.n_strips;
     if (s0 > s1) s0 = s1;
+    // the columns that own a byte of the window.  They are consecutive: a row's owners rise byte by byte except in the
+    // hole, whose owner is the column just before the tail's.
     const int wb0 = (int)x * cp.bpp, wb1 = ((int)x + cp.w) * cp.bpp;
-    k0 = 0;
-    while (k0 < pl.tiles_per_row && crop_own(cp, k0 + 1) <= wb0) k0++;
-    k1 = k0;
-    while (k1 < pl.tiles_per_row && crop_own(cp, k1) < wb1) k1++;
+    k0 = k1 = 0;
+    for (int k = 0; k < pl.tiles_per_row; k++) {
+        int a0, a1, c0, c1;
+        crop_spans(cp, k, a0, a1, c0, c1);
+        const bool in_a = (a0 > wb0 ? a0 : wb0) < (a1 < wb1 ? a1 : wb1), in_c = (c0 > wb0 ? c0 : wb0) < (c1 < wb1 ? c1 : wb1);
+        if (!in_a && !in_c) continue;
+        if (k1 == 0) k0 = k;
+        k1 = k + 1;
+    }
     return ZJ_OK;
 }
 
@@ -324,6 +349,7 @@ inline void fill_crop_params_win(const zj_frame_desc* d, const Plan& pl, const C
     c.out_pitch = stride == 4 ? 0 : (int)cp.out_pitch;
     c.bpp = cp.bpp; c.row_bytes = cp.row_bytes; c.tile_bytes = cp.tile_bytes;
     for (int i = 0; i < 2; i++) { c.cut_tile[i] = cp.cut_tile[i]; c.cut_lo[i] = cp.cut_lo[i]; }
+    c.hole_tile = cp.hole_tile; c.hole_lo = cp.hole_lo; c.hole_hi = cp.hole_hi;
     c.crop_plane = (long long)cp.out_pitch * cp.h;
     nstrips = ncols = 0;
     for (int f = 0; f < SCATTER_MAX; f++) {
