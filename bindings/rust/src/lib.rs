@@ -28,6 +28,8 @@ pub const ZJ_DTYPE_BF16: c_int = 2;
 pub const ZJ_DTYPE_U8: c_int = 3;
 pub const ZJ_TENSOR_NCHW: c_int = 0;
 pub const ZJ_TENSOR_NHWC: c_int = 1;
+pub const ZJ_RESIZE_BILINEAR: c_int = 0;
+pub const ZJ_RESIZE_BILINEAR_AA: c_int = 1;
 
 /// `ColorSpace`, `src/misc.rs:88-106` (same discriminants).
 #[repr(i32)]
@@ -207,6 +209,21 @@ extern "C" {
                                                         h: c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
                                                         out_layout: c_int, scale: *const f32, bias: *const f32, flip: c_int,
                                                         d_out: *mut c_void, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn zj_resize_filtered_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint,
+                                     in_pitch: *const c_uint, channels: c_int, in_layout: c_int, out_w: c_uint, out_h: c_uint,
+                                     dtype: c_int, out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                     filter: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_resized_filtered_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize,
+                                                   d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                                   windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                   out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                                   filter: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_resized_crop_filtered_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint,
+                                                                 w: c_uint, h: c_uint, out_w: c_uint, out_h: c_uint,
+                                                                 dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                                 bias: *const f32, flip: c_int, filter: c_int,
+                                                                 d_out: *mut c_void, out_cap: usize,
+                                                                 out_len: *mut usize) -> c_int;
     pub fn zj_device_pci_bus_id(device: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zj_device_numa_node(device: c_int) -> c_int;
     pub fn zj_bind_thread_to_numa_node(node: c_int) -> c_int;

@@ -248,8 +248,8 @@ ZJ_API int zj_decode_crops_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nf
                                   const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *origins,
                                   unsigned crop_w, unsigned crop_h, uint8_t *const *d_out, unsigned out_pitch, void *stream);
 /* Resize + normalise into a dense tensor: images of their own sizes to ONE out_w x out_h (1..8192), bilinear
- * with half-pixel centres (align_corners=False, no antialiasing: strong downscales alias), in integer arithmetic with the
- * source position truncated to 1/256 pixel.  Per channel c, v = the interpolated value x 65536 (0 .. 255 x 65536):
+ * with half-pixel centres (align_corners=False, no antialiasing: strong downscales alias; ZJ_RESIZE_BILINEAR_AA below
+ * antialiases), in integer arithmetic with the source position truncated to 1/256 pixel.  Per channel c, v = the interpolated value x 65536 (0 .. 255 x 65536):
  *   ZJ_DTYPE_F32   fl32(fl32(v * (scale[c] / 65536)) + bias[c]), two separately rounded float32 operations;
  *                  scale = 1 / (255 std), bias = -mean / std is (x / 255 - mean) / std, the usual normalisation
  *   ZJ_DTYPE_F16 / ZJ_DTYPE_BF16   that float32 rounded to nearest-even
@@ -282,6 +282,27 @@ ZJ_API int zj_decode_crops_resized_device(zj_ctx *ctx, const zj_frame_desc *d, s
                                           const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *windows,
                                           unsigned out_w, unsigned out_h, int dtype, int out_layout, const float *scale,
                                           const float *bias, const uint8_t *flip, void *d_out, void *stream);
+/* Resize filters of the *_filtered_device entry points:
+ *   ZJ_RESIZE_BILINEAR     the bilinear definition above: the entry points without a filter, byte for byte
+ *   ZJ_RESIZE_BILINEAR_AA  antialiased: the triangle filter of Pillow's bilinear / F.interpolate(antialias=True), in exact
+ *                          integers.  Every source pixel under an output's support contributes, with weights in units of
+ *                          2^-14 that sum to exactly 2^14 per output; the vertical pass runs first and rounds its sums to
+ *                          1/256, the horizontal pass gives the same v (0 .. 255 x 65536) the conversions above take.  A
+ *                          window of exactly out_w x out_h gives the crop itself, as the bilinear filter does.
+ * Any other filter is ZJ_ERR_ARG and nothing is launched.  The other arguments are those of the entry point without a
+ * filter. */
+#define ZJ_RESIZE_BILINEAR 0
+#define ZJ_RESIZE_BILINEAR_AA 1
+ZJ_API int zj_resize_filtered_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh,
+                                     const unsigned *in_pitch, int channels, int in_layout, unsigned out_w, unsigned out_h,
+                                     int dtype, int out_layout, const float *scale, const float *bias, const uint8_t *flip,
+                                     int filter, void *d_out, void *stream);
+ZJ_API int zj_decode_crops_resized_filtered_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes,
+                                                   const int16_t *const *d_y, const int16_t *const *d_cb,
+                                                   const int16_t *const *d_cr, const unsigned *windows, unsigned out_w,
+                                                   unsigned out_h, int dtype, int out_layout, const float *scale,
+                                                   const float *bias, const uint8_t *flip, int filter, void *d_out,
+                                                   void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -397,6 +418,12 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_device(zj_decoder *d, zj_ctx *c
                                                         unsigned h, unsigned out_w, unsigned out_h, int dtype, int out_layout,
                                                         const float *scale, const float *bias, int flip, void *d_out,
                                                         size_t out_cap, size_t *out_len);
+/* ... with a resize filter (ZJ_RESIZE_*; any other is ZJ_ERR_ARG) */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y,
+                                                                 unsigned w, unsigned h, unsigned out_w, unsigned out_h,
+                                                                 int dtype, int out_layout, const float *scale,
+                                                                 const float *bias, int flip, int filter, void *d_out,
+                                                                 size_t out_cap, size_t *out_len);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

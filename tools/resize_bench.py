@@ -9,9 +9,11 @@
       .to(bfloat16), in the same run, on the same stream.
 
 Each time is the mean over --iters calls between one event pair; --reps such measurements give the spread (min / median /
-max).
+max).  --antialias runs both parts with the triangle filter (ZJ_RESIZE_BILINEAR_AA, profiles/resize_aa.txt): the torch path
+then uses F.interpolate(antialias=True), and part (a) counts every byte of the crops as read (each output reads all the
+source pixels under it).
 
-usage: python tools/resize_bench.py [--part a|b|all] [--iters N] [--reps R]"""
+usage: python tools/resize_bench.py [--part a|b|all] [--iters N] [--reps R] [--antialias]"""
 import argparse
 import importlib
 import json
@@ -76,17 +78,21 @@ def part_a(a, zj, torch, ctx, s):
     scale, bias = tensors.normalize_factors(3, MEAN, STD)
     ptrs, sizes = [c.data_ptr() for c in crops], [(w, h) for (_, _, w, h) in wins]
     fn = lambda: ctx.resize_device(ptrs, sizes, 3, zj.LAYOUT_HWC, OUT, OUT, zj.DTYPE_BF16, zj.TENSOR_NCHW, out.data_ptr(),
-                                   scale, bias, None, None, s.cuda_stream)
+                                   scale, bias, None, None, s.cuda_stream, antialias=a.antialias)
     timed = timer(torch, s, a.iters)
     ts = [timed(fn) for _ in range(a.reps)]
     written = out.numel() * 2
-    read = 0  # the input bytes the taps touch: rows x columns x 3 of each crop
+    read = 0  # the input bytes the taps touch: rows x columns x 3 of each crop (antialiased: all of it)
     for (_, _, w, h) in wins:
+        if a.antialias:
+            read += w * h * 3
+            continue
         x0, _, x1 = rm.taps(w, OUT)
         y0, _, y1 = rm.taps(h, OUT)
         read += len(set(x0) | set(x1)) * len(set(y0) | set(y1)) * 3
     med = spread(ts)["median"]
-    return {"part": "a", "what": f"zj_resize_device {N} RandomResizedCrop u8 HWC crops of {W}x{H} -> {OUT}x{OUT} bf16 NCHW",
+    fname = "zj_resize_filtered_device (ZJ_RESIZE_BILINEAR_AA)" if a.antialias else "zj_resize_device"
+    return {"part": "a", "what": f"{fname} {N} RandomResizedCrop u8 HWC crops of {W}x{H} -> {OUT}x{OUT} bf16 NCHW",
             "iters": a.iters, "reps": a.reps, "ms": spread(ts), "crop_bytes": sum(w * h * 3 for (_, _, w, h) in wins),
             "bytes_written": written, "bytes_read_touched": read,
             "written_share_of_8TBps": round(written / (med * 1e-3) / 8e12, 4),
@@ -110,7 +116,7 @@ def part_b(a, zj, torch, ctx, s):
     def ours():
         with torch.cuda.stream(s):
             return tensors.decode_resized_crops_to_tensor(ctx, d, frames, wins, (OUT, OUT), dtype=torch.bfloat16, mean=MEAN,
-                                                          std=STD, stream=s)
+                                                          std=STD, stream=s, antialias=a.antialias)
 
     groups = {}
     for i, (x, y, w, h) in enumerate(wins):
@@ -125,7 +131,7 @@ def part_b(a, zj, torch, ctx, s):
                 crops = tensors.decode_crops_to_tensor(ctx, d, [frames[i] for i in idx], [wins[i][:2] for i in idx], (w, h),
                                                        stream=s)
                 x = crops.permute(0, 3, 1, 2).float()
-                y = F.interpolate(x, size=(OUT, OUT), mode="bilinear", align_corners=False, antialias=False)
+                y = F.interpolate(x, size=(OUT, OUT), mode="bilinear", align_corners=False, antialias=a.antialias)
                 y = (y / 255 - mean) / std
                 out[idx] = y.to(torch.bfloat16)
             return out
@@ -139,7 +145,7 @@ def part_b(a, zj, torch, ctx, s):
     torch.cuda.synchronize()
     diff = (o.float() - t.float()).abs().max().item()
     mo, mt = spread(t_ours)["median"], spread(t_torch)["median"]
-    return {"part": "b", "what": f"decode_resized_crops_to_tensor, {N} resident {W}x{H} 4:2:0 frames, RandomResizedCrop "
+    return {"part": "b", "antialias": a.antialias, "what": f"decode_resized_crops_to_tensor, {N} resident {W}x{H} 4:2:0 frames, RandomResizedCrop "
             f"windows -> {OUT}x{OUT} bf16 NCHW normalised", "iters": a.iters, "reps": a.reps, "distinct_sizes": len(groups),
             "ours_ms": spread(t_ours), "torch_path_ms": spread(t_torch), "speedup_median": round(mt / mo, 2),
             "max_abs_diff_vs_torch": round(diff, 4)}
@@ -150,6 +156,7 @@ def main():
     ap.add_argument("--part", default="all", choices=["a", "b", "all"])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--antialias", action="store_true")
     a = ap.parse_args()
     import torch
     zj = importlib.import_module("zune-jpeg_amd")

@@ -794,7 +794,7 @@ int resize_out_args(unsigned out_w, unsigned out_h, int dtype, int out_layout, c
 // pitch[i] (bytes between its rows) already resolved
 int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, int channels,
                     int in_chw, unsigned out_w, unsigned out_h, int dtype, int nhwc, const float s[3], const float b[3],
-                    const uint8_t* flip, uint8_t* out, hipStream_t st)
+                    const uint8_t* flip, int filter, uint8_t* out, hipStream_t st)
 {
     const size_t img_bytes = (size_t)channels * out_w * out_h * resize_elem_bytes(dtype);
     ResizeParams p{};
@@ -816,7 +816,8 @@ int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
             p.pitch[i] = i < m ? pitch[f] : 0;
             if (i < m && flip && flip[f]) p.flip[i >> 5] |= 1u << (i & 31);
         }
-        ZJ_HIP(c, launch_resize(channels, in_chw, dtype, nhwc, p, st));
+        ZJ_HIP(c, filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(channels, in_chw, dtype, nhwc, p, st)
+                                                  : launch_resize(channels, in_chw, dtype, nhwc, p, st));
     }
     return ZJ_OK;
 }
@@ -847,6 +848,8 @@ int resize_scratch_done(zj_ctx* c, hipStream_t st)
 }
 
 size_t crop_bytes(unsigned w, unsigned h, int channels) { return ((size_t)w * h * channels + 15) & ~(size_t)15; }
+
+bool known_filter(int filter) { return filter == ZJ_RESIZE_BILINEAR || filter == ZJ_RESIZE_BILINEAR_AA; }
 } // namespace
 
 size_t zj_resized_out_len(const zj_frame_desc* d, unsigned out_w, unsigned out_h, int dtype)
@@ -865,6 +868,16 @@ int zj_resize_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsi
                      int channels, int in_layout, unsigned out_w, unsigned out_h, int dtype, int out_layout,
                      const float* scale, const float* bias, const uint8_t* flip, void* d_out, void* stream)
 {
+    return zj_resize_filtered_device(c, n, d_in, in_wh, in_pitch, channels, in_layout, out_w, out_h, dtype, out_layout, scale,
+                                     bias, flip, ZJ_RESIZE_BILINEAR, d_out, stream);
+}
+
+int zj_resize_filtered_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch,
+                              int channels, int in_layout, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                              const float* scale, const float* bias, const uint8_t* flip, int filter, void* d_out,
+                              void* stream)
+{
+    if (!known_filter(filter)) return ZJ_ERR_ARG;
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
     if (channels != 1 && channels != 3) return ZJ_ERR_ARG;
     if (in_layout != ZJ_LAYOUT_HWC && in_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
@@ -884,7 +897,7 @@ int zj_resize_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsi
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return resize_launches(c, n, d_in, in_wh, pitch.data(), channels, chw, out_w, out_h, dtype, out_layout == ZJ_TENSOR_NHWC,
-                           s, b, flip, (uint8_t*)d_out, st);
+                           s, b, flip, filter, (uint8_t*)d_out, st);
 }
 
 int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
@@ -892,6 +905,16 @@ int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nfr
                                    unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                    const float* bias, const uint8_t* flip, void* d_out, void* stream)
 {
+    return zj_decode_crops_resized_filtered_device(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout,
+                                                   scale, bias, flip, ZJ_RESIZE_BILINEAR, d_out, stream);
+}
+
+int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                            const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                            unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                            const float* bias, const uint8_t* flip, int filter, void* d_out, void* stream)
+{
+    if (!known_filter(filter)) return ZJ_ERR_ARG;
     if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
     const int ch = resize_channels(d);
     if (!ch) return ZJ_ERR_UNSUPPORTED;
@@ -965,7 +988,7 @@ int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nfr
             ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, st));
         }
         if ((rc = resize_launches(c, g1 - g0, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h,
-                                  dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr,
+                                  dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
                                   (uint8_t*)d_out + g0 * img_bytes, st)))
             return rc;
         if ((rc = resize_scratch_done(c, st))) return rc;
@@ -984,12 +1007,13 @@ int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t** p)
 }
 
 int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, unsigned out_w,
-                     unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, void* d_out)
+                     unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
+                     void* d_out)
 {
     const unsigned wh[2] = {w, h};
     const uint8_t fl = flip ? 1 : 0;
-    int rc = zj_resize_device(c, 1, &in, wh, nullptr, channels, in_layout, out_w, out_h, dtype, out_layout, scale, bias, &fl,
-                              d_out, nullptr);
+    int rc = zj_resize_filtered_device(c, 1, &in, wh, nullptr, channels, in_layout, out_w, out_h, dtype, out_layout, scale,
+                                       bias, &fl, filter, d_out, nullptr);
     if (rc) return rc;
     if ((rc = resize_scratch_done(c, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));

@@ -2672,7 +2672,7 @@ __attribute__((weak)) int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, un
 __attribute__((weak)) int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t** p);
 __attribute__((weak)) int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout,
                                            unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
-                                           const float* bias, int flip, void* d_out);
+                                           const float* bias, int flip, int filter, void* d_out);
 
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
@@ -2831,7 +2831,17 @@ int zj_decoder_finish_pixels_resized_crop_device(zj_decoder* d, zj_ctx* ctx, uns
                                                  unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                                  const float* bias, int flip, void* d_out, size_t out_cap, size_t* out_len)
 {
+    return zj_decoder_finish_pixels_resized_crop_filtered_device(d, ctx, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias,
+                                                                 flip, ZJ_RESIZE_BILINEAR, d_out, out_cap, out_len);
+}
+
+int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w,
+                                                          unsigned h, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                          const float* scale, const float* bias, int flip, int filter,
+                                                          void* d_out, size_t out_cap, size_t* out_len)
+{
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
     if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     zj_frame_desc fd;
@@ -2855,7 +2865,7 @@ int zj_decoder_finish_pixels_resized_crop_device(zj_decoder* d, zj_ctx* ctx, uns
     size_t got = 0;
     if ((rc = zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, crop_len, 0, &got))) return rc;
     rc = zjint_resize_one(ctx, crop, w, h, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype, out_layout, scale, bias,
-                          flip, d_out);
+                          flip, filter, d_out);
     return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 

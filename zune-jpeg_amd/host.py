@@ -66,6 +66,7 @@ FLAG_FULL_AC_VALUES = 8  # zj_options.flags only: the front-end yields AC values
 LAYOUT_HWC, LAYOUT_CHW = 0, 1
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8 = 0, 1, 2, 3  # zj_resize_device and the resized crops: the output's dtype
 TENSOR_NCHW, TENSOR_NHWC = 0, 1                          # ... and its layout
+RESIZE_BILINEAR, RESIZE_BILINEAR_AA = 0, 1               # ... and its filter (the *_filtered_device entry points)
 
 
 class FrameDesc(C.Structure):  # zj_frame_desc
@@ -164,6 +165,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_multi_decode_planes_batch", "zj_multi_decode_frames", "zj_multi_decode_frames_device",
     "zj_crop_out_len", "zj_decode_crops_device", "zj_decoder_finish_pixels_crop_device",
     "zj_resized_out_len", "zj_resize_device", "zj_decode_crops_resized_device", "zj_decoder_finish_pixels_resized_crop_device",
+    "zj_resize_filtered_device", "zj_decode_crops_resized_filtered_device",
+    "zj_decoder_finish_pixels_resized_crop_filtered_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -304,6 +307,13 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                                                C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int, vp, sz,
                                                                C.POINTER(sz)]
+    L.zj_resize_filtered_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp,
+                                            vp, C.c_int, vp, vp]
+    L.zj_decode_crops_resized_filtered_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
+                                                          C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    L.zj_decoder_finish_pixels_resized_crop_filtered_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                                                        C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int,
+                                                                        C.c_int, vp, sz, C.POINTER(sz)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -518,30 +528,40 @@ class Context:
                                             arr(d_out), out_pitch, stream), "zj_decode_crops_device", self._h)
 
     def resize_device(self, d_in, sizes, channels, in_layout, out_w, out_h, dtype, out_layout, d_out, scale=None, bias=None,
-                      flips=None, pitches=None, stream=None):
+                      flips=None, pitches=None, stream=None, antialias=False):
         """Resize + normalise (zj_resize_device): d_in = device pointers of u8 images, sizes = one (w, h) each, pitches =
-        bytes between rows (None: tight); the dense output at d_out.  Asynchronous on `stream`."""
+        bytes between rows (None: tight); the dense output at d_out.  antialias: the triangle filter
+        (zj_resize_filtered_device, RESIZE_BILINEAR_AA).  Asynchronous on `stream`."""
         n = len(d_in)
         if len(sizes) != n or (pitches is not None and len(pitches) != n):
             raise ValueError("one size (and pitch) per image")
         wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
         pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
-        _check(lib().zj_resize_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, in_layout, out_w, out_h, dtype,
-                                      out_layout, _floats(scale), _floats(bias), _flips(flips, n), d_out, stream),
-               "zj_resize_device", self._h)
+        args = (self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, in_layout, out_w, out_h, dtype, out_layout,
+                _floats(scale), _floats(bias), _flips(flips, n))
+        if antialias:
+            _check(lib().zj_resize_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, stream), "zj_resize_filtered_device",
+                   self._h)
+        else:
+            _check(lib().zj_resize_device(*args, d_out, stream), "zj_resize_device", self._h)
 
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
-                                    bias=None, flips=None, stream=None):
+                                    bias=None, flips=None, stream=None, antialias=False):
         """Resized crop windows (zj_decode_crops_resized_device): pointers as in decode_crops_device, windows = one
-        (x, y, w, h) per frame; the dense output at d_out.  Asynchronous on `stream`."""
+        (x, y, w, h) per frame; the dense output at d_out.  antialias: the triangle filter
+        (zj_decode_crops_resized_filtered_device, RESIZE_BILINEAR_AA).  Asynchronous on `stream`."""
         n = len(d_y)
         if len(windows) != n:
             raise ValueError("one window per frame")
         arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
         win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
-        _check(lib().zj_decode_crops_resized_device(self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w,
-                                                    out_h, dtype, out_layout, _floats(scale), _floats(bias), _flips(flips, n),
-                                                    d_out, stream), "zj_decode_crops_resized_device", self._h)
+        args = (self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w, out_h, dtype, out_layout,
+                _floats(scale), _floats(bias), _flips(flips, n))
+        if antialias:
+            _check(lib().zj_decode_crops_resized_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, stream),
+                   "zj_decode_crops_resized_filtered_device", self._h)
+        else:
+            _check(lib().zj_decode_crops_resized_device(*args, d_out, stream), "zj_decode_crops_resized_device", self._h)
 
     def decode_frames(self, desc, frames_planes, outs=None):
         """Host frames that are independent allocations (zj_decode_frames): frames_planes[f] = [y, cb, cr] arrays of frame
@@ -789,15 +809,20 @@ class Decoder:
         return n.value
 
     def finish_pixels_resized_crop_device(self, x, y, w, h, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
-                                          flip=False):
+                                          flip=False, antialias=False):
         """Stage 2 cut to the w x h window at (x, y) and resized (the contract of zj_decode_crops_resized_device), left in
-        HBM at device pointer d_out; returns the output's length in bytes."""
+        HBM at device pointer d_out; returns the output's length in bytes.  antialias: the triangle filter
+        (zj_decoder_finish_pixels_resized_crop_filtered_device, RESIZE_BILINEAR_AA)."""
         if self._ctx is None:
             self._ctx = Context()
         n = C.c_size_t(0)
-        rc = lib().zj_decoder_finish_pixels_resized_crop_device(self._d, self._ctx.handle, x, y, w, h, out_w, out_h, dtype,
-                                                                out_layout, _floats(scale), _floats(bias), 1 if flip else 0,
-                                                                d_out, cap, C.byref(n))
+        args = (self._d, self._ctx.handle, x, y, w, h, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
+                1 if flip else 0)
+        if antialias:
+            rc = lib().zj_decoder_finish_pixels_resized_crop_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, cap,
+                                                                             C.byref(n))
+        else:
+            rc = lib().zj_decoder_finish_pixels_resized_crop_device(*args, d_out, cap, C.byref(n))
         if rc:
             self._raise(rc)
         return n.value

@@ -153,12 +153,13 @@ def _on_stream(s, cur, tensors):
 
 
 def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
-                                   flips=None, stream=None):
+                                   flips=None, stream=None, antialias=False):
     """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
     per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
     ("NHWC") of `dtype` (default bfloat16); C = 3 for RGB / YCbCr, 1 for GRAYSCALE.  mean / std: torchvision's Normalize
     of the [0, 1] image (None: the [0, 1] image itself); unused for uint8.  flips: one bool per frame (horizontal).
+    antialias: the triangle filter of F.interpolate(antialias=True) instead of plain bilinear.
     Stream and allocator rules as decode_to_tensor."""
     import torch
     dtype = torch.bfloat16 if dtype is None else dtype
@@ -180,15 +181,15 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
                                     [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
                                     TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
-                                    s.cuda_stream)
+                                    s.cuda_stream, antialias)
     return out
 
 
 def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
-                     stream=None):
+                     stream=None, antialias=False):
     """u8 CUDA images of their own sizes resized and normalised into ONE dense tensor (zj_resize_device): images =
     [H, W, C] or [H, W] tensors (in_layout "HWC"), or [3, H, W] ("CHW"); rows may be strided, pixels not.  Output,
-    mean / std, flips and streams as decode_resized_crops_to_tensor."""
+    mean / std, flips, streams and antialias as decode_resized_crops_to_tensor."""
     import torch
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
@@ -227,5 +228,5 @@ def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HW
     _on_stream(s, cur, imgs)
     ctx.resize_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
                       size[0], size[1], code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias,
-                      flips, pitches, s.cuda_stream)
+                      flips, pitches, s.cuda_stream, antialias)
     return out
