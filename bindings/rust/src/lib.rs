@@ -218,12 +218,33 @@ extern "C" {
                                                    windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
                                                    out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
                                                    filter: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_scaled_size(d: *const zj_frame_desc, scale_log2: c_int, w: *mut c_uint, h: *mut c_uint) -> c_int;
+    pub fn zj_scaled_crop_out_len(d: *const zj_frame_desc, scale_log2: c_int, w: c_uint, h: c_uint, out_pitch: c_uint) -> usize;
+    pub fn zj_decode_crops_scaled_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize, d_y: *const *const i16,
+                                         d_cb: *const *const i16, d_cr: *const *const i16, scale_log2: c_int,
+                                         windows: *const c_uint, d_out: *const *mut u8, out_pitch: c_uint,
+                                         stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_resized_prescaled_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize,
+                                                    d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                                    windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                    out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                                    filter: c_int, max_prescale_log2: c_int, d_out: *mut c_void,
+                                                    stream: *mut c_void) -> c_int;
     pub fn zj_decoder_finish_pixels_resized_crop_filtered_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint,
                                                                  w: c_uint, h: c_uint, out_w: c_uint, out_h: c_uint,
                                                                  dtype: c_int, out_layout: c_int, scale: *const f32,
                                                                  bias: *const f32, flip: c_int, filter: c_int,
                                                                  d_out: *mut c_void, out_cap: usize,
                                                                  out_len: *mut usize) -> c_int;
+    pub fn zj_decoder_finish_pixels_scaled_device(d: *mut zj_decoder, ctx: *mut zj_ctx, scale_log2: c_int, x: c_uint, y: c_uint,
+                                                  w: c_uint, h: c_uint, d_out: *mut u8, out_cap: usize, out_pitch: c_uint,
+                                                  out_len: *mut usize) -> c_int;
+    pub fn zj_decoder_finish_pixels_resized_crop_prescaled_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint,
+                                                                  w: c_uint, h: c_uint, out_w: c_uint, out_h: c_uint,
+                                                                  dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                                  bias: *const f32, flip: c_int, filter: c_int,
+                                                                  max_prescale_log2: c_int, d_out: *mut c_void,
+                                                                  out_cap: usize, out_len: *mut usize) -> c_int;
     pub fn zj_device_pci_bus_id(device: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zj_device_numa_node(device: c_int) -> c_int;
     pub fn zj_bind_thread_to_numa_node(node: c_int) -> c_int;

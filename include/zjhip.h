@@ -303,6 +303,44 @@ ZJ_API int zj_decode_crops_resized_filtered_device(zj_ctx *ctx, const zj_frame_d
                                                    unsigned out_h, int dtype, int out_layout, const float *scale,
                                                    const float *bias, const uint8_t *flip, int filter, void *d_out,
                                                    void *stream);
+/* Reduced-size decode: the frame at 1/2, 1/4 or 1/8 of its size per axis (scale_log2 = 1, 2, 3; anything else
+ * is ZJ_ERR_ARG), straight from the coefficient planes -- libjpeg's scale_num / scale_denom, Pillow's Image.draft.  The
+ * reduced frame is ceil(width / s) x ceil(height / s).  Per component and axis a block yields N = min(8, (8 / s) x (f_max /
+ * f_c)) samples, each the mean of 8 / N consecutive outputs of the exact 8-point IDCT, taken before rounding, then rounded to
+ * nearest and clamped to 0..255 (tests/scaled_model.py is the definition, bit for bit).  Every component lands on the reduced
+ * grid, so chroma is never up-sampled; a component with N = 8 on both axes (chroma of 4:2:0 at 1/2) takes the full decode's
+ * block transform as it is.  Colour is the full decode's per-pixel arithmetic; every pixel of the reduced frame is written at
+ * its place (no early tail, no zero columns or rows).  Of zj_frame_desc.flags only ZJ_FLAG_CLAMP_DC has an effect, and only
+ * on the components that take the full transform; the other flags have none.  Outputs: RGB, GRAYSCALE, YCbCr, HWC or CHW;
+ * RGBA / RGBX are ZJ_ERR_UNSUPPORTED.  A single-component d with a colour output is zeros of that output's size, as for
+ * zj_crop_out_len.  d->out_pitch must be 0.
+ * zj_scaled_size: the reduced frame.  zj_scaled_crop_out_len: bytes of a w x h window of it whose rows lie out_pitch bytes
+ * apart (0 = tight; x 3 planes for CHW); 0 = not a valid size for d. */
+ZJ_API int zj_scaled_size(const zj_frame_desc *d, int scale_log2, unsigned *w, unsigned *h);
+ZJ_API size_t zj_scaled_crop_out_len(const zj_frame_desc *d, int scale_log2, unsigned w, unsigned h, unsigned out_pitch);
+/* nframes frames of ONE geometry, frame f cut to the window windows[4f .. 4f + 3] = x, y, w, h in REDUCED pixels (windows ==
+ * NULL: the whole reduced frame); only the blocks a window touches are read.  Each crop is tight (out_pitch 0) or has its
+ * rows out_pitch bytes apart; what lies outside a window's rows, the pitch padding included, is never written.  Pointers as
+ * in zj_decode_crops_device; batches larger than ZJ_SCATTER_MAX are split into several launches.  A scale outside 1..3, an
+ * empty window, one that leaves the reduced frame, a pitch below a row or d->out_pitch != 0 is ZJ_ERR_ARG and nothing is
+ * launched.  Asynchronous on `stream`. */
+ZJ_API int zj_decode_crops_scaled_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
+                                         const int16_t *const *d_cb, const int16_t *const *d_cr, int scale_log2,
+                                         const unsigned *windows, uint8_t *const *d_out, unsigned out_pitch, void *stream);
+/* zj_decode_crops_resized_filtered_device with a reduced-size decode under the resize: windows stay in FULL-resolution
+ * pixels; max_prescale_log2 = 0..3 (else ZJ_ERR_ARG).  Per image, s is the largest power of two <= 2^max_prescale_log2 with
+ * floor(w / s) >= out_w and floor(h / s) >= out_h, so the resize never enlarges.  An image with s = 1 is decoded and resized
+ * exactly as before.  Otherwise the output is the resize (`filter`) of the reduced crop (zj_decode_crops_scaled_device at
+ * log2 s) at the window [floor(x / s), ceil((x + w) / s)) x [floor(y / s), ceil((y + h) / s)), clipped to the reduced
+ * frame.  This is the one place where prescaling changes geometry: that window covers the requested one and exceeds it by
+ * less than s source pixels per side, which -- because w >= s x out_w -- is less than one output pixel's footprint.
+ * max_prescale_log2 = 0 is zj_decode_crops_resized_filtered_device byte for byte. */
+ZJ_API int zj_decode_crops_resized_prescaled_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes,
+                                                    const int16_t *const *d_y, const int16_t *const *d_cb,
+                                                    const int16_t *const *d_cr, const unsigned *windows, unsigned out_w,
+                                                    unsigned out_h, int dtype, int out_layout, const float *scale,
+                                                    const float *bias, const uint8_t *flip, int filter,
+                                                    int max_prescale_log2, void *d_out, void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -424,6 +462,22 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder *d, 
                                                                  int dtype, int out_layout, const float *scale,
                                                                  const float *bias, int flip, int filter, void *d_out,
                                                                  size_t out_cap, size_t *out_len);
+/* the decoder's last prepared file at 1 / 2^scale_log2, cut to the window x, y, w, h of the REDUCED frame (all four 0: the
+ * whole reduced frame), pixels left in HBM: zj_decode_crops_scaled_device's contract.  With the CPU walker only the plane
+ * rows the window's blocks lie in are uploaded; with device entropy the planes in HBM are used.
+ * *out_len = zj_scaled_crop_out_len(); out_cap below it is ZJ_ERR_ARG.  Synchronous on the context's stream. */
+ZJ_API int zj_decoder_finish_pixels_scaled_device(zj_decoder *d, zj_ctx *ctx, int scale_log2, unsigned x, unsigned y,
+                                                  unsigned w, unsigned h, uint8_t *d_out, size_t out_cap,
+                                                  unsigned out_pitch, size_t *out_len);
+/* zj_decoder_finish_pixels_resized_crop_filtered_device with a reduced-size decode under the resize
+ * (zj_decode_crops_resized_prescaled_device's contract for one image: x, y, w, h in full-resolution pixels,
+ * max_prescale_log2 = 0..3, 0 = the call without it byte for byte) */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y,
+                                                                  unsigned w, unsigned h, unsigned out_w, unsigned out_h,
+                                                                  int dtype, int out_layout, const float *scale,
+                                                                  const float *bias, int flip, int filter,
+                                                                  int max_prescale_log2, void *d_out, size_t out_cap,
+                                                                  size_t *out_len);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

@@ -1,6 +1,7 @@
 """Crop-window decode against the full decode, HIP-event timings on 128 resident 4096x4096 4:2:0 frames (synth.make_frame_t
 on the GPU, like bench.py), one JSON line:
 
+  --scaled            the reduced whole-frame decode of 16 frames at 1/2, 1/4, 1/8 against 16 full decodes
   whole_rate_ratio    16 whole-frame windows (zj_decode_crops_device) vs 16 full decodes (zj_decode_frames_device): rate
   centre_time_ratio   16 centre 2048x2048 windows vs 16 full decodes: time
   random224_speedup   128 random 224x224 windows vs 128 full decodes
@@ -26,6 +27,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--file")
     ap.add_argument("--rows", type=int, default=1024)
+    ap.add_argument("--scaled", action="store_true", help="only the reduced whole-frame case (profiles/scaled_decode.txt)")
+    ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     if a.file:
         return file_upload(a)
@@ -67,6 +70,32 @@ def main():
         outs = [base + i * ln for i in range(n)]
         return lambda: ctx.decode_crops_device(d, ptrs(0, n), ptrs(1, n), ptrs(2, n), origins, w, h, outs, 0, s.cuda_stream)
 
+    if a.scaled:
+        # Reduced whole-frame decode (zj_decode_crops_scaled_device, windows NULL) of 16 resident frames at each scale
+        # against zj_decode_frames_device of the same frames, alternating; bytes = the planes read (every block is one
+        # 128-byte line whatever the scale: the floor) + the pixels written, as a fraction of 8 TB/s
+        plane_bytes = 16 * W * H * 3                       # 4:2:0: 1.5 coefficients of 2 bytes per pixel
+        res = {"frames": f"16 of {N} x {W}x{H} 4:2:0 RGB, resident", "iters": a.iters, "reps": a.reps,
+               "plane_bytes": plane_bytes, "floor_ms_at_8TBs": round(plane_bytes / 8e12 * 1e3, 4)}
+        sp = lambda ts: {"min": round(min(ts), 4), "median": round(sorted(ts)[len(ts) // 2], 4), "max": round(max(ts), 4)}
+        for scale in (2, 4, 8):
+            rw, rh = zj.scaled_size(d, scale)
+            ln = zj.scaled_crop_out_len(d, scale, rw, rh)
+            outs = [crop_buf.data_ptr() + i * ln for i in range(16)]
+            run = lambda: ctx.decode_crops_scaled_device(d, ptrs(0, 16), ptrs(1, 16), ptrs(2, 16), scale, outs, None, 0, s.cuda_stream)
+            t_s, t_f = [], []
+            for _ in range(a.reps):
+                t_f.append(timed(full_n(16)))
+                t_s.append(timed(run))
+            ms, mf = sp(t_s)["median"], sp(t_f)["median"]
+            res[f"1/{scale}"] = {"scaled16_ms": sp(t_s), "full16_ms": sp(t_f), "time_ratio_full_over_scaled": round(mf / ms, 2),
+                                 "bytes": plane_bytes + 16 * ln,
+                                 "fraction_of_8TBs": round((plane_bytes + 16 * ln) / (ms * 1e-3) / 8e12, 3),
+                                 "full_fraction_of_8TBs": round((plane_bytes + 16 * out_len) / (mf * 1e-3) / 8e12, 3),
+                                 "times_the_plane_floor": round(ms / (plane_bytes / 8e12 * 1e3), 2)}
+        print(json.dumps(res))
+        ctx.close()
+        return
     t_full16 = timed(full_n(16))
     t_full128 = timed(full_n(N))
     t_whole16 = timed(crops(16, [(0, 0)] * 16, W, H))

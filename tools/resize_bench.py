@@ -13,7 +13,11 @@ max).  --antialias runs both parts with the triangle filter (ZJ_RESIZE_BILINEAR_
 then uses F.interpolate(antialias=True), and part (a) counts every byte of the crops as read (each output reads all the
 source pixels under it).
 
-usage: python tools/resize_bench.py [--part a|b|all] [--iters N] [--reps R] [--antialias]"""
+--max-prescale 2|4|8 (profiles/scaled_decode.txt) times part (b)'s call with a reduced-size decode under the resize
+ against max_prescale=1 in the same process, alternating, for the bilinear and the antialiased filter (or,
+with --antialias, that one alone), and gives the largest difference between the two outputs.
+
+usage: python tools/resize_bench.py [--part a|b|all] [--iters N] [--reps R] [--antialias] [--max-prescale S]"""
 import argparse
 import importlib
 import json
@@ -151,17 +155,71 @@ def part_b(a, zj, torch, ctx, s):
             "max_abs_diff_vs_torch": round(diff, 4)}
 
 
+def part_prescale(a, zj, torch, ctx, s):
+    import numpy as np
+    synth = importlib.import_module("zune-jpeg_amd.synth")
+    tensors = importlib.import_module("zune-jpeg_amd.tensors")
+    frames, qts = [], None
+    for i in range(N):
+        planes, qts = synth.make_frame_t(W, H, 2, 2, 3, seed=1234, frame_index=i, device="cuda")
+        frames.append(planes)
+    d = zj.FrameDesc.make(W, H, 2, 2, 3, zj.ColorSpace.RGB, qts)
+    wins = rrc_windows(np.random.default_rng(12), N)
+    if a.windows == "half":  # the windows that decode at 1/2: 448..895 source pixels per side for a 224 output
+        rng = np.random.default_rng(13)
+        wins = []
+        for _ in range(N):
+            w, h = int(rng.integers(2 * OUT, 4 * OUT)), int(rng.integers(2 * OUT, 4 * OUT))
+            wins.append((int(rng.integers(W - w + 1)), int(rng.integers(H - h + 1)), w, h))
+    torch.cuda.synchronize()
+    scales = {}
+    for (x, y, w, h) in wins:
+        k = 1
+        while 2 * k <= a.max_prescale and w // (2 * k) >= OUT and h // (2 * k) >= OUT:
+            k *= 2
+        scales[k] = scales.get(k, 0) + 1
+    timed = timer(torch, s, a.iters)
+    res = []
+    for aa in ((True,) if a.antialias else (False, True)):
+        def run(mp):
+            with torch.cuda.stream(s):
+                return tensors.decode_resized_crops_to_tensor(ctx, d, frames, wins, (OUT, OUT), dtype=torch.bfloat16, mean=MEAN,
+                                                              std=STD, stream=s, antialias=aa, max_prescale=mp)
+        t_plain, t_pre = [], []
+        for _ in range(a.reps):
+            t_plain.append(timed(lambda: run(1)))
+            t_pre.append(timed(lambda: run(a.max_prescale)))
+        o, q = run(1), run(a.max_prescale)
+        torch.cuda.synchronize()
+        mp_, mq = spread(t_plain)["median"], spread(t_pre)["median"]
+        res.append({"part": "prescale", "windows": a.windows, "antialias": aa, "max_prescale": a.max_prescale,
+                    "what": f"decode_resized_crops_to_tensor, {N} resident {W}x{H} 4:2:0 frames, RandomResizedCrop windows -> "
+                            f"{OUT}x{OUT} bf16 NCHW normalised", "iters": a.iters, "reps": a.reps,
+                    "images_per_scale": {str(k): v for k, v in sorted(scales.items())},
+                    "max_prescale_1_ms": spread(t_plain), "prescaled_ms": spread(t_pre), "ratio_median": round(mp_ / mq, 2),
+                    "max_abs_diff_between_them": round((o.float() - q.float()).abs().max().item(), 4)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", default="all", choices=["a", "b", "all"])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--antialias", action="store_true")
+    ap.add_argument("--max-prescale", type=int, default=1, choices=[1, 2, 4, 8])
+    ap.add_argument("--windows", default="rrc", choices=["rrc", "half"],
+                    help="with --max-prescale: RandomResizedCrop windows, or windows of 448..895 pixels (all decode at 1/2)")
     a = ap.parse_args()
     import torch
     zj = importlib.import_module("zune-jpeg_amd")
     ctx = zj.Context(zj.BACKEND_HIP, 0)
     s = torch.cuda.Stream()  # (a stream of its own: a null handle would mean the library's stream, not torch's)
+    if a.max_prescale > 1:
+        for r in part_prescale(a, zj, torch, ctx, s):
+            print(json.dumps(r), flush=True)
+        ctx.close()
+        return
     if a.part in ("a", "all"):
         print(json.dumps(part_a(a, zj, torch, ctx, s)), flush=True)
     if a.part in ("b", "all"):

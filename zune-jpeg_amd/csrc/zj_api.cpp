@@ -16,6 +16,7 @@
 #include "zj_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
+#include "zj_scaled_launch.h"
 
 using namespace zj;
 static_assert(SCATTER_MAX == ZJ_SCATTER_MAX, "include/zjhip.h and zj_device.h disagree");
@@ -909,12 +910,28 @@ int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nfr
                                                    scale, bias, flip, ZJ_RESIZE_BILINEAR, d_out, stream);
 }
 
+static int scaled_launches(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const ScaledPlan& sp, size_t nframes,
+                           const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* win,
+                           uint8_t* const* out, unsigned out_pitch, hipStream_t s);
+
 int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
                                             const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
                                             unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                             const float* bias, const uint8_t* flip, int filter, void* d_out, void* stream)
 {
-    if (!known_filter(filter)) return ZJ_ERR_ARG;
+    return zj_decode_crops_resized_prescaled_device(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout,
+                                                    scale, bias, flip, filter, 0, d_out, stream);
+}
+
+// Every image at its own scale (zj_plan.h: prescale_pick): scale 1 through the crop kernel exactly as before, the others
+// through the reduced decode at the reduced window (prescale_window); then the resize over the group's crops, in order.
+int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                             const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                             unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                             const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                             void* d_out, void* stream)
+{
+    if (!known_filter(filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
     if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
     const int ch = resize_channels(d);
     if (!ch) return ZJ_ERR_UNSUPPORTED;
@@ -941,10 +958,26 @@ int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, s
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const bool chw = pl.out == OUT_RGB_CHW;
     const size_t img_bytes = (size_t)ch * out_w * out_h * resize_elem_bytes(dtype);
+    // per image: its scale and the window the crop stage decodes (scale 1: the window itself)
+    std::vector<unsigned> cwin_store;
+    std::vector<int> klog;
+    if (max_prescale_log2 > 0) { cwin_store.assign(windows, windows + 4 * nframes); klog.assign(nframes, 0); }
+    unsigned* const cwin_w = cwin_store.data();
+    const unsigned* const cwin = max_prescale_log2 > 0 ? cwin_w : windows;
+    ScaledPlan sps[4];
+    Plan spl;
+    for (int k = 1; k <= max_prescale_log2; k++)
+        if ((rc = make_scaled_plan(d, k, spl, sps[k]))) return rc;
+    if (max_prescale_log2 > 0)
+        for (size_t f = 0; f < nframes; f++) {
+            const unsigned* w = windows + 4 * f;
+            klog[f] = prescale_pick(w[2], w[3], out_w, out_h, max_prescale_log2);
+            if (klog[f]) prescale_window(w, klog[f], d->width, d->height, cwin_w + 4 * f);
+        }
     // launch groups: frames whose crops fit RZ_GROUP_CAP together (a larger window alone); the buffer sized for the largest
     size_t need = 0;
     for (size_t f = 0, g = 0; f < nframes; f++) {
-        const size_t cb = crop_bytes(windows[4 * f + 2], windows[4 * f + 3], ch);
+        const size_t cb = crop_bytes(cwin[4 * f + 2], cwin[4 * f + 3], ch);
         g = g && g + cb > RZ_GROUP_CAP ? cb : g + cb;
         if (g > need) need = g;
     }
@@ -952,40 +985,65 @@ int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, s
     if ((rc = resize_scratch(c, need, st, &buf))) return rc;
     std::vector<uint8_t*> crops(nframes);
     std::vector<unsigned> pitch(nframes), wh(2 * nframes);
+    std::vector<const int16_t*> gy, gcb, gcr; // the frames of one scale of a group, gathered
+    std::vector<uint8_t*> gout;
+    std::vector<unsigned> gwin;
     for (size_t g0 = 0; g0 < nframes;) {
         size_t g1 = g0, off = 0;
         while (g1 < nframes) {
-            const size_t cb = crop_bytes(windows[4 * g1 + 2], windows[4 * g1 + 3], ch);
+            const size_t cb = crop_bytes(cwin[4 * g1 + 2], cwin[4 * g1 + 3], ch);
             if (g1 > g0 && off + cb > RZ_GROUP_CAP) break;
             crops[g1] = buf + off;
-            pitch[g1] = windows[4 * g1 + 2] * (chw ? 1 : ch);
-            wh[2 * g1] = windows[4 * g1 + 2]; wh[2 * g1 + 1] = windows[4 * g1 + 3];
+            pitch[g1] = cwin[4 * g1 + 2] * (chw ? 1 : ch);
+            wh[2 * g1] = cwin[4 * g1 + 2]; wh[2 * g1 + 1] = cwin[4 * g1 + 3];
             off += cb;
             g1++;
         }
         // the crops of the group, each tight at its own size (CropParams.out_pitch 0); the group before it has been read by
         // then (the same stream)
-        for (size_t f0 = g0; f0 < g1; f0 += SCATTER_MAX) {
-            const int n = (int)(g1 - f0 < (size_t)SCATTER_MAX ? g1 - f0 : (size_t)SCATTER_MAX);
-            CropParams p;
-            int nstrips = 0, ncols = 0;
-            fill_crop_params_win(d, pl, cp, d_y, chroma ? d_cb : nullptr, chroma ? d_cr : nullptr, crops.data(), windows, 4,
-                                 f0, n, p, nstrips, ncols);
-            CropZero z{};
-            z.rows_covered = pl.rows_covered; z.out_pitch = 0; z.nplanes = cp.nplanes; z.bpp = cp.bpp;
-            bool any = false;
-            for (int f = 0; f < n; f++) {
-                const unsigned* w = windows + 4 * (f0 + f);
-                z.fptr[f] = (uint64_t)(uintptr_t)crops[f0 + f];
-                z.y0[f] = w[1];
-                z.size[f] = w[2] | (w[3] << 16);
-                if ((int)w[3] > z.crop_h) z.crop_h = (int)w[3];
-                if ((int)(w[2] * cp.bpp) > z.nbytes) z.nbytes = (int)(w[2] * cp.bpp);
-                any = any || (long long)w[1] + w[3] > pl.rows_covered;
+        for (int k = 0; k <= max_prescale_log2; k++) {
+            // the frames of scale k: without prescaling the caller's arrays as they are, else gathered
+            const int16_t* const* py = d_y + g0; const int16_t* const* pcb = chroma ? d_cb + g0 : nullptr;
+            const int16_t* const* pcr = chroma ? d_cr + g0 : nullptr;
+            uint8_t* const* pout = crops.data() + g0;
+            const unsigned* pwin = windows + 4 * g0;
+            size_t ng = g1 - g0;
+            if (max_prescale_log2 > 0) {
+                gy.clear(); gcb.clear(); gcr.clear(); gout.clear(); gwin.clear();
+                for (size_t f = g0; f < g1; f++) {
+                    if (klog[f] != k) continue;
+                    gy.push_back(d_y[f]); gcb.push_back(chroma ? d_cb[f] : nullptr); gcr.push_back(chroma ? d_cr[f] : nullptr);
+                    gout.push_back(crops[f]);
+                    gwin.insert(gwin.end(), cwin + 4 * f, cwin + 4 * f + 4);
+                }
+                py = gy.data(); pcb = chroma ? gcb.data() : nullptr; pcr = chroma ? gcr.data() : nullptr;
+                pout = gout.data(); pwin = gwin.data(); ng = gy.size();
             }
-            z.nframes = n;
-            if (any) ZJ_HIP(c, launch_crop_zero(z, st));
-            ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, st));
+            if (k > 0) {
+                if (ng && (rc = scaled_launches(c, d, pl, sps[k], ng, py, pcb, pcr, pwin, pout, 0, st))) return rc;
+                continue;
+            }
+            for (size_t f0 = 0; f0 < ng; f0 += SCATTER_MAX) {
+                const int n = (int)(ng - f0 < (size_t)SCATTER_MAX ? ng - f0 : (size_t)SCATTER_MAX);
+                CropParams p;
+                int nstrips = 0, ncols = 0;
+                fill_crop_params_win(d, pl, cp, py, pcb, pcr, pout, pwin, 4, f0, n, p, nstrips, ncols);
+                CropZero z{};
+                z.rows_covered = pl.rows_covered; z.out_pitch = 0; z.nplanes = cp.nplanes; z.bpp = cp.bpp;
+                bool any = false;
+                for (int f = 0; f < n; f++) {
+                    const unsigned* w = pwin + 4 * (f0 + f);
+                    z.fptr[f] = (uint64_t)(uintptr_t)pout[f0 + f];
+                    z.y0[f] = w[1];
+                    z.size[f] = w[2] | (w[3] << 16);
+                    if ((int)w[3] > z.crop_h) z.crop_h = (int)w[3];
+                    if ((int)(w[2] * cp.bpp) > z.nbytes) z.nbytes = (int)(w[2] * cp.bpp);
+                    any = any || (long long)w[1] + w[3] > pl.rows_covered;
+                }
+                z.nframes = n;
+                if (any) ZJ_HIP(c, launch_crop_zero(z, st));
+                ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, st));
+            }
         }
         if ((rc = resize_launches(c, g1 - g0, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h,
                                   dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
@@ -994,6 +1052,115 @@ int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, s
         if ((rc = resize_scratch_done(c, st))) return rc;
         g0 = g1;
     }
+    return ZJ_OK;
+}
+
+/* ---- reduced-size decode -------------------------------------------------------- */
+int zj_scaled_size(const zj_frame_desc* d, int scale_log2, unsigned* w, unsigned* h)
+{
+    Plan pl;
+    ScaledPlan sp;
+    const int rc = make_scaled_plan(d, scale_log2, pl, sp);
+    if (rc) return rc;
+    if (w) *w = (unsigned)sp.rw;
+    if (h) *h = (unsigned)sp.rh;
+    return ZJ_OK;
+}
+
+size_t zj_scaled_crop_out_len(const zj_frame_desc* d, int scale_log2, unsigned w, unsigned h, unsigned out_pitch)
+{
+    Plan pl;
+    ScaledPlan sp;
+    if (make_scaled_plan(d, scale_log2, pl, sp)) return 0;
+    return scaled_window_len(sp, 0, 0, w, h, out_pitch);
+}
+
+// frames [0, nframes) of ONE geometry at one scale, each cut to its own window (win == nullptr: the whole reduced frame);
+// launches of up to SCATTER_MAX frames (grid.z).  Arguments checked by the caller.
+static int scaled_launches(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const ScaledPlan& sp, size_t nframes,
+                           const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* win,
+                           uint8_t* const* out, unsigned out_pitch, hipStream_t s)
+{
+    const bool chroma = pl.out != OUT_GRAY;
+    for (size_t f0 = 0; f0 < nframes; f0 += SCATTER_MAX) {
+        const int n = (int)(nframes - f0 < (size_t)SCATTER_MAX ? nframes - f0 : (size_t)SCATTER_MAX);
+        if (sp.zero) { // a single-component frame with a colour output: zeros in the windows' rows (zj_crop_out_len's rule)
+            for (int f = 0; f < n; f++) {
+                const unsigned w = win ? win[4 * (f0 + f) + 2] : (unsigned)sp.rw, h = win ? win[4 * (f0 + f) + 3] : (unsigned)sp.rh;
+                CropZero z{};
+                z.rows_covered = 0; z.crop_h = (int)h; z.nbytes = (int)(w * sp.bpp); z.out_pitch = (int)(out_pitch ? out_pitch : w * sp.bpp);
+                z.nplanes = sp.nplanes; z.crop_plane = (long long)z.out_pitch * h; z.nframes = 1; z.bpp = sp.bpp;
+                z.fptr[0] = (uint64_t)(uintptr_t)out[f0 + f];
+                ZJ_HIP(c, launch_crop_zero(z, s));
+            }
+            continue;
+        }
+        ScaledParams p;
+        fill_scaled_params(d, pl, sp, y, chroma ? cb : nullptr, chroma ? cr : nullptr, out, win, out_pitch, f0, n, p);
+        ZJ_HIP(c, launch_scaled(pl.hs, pl.vs, pl.out, sp.sl, p, s));
+    }
+    return ZJ_OK;
+}
+
+int zj_decode_crops_scaled_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                  const int16_t* const* d_cb, const int16_t* const* d_cr, int scale_log2,
+                                  const unsigned* windows, uint8_t* const* d_out, unsigned out_pitch, void* stream)
+{
+    if (!c || nframes == 0 || nframes > (size_t)1 << 20 || !d_out) return ZJ_ERR_ARG;
+    Plan pl;
+    ScaledPlan sp;
+    int rc = make_scaled_plan(d, scale_log2, pl, sp);
+    if (rc) return rc;
+    const bool chroma = !sp.zero && pl.out != OUT_GRAY;
+    if (!sp.zero && (!d_y || (chroma && (!d_cb || !d_cr)))) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < nframes; f++) {
+        const unsigned whole[4] = {0, 0, (unsigned)sp.rw, (unsigned)sp.rh};
+        const unsigned* w = windows ? windows + 4 * f : whole;
+        if (!scaled_window_len(sp, w[0], w[1], w[2], w[3], out_pitch)) return ZJ_ERR_ARG;
+        if (!d_out[f]) return ZJ_ERR_ARG;
+        if (sp.zero) continue;
+        if (!d_y[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
+        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return scaled_launches(c, d, pl, sp, nframes, d_y, d_cb, d_cr, windows, d_out, out_pitch, s);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_scaled_device).  One frame's window of the reduced frame on the
+// context stream, from planes in host memory -- only the MCU rows the window's blocks lie in are uploaded, each at its
+// full-frame offset in the context's scratch -- or from planes already in HBM.  w == 0 && h == 0: the whole reduced frame.
+int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                       int planes_on_device, int scale_log2, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out,
+                       unsigned out_pitch)
+{
+    if (!c || !d_out) return ZJ_ERR_ARG;
+    Plan pl;
+    ScaledPlan sp;
+    int rc = make_scaled_plan(d, scale_log2, pl, sp);
+    if (rc) return rc;
+    if (w == 0 && h == 0 && x == 0 && yy == 0) { w = (unsigned)sp.rw; h = (unsigned)sp.rh; }
+    if (!scaled_window_len(sp, x, yy, w, h, out_pitch)) return ZJ_ERR_ARG;
+    const bool chroma = !sp.zero && pl.out != OUT_GRAY;
+    if (!sp.zero && (!y || (chroma && (!cb || !cr)))) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    const int16_t* py = y; const int16_t* pcb = chroma ? cb : nullptr; const int16_t* pcr = chroma ? cr : nullptr;
+    if (!planes_on_device && !sp.zero) {
+        const size_t r0 = yy / sp.mh, r1 = ((size_t)yy + h + sp.mh - 1) / sp.mh; // MCU rows [r0, r1)
+        if ((rc = ensure_scratch(c, 0, pl.y_len * 2))) return rc;
+        if (chroma && ((rc = ensure_scratch(c, 1, pl.c_len * 2)) || (rc = ensure_scratch(c, 2, pl.c_len * 2)))) return rc;
+        const size_t yrow = (size_t)pl.mcu_x * pl.hs * pl.vs * 64, crow = (size_t)pl.mcu_x * 64; // i16 elements per MCU row
+        ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[0] + r0 * yrow, y + r0 * yrow, (r1 - r0) * yrow * 2, hipMemcpyHostToDevice, c->stream));
+        if (chroma) {
+            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[1] + r0 * crow, cb + r0 * crow, (r1 - r0) * crow * 2, hipMemcpyHostToDevice, c->stream));
+            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[2] + r0 * crow, cr + r0 * crow, (r1 - r0) * crow * 2, hipMemcpyHostToDevice, c->stream));
+        }
+        py = (const int16_t*)c->scratch[0];
+        pcb = chroma ? (const int16_t*)c->scratch[1] : nullptr; pcr = chroma ? (const int16_t*)c->scratch[2] : nullptr;
+    }
+    const unsigned win[4] = {x, yy, w, h};
+    if ((rc = scaled_launches(c, d, pl, sp, 1, &py, &pcb, &pcr, win, &d_out, out_pitch, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }
 

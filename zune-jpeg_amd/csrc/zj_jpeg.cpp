@@ -2674,6 +2674,11 @@ __attribute__((weak)) int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigne
                                            unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                            const float* bias, int flip, int filter, void* d_out);
 
+// ... and the reduced-size decode of one frame's window
+__attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                                             int planes_on_device, int scale_log2, unsigned x, unsigned yy, unsigned w, unsigned h,
+                                             uint8_t* d_out, unsigned out_pitch);
+
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
     if (!d || !ctx || !out) return ZJ_ERR_ARG;
@@ -2865,6 +2870,98 @@ int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder* d, zj_ctx*
     size_t got = 0;
     if ((rc = zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, crop_len, 0, &got))) return rc;
     rc = zjint_resize_one(ctx, crop, w, h, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype, out_layout, scale, bias,
+                          flip, filter, d_out);
+    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+}
+
+// The decoder's last prepared file at 1 / 2^scale_log2, cut to the window x, y, w, h of the REDUCED frame (all four 0: the
+// whole reduced frame): zj_decode_crops_scaled_device's contract.  With the CPU walker only the MCU rows the window's blocks
+// lie in are uploaded; with device entropy the planes in HBM are used.
+int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale_log2, unsigned x, unsigned y, unsigned w,
+                                           unsigned h, uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!zjint_scaled_frame || !zjint_scan_to_planes) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (scale_log2 < 1 || scale_log2 > 3) return fail(d, ZJ_ERR_ARG, "scale_log2 is 1, 2 or 3");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int ncomp = fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : ((fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : 0);
+    if (!ncomp) return fail(d, ZJ_ERR_UNSUPPORTED, "reduced outputs have 1 or 3 channels");
+    const bool zeros = fd.in_components == 1 && fd.out_colorspace != ZJ_CS_GRAYSCALE;
+    // zj_scaled_crop_out_len's arithmetic (zjint_scaled_frame checks the window in full)
+    const unsigned s = 1u << scale_log2, rw = (fd.width + s - 1) >> scale_log2, rh = (fd.height + s - 1) >> scale_log2;
+    if (x == 0 && y == 0 && w == 0 && h == 0) { w = rw; h = rh; }
+    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
+    const size_t row = (size_t)w * (chw ? 1 : ncomp), pitch = out_pitch ? (size_t)out_pitch : row;
+    const size_t need = pitch * h * (chw ? 3 : 1);
+    if (out_len) *out_len = need;
+    if (w == 0 || h == 0 || pitch < row || (size_t)x + w > rw || (size_t)y + h > rh) return fail(d, ZJ_ERR_ARG, "not a valid window of the reduced frame");
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    if (d->scan_ready) {
+        const int16_t* planes[3] = {nullptr, nullptr, nullptr};
+        unsigned status = 0;
+        int rc = zeros ? (int)ZJ_RETRY_CPU : zjint_scan_to_planes(ctx, &fd, d->blob_store.p, d->blob_len, planes, &status);
+        if (!zeros) d->gpu_status = status;
+        if (rc == ZJ_OK) {
+            const int rc2 = zjint_scaled_frame(ctx, &fd, planes[0], planes[1], planes[2], 1, scale_log2, x, y, w, h, d_out, out_pitch);
+            return rc2 ? fail(d, rc2, std::string("reduced decode: ") + zj_strerror(rc2) + " " + zj_last_error(ctx)) : ZJ_OK;
+        }
+        if (rc != ZJ_RETRY_CPU) return fail(d, rc, std::string("GPU entropy stage: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+        // handed back (or an all-zero output, whose scan is decoded all the same): the CPU walker decodes the file
+        const uint8_t* src = d->src;
+        const size_t src_len = d->src_len;
+        const int rc2 = decode_all(d, src, src_len, false, false);
+        if (rc2) return rc2;
+    }
+    const int rc = zjint_scaled_frame(ctx, &fd, d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr,
+                                      d->ncomp == 3 ? d->comps[2].coef : nullptr, 0, scale_log2, x, y, w, h, d_out, out_pitch);
+    return rc ? fail(d, rc, std::string("reduced decode: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+}
+
+// zj_decoder_finish_pixels_resized_crop_filtered_device with a reduced-size decode under the resize
+// (zj_decode_crops_resized_prescaled_device's contract for one image; x, y, w, h in full-resolution pixels)
+int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w,
+                                                           unsigned h, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                           const float* scale, const float* bias, int flip, int filter,
+                                                           int max_prescale_log2, void* d_out, size_t out_cap, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
+    int k = 0; // zj_plan.h: prescale_pick
+    for (int c = 1; c <= max_prescale_log2; c++)
+        if ((w >> c) >= out_w && (h >> c) >= out_h) k = c;
+    if (k == 0 || out_w == 0 || out_h == 0)
+        return zj_decoder_finish_pixels_resized_crop_filtered_device(d, ctx, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias,
+                                                                     flip, filter, d_out, out_cap, out_len);
+    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
+    if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED;
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int ch = (fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : (fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0);
+    if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
+    if (fd.in_components == 1 && ch == 3) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
+    const int esz = dtype == ZJ_DTYPE_F32 ? 4 : (dtype == ZJ_DTYPE_F16 || dtype == ZJ_DTYPE_BF16) ? 2 : (dtype == ZJ_DTYPE_U8 ? 1 : 0);
+    const size_t need = esz && out_w <= 8192 && out_h <= 8192 ? (size_t)ch * out_w * out_h * esz : 0;
+    if (out_len) *out_len = need;
+    if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
+    // the reduced window (zj_plan.h: prescale_window)
+    const unsigned s = 1u << k, rw = (fd.width + s - 1) >> k, rh = (fd.height + s - 1) >> k;
+    unsigned x1 = (x + w + s - 1) >> k, y1 = (y + h + s - 1) >> k;
+    if (x1 > rw) x1 = rw;
+    if (y1 > rh) y1 = rh;
+    const unsigned cx = x >> k, cy = y >> k, cw = x1 - cx, chh = y1 - cy;
+    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
+    const size_t crop_len = (size_t)cw * chh * ch;
+    uint8_t* crop = nullptr;
+    int rc = zjint_resize_scratch(ctx, crop_len, &crop);
+    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    size_t got = 0;
+    if ((rc = zj_decoder_finish_pixels_scaled_device(d, ctx, k, cx, cy, cw, chh, crop, crop_len, 0, &got))) return rc;
+    rc = zjint_resize_one(ctx, crop, cw, chh, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype, out_layout, scale, bias,
                           flip, filter, d_out);
     return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }

@@ -10,6 +10,7 @@
 
 #include "../../include/zjhip.h"
 #include "zj_device.h"
+#include "zj_scaled.h"
 
 namespace zj {
 
@@ -376,6 +377,107 @@ inline void fill_crop_params(const zj_frame_desc* d, const Plan& pl, const CropP
                              size_t f0, int n, CropParams& c, int& nstrips, int& ncols)
 {
     fill_crop_params_win(d, pl, cp, y, cb, cr, out, origins, 2, f0, n, c, nstrips, ncols);
+}
+
+// ---- reduced-size decode (zj_decode_crops_scaled_device; zj_scaled.h: ScaledParams) -------------------
+struct ScaledPlan {
+    int sl;               // scale_log2: 1, 2, 3
+    int rw, rh;           // the reduced frame: ceil(W / s) x ceil(H / s)
+    int bpp, nplanes;     // bytes per pixel of a row (CHW: 1, per plane); 3 planes for CHW
+    int mw, mh, tm;       // reduced pixels per MCU, MCUs per tile (zj_scaled.h: ScaledCfg)
+    bool zero;            // a single-component frame with a colour output: zeros (zero_output)
+};
+
+// The reduced frame of d.  RGBA / RGBX: ZJ_ERR_UNSUPPORTED; the frame's own out_pitch must be 0.  (The reduced decode has
+// no strips: the grayscale widths the reference panics on, make_plan's ZJ_ERR_PANIC, decode like every other.)
+inline int make_scaled_plan(const zj_frame_desc* d, int scale_log2, Plan& pl, ScaledPlan& sp)
+{
+    if (!d || scale_log2 < 1 || scale_log2 > 3) return ZJ_ERR_ARG;
+    if (d->out_colorspace == ZJ_CS_RGBA || d->out_colorspace == ZJ_CS_RGBX) return ZJ_ERR_UNSUPPORTED;
+    sp = ScaledPlan{};
+    sp.sl = scale_log2;
+    sp.zero = zero_output(d);
+    if (sp.zero) {
+        CropPlan cp;
+        const int rc = make_zero_crop(d, 1, 1, 0, cp);
+        if (rc) return rc;
+        sp.bpp = cp.bpp; sp.nplanes = cp.nplanes;
+        pl = Plan{};
+        pl.hs = pl.vs = 1;
+    } else {
+        const int rc = make_plan(d, pl);
+        if (rc && rc != ZJ_ERR_PANIC) return rc;
+        if (d->out_pitch != 0) return ZJ_ERR_ARG;
+        sp.nplanes = pl.out == OUT_RGB_CHW ? 3 : 1;
+        sp.bpp = pl.out == OUT_RGB_CHW ? 1 : pl.ncomp_out;
+    }
+    const unsigned s = 1u << scale_log2;
+    sp.rw = (int)((d->width + s - 1) / s); sp.rh = (int)((d->height + s - 1) / s);
+    const int ln = 8 >> scale_log2, ypm = pl.hs * pl.vs;
+    sp.mw = ln * pl.hs; sp.mh = ln * pl.vs;
+    sp.tm = pl.out != OUT_GRAY ? (ypm == 4 ? 32 : 64) : 256 / ypm;
+    return ZJ_OK;
+}
+
+// a window of the reduced frame whose rows lie out_pitch bytes apart (0: tight): its bytes, 0 = not a valid window
+inline size_t scaled_window_len(const ScaledPlan& sp, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_pitch)
+{
+    if (w == 0 || h == 0 || (size_t)x + w > (size_t)sp.rw || (size_t)y + h > (size_t)sp.rh) return 0;
+    const size_t tight = (size_t)w * sp.bpp, pitch = out_pitch ? (size_t)out_pitch : tight;
+    if (pitch < tight || pitch > (1u << 20)) return 0;
+    return pitch * h * sp.nplanes;
+}
+
+// the launch's arguments for frames [f0, f0 + n): win = x, y, w, h per frame in reduced pixels (checked by the caller),
+// nullptr = the whole reduced frame
+inline void fill_scaled_params(const zj_frame_desc* d, const Plan& pl, const ScaledPlan& sp, const int16_t* const* y,
+                               const int16_t* const* cb, const int16_t* const* cr, uint8_t* const* out, const unsigned* win,
+                               unsigned out_pitch, size_t f0, int n, ScaledParams& p)
+{
+    p.mcu_x = pl.mcu_x; p.rw = sp.rw; p.rh = sp.rh;
+    p.out_pitch = (int)out_pitch; p.clamp_dc = pl.clamp_dc; p.nframes = n;
+    for (int c = 0; c < 3; c++) build_table(d->qt[c], p.tab + TAB_DW * c);
+    p.ncols = p.nrows = 0;
+    for (int f = 0; f < SCATTER_MAX; f++) {
+        const bool in = f < n;
+        p.fptr[f][0] = in ? (uint64_t)(uintptr_t)y[f0 + f] : 0;
+        p.fptr[f][1] = in && cb ? (uint64_t)(uintptr_t)cb[f0 + f] : 0;
+        p.fptr[f][2] = in && cr ? (uint64_t)(uintptr_t)cr[f0 + f] : 0;
+        p.fptr[f][3] = in ? (uint64_t)(uintptr_t)out[f0 + f] : 0;
+        p.origin[f] = p.size[f] = p.first[f] = 0;
+        if (!in) continue;
+        const unsigned* const wf = win ? win + 4 * (f0 + f) : nullptr;
+        const int x = wf ? (int)wf[0] : 0, yy = wf ? (int)wf[1] : 0, w = wf ? (int)wf[2] : sp.rw, h = wf ? (int)wf[3] : sp.rh;
+        const int m0 = x / sp.mw, m1 = (x + w + sp.mw - 1) / sp.mw, r0 = yy / sp.mh, r1 = (yy + h + sp.mh - 1) / sp.mh;
+        p.origin[f] = (uint32_t)x | ((uint32_t)yy << 16);
+        p.size[f] = (uint32_t)w | ((uint32_t)h << 16);
+        p.first[f] = (uint32_t)m0 | ((uint32_t)r0 << 16);
+        const int nc = (m1 - m0 + sp.tm - 1) / sp.tm;
+        if (nc > p.ncols) p.ncols = nc;
+        if (r1 - r0 > p.nrows) p.nrows = r1 - r0;
+    }
+}
+
+// ---- prescaled resized crops (zj_decode_crops_resized_prescaled_device) ----------------------------------------------
+// the scale of one image: the largest k <= max_log2 with floor(w / 2^k) >= out_w and floor(h / 2^k) >= out_h (0: none) --
+// the resize that follows never enlarges
+inline int prescale_pick(unsigned w, unsigned h, unsigned out_w, unsigned out_h, int max_log2)
+{
+    int k = 0;
+    for (int c = 1; c <= max_log2; c++)
+        if ((w >> c) >= out_w && (h >> c) >= out_h) k = c;
+    return k;
+}
+// the window of the reduced frame that covers the full-resolution window x, y, w, h:
+// [floor(x / s), ceil((x + w) / s)) x [floor(y / s), ceil((y + h) / s)), clipped to the reduced frame
+inline void prescale_window(const unsigned full[4], int k, unsigned width, unsigned height, unsigned red[4])
+{
+    const unsigned s = 1u << k, rw = (width + s - 1) >> k, rh = (height + s - 1) >> k;
+    unsigned x1 = (full[0] + full[2] + s - 1) >> k, y1 = (full[1] + full[3] + s - 1) >> k;
+    if (x1 > rw) x1 = rw;
+    if (y1 > rh) y1 = rh;
+    red[0] = full[0] >> k; red[1] = full[1] >> k;
+    red[2] = x1 - red[0]; red[3] = y1 - red[1];
 }
 
 } // namespace zj

@@ -167,6 +167,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_resized_out_len", "zj_resize_device", "zj_decode_crops_resized_device", "zj_decoder_finish_pixels_resized_crop_device",
     "zj_resize_filtered_device", "zj_decode_crops_resized_filtered_device",
     "zj_decoder_finish_pixels_resized_crop_filtered_device",
+    "zj_scaled_size", "zj_scaled_crop_out_len", "zj_decode_crops_scaled_device", "zj_decode_crops_resized_prescaled_device",
+    "zj_decoder_finish_pixels_scaled_device", "zj_decoder_finish_pixels_resized_crop_prescaled_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -314,6 +316,17 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_filtered_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                                                         C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int,
                                                                         C.c_int, vp, sz, C.POINTER(sz)]
+    L.zj_scaled_size.argtypes = [C.POINTER(FrameDesc), C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    L.zj_scaled_crop_out_len.restype = sz
+    L.zj_scaled_crop_out_len.argtypes = [C.POINTER(FrameDesc), C.c_int, C.c_uint, C.c_uint, C.c_uint]
+    L.zj_decode_crops_scaled_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, C.c_int, vp, vp, C.c_uint, vp]
+    L.zj_decode_crops_resized_prescaled_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
+                                                           C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.zj_decoder_finish_pixels_scaled_device.argtypes = [vp, vp, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, sz, C.c_uint,
+                                                         C.POINTER(sz)]
+    L.zj_decoder_finish_pixels_resized_crop_prescaled_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                                                         C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int,
+                                                                         C.c_int, C.c_int, vp, sz, C.POINTER(sz)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -356,6 +369,25 @@ def crop_out_len(desc, w, h, out_pitch=0):
 def resized_out_len(desc, out_w, out_h, dtype):
     """bytes of one out_w x out_h resized output of frames of `desc` (zj_resized_out_len); 0: not supported"""
     return lib().zj_resized_out_len(C.byref(desc), out_w, out_h, dtype)
+
+
+def scale_log2(scale):
+    """1, 2, 4, 8 -> 0, 1, 2, 3 (a reduced decode's scale, a resize's max_prescale); anything else is a ValueError"""
+    if scale not in (1, 2, 4, 8) or isinstance(scale, bool):
+        raise ValueError(f"scale must be 1, 2, 4 or 8, not {scale!r}")
+    return {1: 0, 2: 1, 4: 2, 8: 3}[scale]
+
+
+def scaled_size(desc, scale):
+    """(w, h) of frames of `desc` decoded at 1/scale (zj_scaled_size): ceil(width / scale) x ceil(height / scale)"""
+    w, h = C.c_uint(0), C.c_uint(0)
+    _check(lib().zj_scaled_size(C.byref(desc), scale_log2(scale), C.byref(w), C.byref(h)), "zj_scaled_size")
+    return w.value, h.value
+
+
+def scaled_crop_out_len(desc, scale, w, h, out_pitch=0):
+    """bytes of a w x h window of the frame decoded at 1/scale (zj_scaled_crop_out_len); 0: not a valid size"""
+    return lib().zj_scaled_crop_out_len(C.byref(desc), scale_log2(scale), w, h, out_pitch)
 
 
 def _floats(v):
@@ -546,22 +578,42 @@ class Context:
             _check(lib().zj_resize_device(*args, d_out, stream), "zj_resize_device", self._h)
 
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
-                                    bias=None, flips=None, stream=None, antialias=False):
+                                    bias=None, flips=None, stream=None, antialias=False, max_prescale=1):
         """Resized crop windows (zj_decode_crops_resized_device): pointers as in decode_crops_device, windows = one
         (x, y, w, h) per frame; the dense output at d_out.  antialias: the triangle filter
-        (zj_decode_crops_resized_filtered_device, RESIZE_BILINEAR_AA).  Asynchronous on `stream`."""
+        (zj_decode_crops_resized_filtered_device, RESIZE_BILINEAR_AA).  max_prescale = 2, 4, 8: a reduced-size decode of
+        up to that scale under the resize wherever it does not enlarge (zj_decode_crops_resized_prescaled_device); 1: none,
+        today's bytes.  Asynchronous on `stream`."""
         n = len(d_y)
+        scale_log2(max_prescale)
         if len(windows) != n:
             raise ValueError("one window per frame")
         arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
         win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
         args = (self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w, out_h, dtype, out_layout,
                 _floats(scale), _floats(bias), _flips(flips, n))
-        if antialias:
+        if max_prescale != 1:
+            _check(lib().zj_decode_crops_resized_prescaled_device(*args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR,
+                                                                  scale_log2(max_prescale), d_out, stream),
+                   "zj_decode_crops_resized_prescaled_device", self._h)
+        elif antialias:
             _check(lib().zj_decode_crops_resized_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, stream),
                    "zj_decode_crops_resized_filtered_device", self._h)
         else:
             _check(lib().zj_decode_crops_resized_device(*args, d_out, stream), "zj_decode_crops_resized_device", self._h)
+
+    def decode_crops_scaled_device(self, desc, d_y, d_cb, d_cr, scale, d_out, windows=None, out_pitch=0, stream=None):
+        """Reduced-size decode (zj_decode_crops_scaled_device): the frames at 1/scale (2, 4 or 8), pointers as in
+        decode_crops_device, windows = one (x, y, w, h) per frame in reduced pixels (None: the whole reduced frame); each
+        output gets scaled_crop_out_len(desc, scale, w, h, out_pitch) bytes.  Asynchronous on `stream`."""
+        n = len(d_y)
+        k = scale_log2(scale)
+        if len(d_out) != n or (windows is not None and len(windows) != n):
+            raise ValueError("one output (and window) per frame")
+        arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
+        win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w]) if windows is not None else None
+        _check(lib().zj_decode_crops_scaled_device(self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), k, win, arr(d_out),
+                                                   out_pitch, stream), "zj_decode_crops_scaled_device", self._h)
 
     def decode_frames(self, desc, frames_planes, outs=None):
         """Host frames that are independent allocations (zj_decode_frames): frames_planes[f] = [y, cb, cr] arrays of frame
@@ -808,17 +860,39 @@ class Decoder:
             self._raise(rc)
         return n.value
 
+    def finish_pixels_scaled_device(self, scale, d_out, cap, window=None, out_pitch=0):
+        """Stage 2 at 1/scale (2, 4 or 8), cut to window = (x, y, w, h) of the reduced frame (None: all of it), pixels left
+        in HBM at device pointer d_out (the contract of zj_decode_crops_scaled_device); returns the length in bytes."""
+        if self._ctx is None:
+            self._ctx = Context()
+        k = scale_log2(scale)
+        if k == 0:
+            raise ValueError("scale must be 2, 4 or 8")
+        x, y, w, h = window if window is not None else (0, 0, 0, 0)
+        if window is not None and (w == 0 or h == 0):
+            raise ValueError("an empty window")
+        n = C.c_size_t(0)
+        rc = lib().zj_decoder_finish_pixels_scaled_device(self._d, self._ctx.handle, k, x, y, w, h, d_out, cap, out_pitch, C.byref(n))
+        if rc:
+            self._raise(rc)
+        return n.value
+
     def finish_pixels_resized_crop_device(self, x, y, w, h, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
-                                          flip=False, antialias=False):
+                                          flip=False, antialias=False, max_prescale=1):
         """Stage 2 cut to the w x h window at (x, y) and resized (the contract of zj_decode_crops_resized_device), left in
         HBM at device pointer d_out; returns the output's length in bytes.  antialias: the triangle filter
-        (zj_decoder_finish_pixels_resized_crop_filtered_device, RESIZE_BILINEAR_AA)."""
+        (zj_decoder_finish_pixels_resized_crop_filtered_device, RESIZE_BILINEAR_AA).  max_prescale = 2, 4, 8: a
+        reduced-size decode under the resize (zj_decoder_finish_pixels_resized_crop_prescaled_device); 1: none."""
         if self._ctx is None:
             self._ctx = Context()
         n = C.c_size_t(0)
+        k = scale_log2(max_prescale)
         args = (self._d, self._ctx.handle, x, y, w, h, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
                 1 if flip else 0)
-        if antialias:
+        if k:
+            rc = lib().zj_decoder_finish_pixels_resized_crop_prescaled_device(
+                *args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR, k, d_out, cap, C.byref(n))
+        elif antialias:
             rc = lib().zj_decoder_finish_pixels_resized_crop_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, cap,
                                                                              C.byref(n))
         else:

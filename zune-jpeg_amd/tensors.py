@@ -153,15 +153,19 @@ def _on_stream(s, cur, tensors):
 
 
 def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
-                                   flips=None, stream=None, antialias=False):
+                                   flips=None, stream=None, antialias=False, max_prescale=1):
     """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
     per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
     ("NHWC") of `dtype` (default bfloat16); C = 3 for RGB / YCbCr, 1 for GRAYSCALE.  mean / std: torchvision's Normalize
     of the [0, 1] image (None: the [0, 1] image itself); unused for uint8.  flips: one bool per frame (horizontal).
     antialias: the triangle filter of F.interpolate(antialias=True) instead of plain bilinear.
-    Stream and allocator rules as decode_to_tensor."""
+    max_prescale = 2, 4 or 8: every window is decoded at the largest reduced size (1/2, 1/4, 1/8, up to 1/max_prescale)
+    that still is at least the output's, and resized from there; 1 (default): none.  Anything else is a
+    ValueError.  Stream and allocator rules as decode_to_tensor."""
     import torch
+    from .host import scale_log2
+    scale_log2(max_prescale)
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
     n = len(frames)
@@ -181,8 +185,46 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
                                     [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
                                     TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
-                                    s.cuda_stream, antialias)
+                                    s.cuda_stream, antialias, max_prescale)
     return out
+
+
+def decode_scaled_to_tensor(ctx, desc, frames, scale, windows=None, stream=None):
+    """Frames decoded at 1/scale (2, 4 or 8) as one dense uint8 tensor (zj_decode_crops_scaled_device): frames = a list of
+    (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output); windows = None (the whole
+    reduced frame, ceil(width / scale) x ceil(height / scale)) or one (x, y, w, h) per frame in reduced pixels, all of one
+    size (windows of different sizes are a ValueError).  Returns [N, h, w, C], [N, 3, h, w] or [N, h, w].  Stream and
+    allocator rules as decode_to_tensor."""
+    import torch
+    from .host import scaled_size, scale_log2
+    scale_log2(scale)
+    if scale == 1:
+        raise ValueError("scale must be 2, 4 or 8")
+    n = len(frames)
+    if n == 0 or (windows is not None and len(windows) != n):
+        raise ValueError("one window per frame, at least one frame")
+    if windows is None:
+        w, h = scaled_size(desc, scale)
+    else:
+        sizes = {(int(wd[2]), int(wd[3])) for wd in windows}
+        if len(sizes) != 1:
+            raise ValueError("the windows of one call have one size")
+        w, h = sizes.pop()
+    crop_len = lib().zj_scaled_crop_out_len(C.byref(desc), scale_log2(scale), w, h, 0)
+    if crop_len == 0:
+        raise ValueError(f"{w}x{h} is not a valid window of this frame descriptor at 1/{scale}")
+    dev = frames[0][0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        storage = torch.empty(n * crop_len, dtype=torch.uint8, device=dev)
+    _on_stream(s, cur, [p for fr in frames for p in fr])
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    base = storage.data_ptr()
+    ctx.decode_crops_scaled_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
+                                   [ptr(fr[2]) for fr in frames], scale, [base + i * crop_len for i in range(n)], windows, 0,
+                                   s.cuda_stream)
+    return crop_view_of(desc, storage, n, w, h)
 
 
 def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
