@@ -1,10 +1,10 @@
 """ctypes binding of the CPU emulation of the HIP workgroup phases (tests/emu).  TEST ONLY."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
+
+import emu_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -18,20 +18,10 @@ def lib():
         srcs = [os.path.join(HERE, "emu", "zj_emu.cpp"),
                 os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_device.h"),
                 os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_plan.h"),
+                os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_geom.h"),
                 os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_huff.h"),
                 os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_huff_device.h")]
-        def stale():
-            return not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
-        if stale():
-            # pytest-xdist workers import this together: one of them builds (to a name of its own, renamed when whole),
-            # the others wait at the lock and find the library fresh
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-fno-strict-aliasing",
-                                           "-Wall", "-Wno-unknown-pragmas", "-o", tmp, srcs[0]])
-                    os.replace(tmp, so)
+        emu_build.build(so, srcs, "-O1")
         _LIB = C.CDLL(so)
     return _LIB
 

@@ -1,10 +1,10 @@
 """ctypes binding of the CPU emulation of the antialiased resize kernel (tests/emu_resize_aa).  TEST ONLY."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
+
+import emu_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -17,18 +17,9 @@ def lib():
         so = os.path.join(HERE, "emu_resize_aa", "libzjemuresizeaa.so")
         csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
         srcs = [os.path.join(HERE, "emu_resize_aa", "zj_emu_resize_aa.cpp"), os.path.join(csrc, "zj_resize_aa.h"),
-                os.path.join(csrc, "zj_resize.h")]
+                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
 
-        def stale():
-            return not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
-        if stale():
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fno-strict-aliasing",
-                                           "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", tmp, srcs[0]])
-                    os.replace(tmp, so)
+        emu_build.build(so, srcs, "-O2", ["-ffp-contract=off"])
         L = C.CDLL(so)
         L.zjea_weight.restype = C.c_uint32
         L.zjea_weight.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]

@@ -1,10 +1,10 @@
 """ctypes binding of the CPU emulation of the resize kernel (tests/emu_resize).  TEST ONLY."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
+
+import emu_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -15,18 +15,10 @@ def lib():
     global _LIB
     if _LIB is None:
         so = os.path.join(HERE, "emu_resize", "libzjemuresize.so")
-        srcs = [os.path.join(HERE, "emu_resize", "zj_emu_resize.cpp"), os.path.join(ROOT, "zune-jpeg_amd", "csrc", "zj_resize.h")]
+        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
+        srcs = [os.path.join(HERE, "emu_resize", "zj_emu_resize.cpp"), os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
 
-        def stale():
-            return not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
-        if stale():
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-fno-strict-aliasing",
-                                           "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", tmp, srcs[0]])
-                    os.replace(tmp, so)
+        emu_build.build(so, srcs, "-O1", ["-ffp-contract=off"])
         L = C.CDLL(so)
         L.zjer_tap.restype = C.c_uint32
         L.zjer_tap.argtypes = [C.c_uint32] * 3

@@ -1,10 +1,10 @@
 """ctypes binding of the CPU emulation of the reduced-size decode's kernel and plan (tests/emu_scaled).  TEST ONLY."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
+
+import emu_build
 
 from emu_c import FrameDesc
 from emu_crop_c import desc  # noqa: F401  (the same descriptor helper)
@@ -20,18 +20,9 @@ def lib():
         so = os.path.join(HERE, "emu_scaled", "libzjemuscaled.so")
         csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
         srcs = [os.path.join(HERE, "emu_scaled", "zj_emu_scaled.cpp"), os.path.join(csrc, "zj_device.h"),
-                os.path.join(csrc, "zj_scaled.h"), os.path.join(csrc, "zj_plan.h")]
+                os.path.join(csrc, "zj_scaled.h"), os.path.join(csrc, "zj_plan.h"), os.path.join(csrc, "zj_geom.h")]
 
-        def stale():
-            return not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
-        if stale():
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-fno-strict-aliasing",
-                                           "-Wall", "-Wno-unknown-pragmas", "-o", tmp, srcs[0]])
-                    os.replace(tmp, so)
+        emu_build.build(so, srcs, "-O1")
         _LIB = C.CDLL(so)
         _LIB.zjes_out_len.restype = C.c_size_t
         _LIB.zjes_out_len.argtypes = [C.POINTER(FrameDesc), C.c_int, C.c_uint, C.c_uint, C.c_uint]

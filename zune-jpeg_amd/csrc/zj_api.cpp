@@ -21,8 +21,6 @@
 using namespace zj;
 static_assert(SCATTER_MAX == ZJ_SCATTER_MAX, "include/zjhip.h and zj_device.h disagree");
 static_assert(sizeof(CropParams) <= 4096 && sizeof(CropZero) <= 4096 && sizeof(ResizeParams) <= 4096, "kernel arguments: 4 KB");
-static_assert(RZ_F32 == ZJ_DTYPE_F32 && RZ_F16 == ZJ_DTYPE_F16 && RZ_BF16 == ZJ_DTYPE_BF16 && RZ_U8 == ZJ_DTYPE_U8,
-              "include/zjhip.h and zj_resize.h disagree");
 
 namespace {
 constexpr int N_SCRATCH = 4;
@@ -644,29 +642,83 @@ size_t zj_crop_out_len(const zj_frame_desc* d, unsigned crop_w, unsigned crop_h,
     return make_crop_plan(d, crop_w, crop_h, out_pitch, pl, cp) == ZJ_OK ? cp.out_len : 0;
 }
 
-// frames [0, nframes) of ONE geometry, each cut to its own window; launches of up to SCATTER_MAX frames (grid.z)
+// every plane of frames [0, nframes): there, and 16-byte aligned (the kernels' loads)
+static int check_plane_ptrs(const int16_t* const* d_y, const int16_t* const* d_cb, const int16_t* const* d_cr, bool chroma,
+                            size_t nframes)
+{
+    if (!d_y || (chroma && (!d_cb || !d_cr))) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < nframes; f++) {
+        if (!d_y[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
+        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
+    }
+    return ZJ_OK;
+}
+
+// Host planes to the context's scratch, on the context stream: the elements [r0, r1) x yrow of y (x crow of cb and cr, with
+// chroma) at their full-frame offsets -- whole strips or MCU rows are contiguous ranges of a plane, and nothing reads across
+// one.  dev: the device planes.
+static int upload_plane_rows(zj_ctx* c, const Plan& pl, bool chroma, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                             size_t r0, size_t r1, size_t yrow, size_t crow, const int16_t* dev[3])
+{
+    int rc;
+    if ((rc = ensure_scratch(c, 0, pl.y_len * 2))) return rc;
+    if (chroma && ((rc = ensure_scratch(c, 1, pl.c_len * 2)) || (rc = ensure_scratch(c, 2, pl.c_len * 2)))) return rc;
+    if (r1 > r0) {
+        ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[0] + r0 * yrow, y + r0 * yrow, (r1 - r0) * yrow * 2, hipMemcpyHostToDevice, c->stream));
+        if (chroma) {
+            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[1] + r0 * crow, cb + r0 * crow, (r1 - r0) * crow * 2, hipMemcpyHostToDevice, c->stream));
+            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[2] + r0 * crow, cr + r0 * crow, (r1 - r0) * crow * 2, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    dev[0] = (const int16_t*)c->scratch[0];
+    dev[1] = chroma ? (const int16_t*)c->scratch[1] : nullptr; dev[2] = chroma ? (const int16_t*)c->scratch[2] : nullptr;
+    return ZJ_OK;
+}
+
+// Zeros for the rows of the crops of frames [f0, f0 + n) that lie at or below rows_covered (Q6; rows_covered 0: every row,
+// the all-zero output), from a launch of their own, if any frame has such rows.  win, stride: as fill_crop_params_win's
+// (stride 2: every window cp.w x cp.h at cp.out_pitch; stride 4: each crop tight at its own size).
+static int crop_zero_launch(zj_ctx* c, int rows_covered, const CropPlan& cp, const unsigned* win, int stride, uint8_t* const* out,
+                            size_t f0, int n, hipStream_t s)
+{
+    CropZero z{};
+    z.rows_covered = rows_covered; z.nplanes = cp.nplanes; z.bpp = cp.bpp; z.nframes = n;
+    if (stride == 2) {
+        z.crop_h = cp.h; z.nbytes = cp.w * cp.bpp;
+        z.out_pitch = (int)cp.out_pitch; z.crop_plane = (long long)cp.out_pitch * cp.h;
+    }
+    bool any = false;
+    for (int f = 0; f < n; f++) {
+        const unsigned* const w = win + (size_t)stride * (f0 + f);
+        unsigned h = (unsigned)cp.h;
+        z.fptr[f] = (uint64_t)(uintptr_t)out[f0 + f];
+        z.y0[f] = w[1];
+        if (stride == 4) {
+            h = w[3];
+            z.size[f] = w[2] | (w[3] << 16);
+            if ((int)w[3] > z.crop_h) z.crop_h = (int)w[3];
+            if ((int)(w[2] * cp.bpp) > z.nbytes) z.nbytes = (int)(w[2] * cp.bpp);
+        }
+        any = any || (long long)w[1] + h > rows_covered;
+    }
+    if (any) ZJ_HIP(c, launch_crop_zero(z, s));
+    return ZJ_OK;
+}
+
+// frames [0, nframes) of ONE geometry, each cut to its own window (win, stride: as fill_crop_params_win's); launches of up
+// to SCATTER_MAX frames (grid.z)
 static int decode_crops_impl(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, size_t nframes,
-                             const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins,
-                             uint8_t* const* out, hipStream_t s)
+                             const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* win,
+                             int stride, uint8_t* const* out, hipStream_t s)
 {
     const bool chroma = pl.out != OUT_GRAY;
     for (size_t f0 = 0; f0 < nframes; f0 += SCATTER_MAX) {
         const int n = (int)(nframes - f0 < (size_t)SCATTER_MAX ? nframes - f0 : (size_t)SCATTER_MAX);
         CropParams p;
         int nstrips = 0, ncols = 0;
-        fill_crop_params(d, pl, cp, y, chroma ? cb : nullptr, chroma ? cr : nullptr, out, origins, f0, n, p, nstrips, ncols);
-        // the window rows at or below rows_covered (Q6): zeros, from a launch of their own, for the frames that have any
-        CropZero z{};
-        z.rows_covered = pl.rows_covered; z.crop_h = cp.h; z.nbytes = cp.w * cp.bpp; z.out_pitch = (int)cp.out_pitch;
-        z.nplanes = cp.nplanes; z.crop_plane = (long long)cp.out_pitch * cp.h;
-        bool any = false;
-        for (int f = 0; f < n; f++) {
-            z.fptr[f] = (uint64_t)(uintptr_t)out[f0 + f];
-            z.y0[f] = origins[2 * (f0 + f) + 1];
-            any = any || (long long)z.y0[f] + cp.h > pl.rows_covered;
-        }
-        z.nframes = n;
-        if (any) ZJ_HIP(c, launch_crop_zero(z, s));
+        fill_crop_params_win(d, pl, cp, y, chroma ? cb : nullptr, chroma ? cr : nullptr, out, win, stride, f0, n, p, nstrips, ncols);
+        const int rc = crop_zero_launch(c, pl.rows_covered, cp, win, stride, out, f0, n, s);
+        if (rc) return rc;
         ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, s));
     }
     return ZJ_OK;
@@ -693,16 +745,12 @@ int zj_decode_crops_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, co
     CropPlan cp;
     int rc = check_crop_args(c, d, nframes, origins, crop_w, crop_h, out_pitch, pl, cp);
     if (rc) return rc;
-    if (!d_y || !d_out) return ZJ_ERR_ARG;
-    const bool chroma = pl.out != OUT_GRAY;
-    if (chroma && (!d_cb || !d_cr)) return ZJ_ERR_ARG;
-    for (size_t f = 0; f < nframes; f++) {
-        if (!d_y[f] || !d_out[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
-        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
-    }
+    if (!d_out || (rc = check_plane_ptrs(d_y, d_cb, d_cr, pl.out != OUT_GRAY, nframes))) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < nframes; f++)
+        if (!d_out[f]) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return decode_crops_impl(c, d, pl, cp, nframes, d_y, d_cb, d_cr, origins, d_out, s);
+    return decode_crops_impl(c, d, pl, cp, nframes, d_y, d_cb, d_cr, origins, 2, d_out, s);
 }
 
 // Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_crop_device).  One frame's window on the context stream, from
@@ -719,25 +767,15 @@ int zjint_crop_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const 
     const bool chroma = pl.out != OUT_GRAY;
     if (!y || !d_out || (chroma && (!cb || !cr))) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
-    const int16_t* py = y; const int16_t* pcb = cb; const int16_t* pcr = cr;
+    const int16_t* p[3] = {y, cb, cr};
     if (!planes_on_device) {
         int s0, s1, k0, k1;
         crop_window(d, pl, cp, x, yy, s0, s1, k0, k1);
-        if ((rc = ensure_scratch(c, 0, pl.y_len * 2))) return rc;
-        if (chroma && ((rc = ensure_scratch(c, 1, pl.c_len * 2)) || (rc = ensure_scratch(c, 2, pl.c_len * 2)))) return rc;
         // i16 elements per strip (the split of decode_device_impl's ZJ_SPLIT experiment)
         const size_t yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8), crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
-        if (s1 > s0) {
-            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[0] + s0 * yrow, y + s0 * yrow, (s1 - s0) * yrow * 2, hipMemcpyHostToDevice, c->stream));
-            if (chroma) {
-                ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[1] + s0 * crow, cb + s0 * crow, (s1 - s0) * crow * 2, hipMemcpyHostToDevice, c->stream));
-                ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[2] + s0 * crow, cr + s0 * crow, (s1 - s0) * crow * 2, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        py = (const int16_t*)c->scratch[0];
-        pcb = chroma ? (const int16_t*)c->scratch[1] : nullptr; pcr = chroma ? (const int16_t*)c->scratch[2] : nullptr;
+        if ((rc = upload_plane_rows(c, pl, chroma, y, cb, cr, (size_t)s0, (size_t)s1, yrow, crow, p))) return rc;
     }
-    if ((rc = decode_crops_impl(c, d, pl, cp, 1, &py, &pcb, &pcr, origin, &d_out, c->stream))) return rc;
+    if ((rc = decode_crops_impl(c, d, pl, cp, 1, &p[0], &p[1], &p[2], origin, 2, &d_out, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }
@@ -752,11 +790,8 @@ int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy,
     if (rc) return rc;
     if ((size_t)x + w > d->width || (size_t)yy + h > d->height) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
-    CropZero z{};
-    z.rows_covered = 0; z.crop_h = cp.h; z.nbytes = cp.w * cp.bpp; z.out_pitch = (int)cp.out_pitch;
-    z.nplanes = cp.nplanes; z.crop_plane = (long long)cp.out_pitch * cp.h; z.nframes = 1;
-    z.fptr[0] = (uint64_t)(uintptr_t)d_out; z.y0[0] = yy;
-    ZJ_HIP(c, launch_crop_zero(z, c->stream));
+    const unsigned origin[2] = {x, yy};
+    if ((rc = crop_zero_launch(c, 0, cp, origin, 2, &d_out, 0, 1, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }
@@ -765,22 +800,13 @@ int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy,
 namespace {
 constexpr size_t RZ_GROUP_CAP = (size_t)256 << 20; // u8 crop bytes per launch group of zj_decode_crops_resized_device
 
-// channels of the resized output of descriptor d: 3 (RGB, YCbCr), 1 (GRAYSCALE), 0 (no such output: RGBA / RGBX)
-int resize_channels(const zj_frame_desc* d)
-{
-    if (!d) return 0;
-    if (d->out_colorspace == ZJ_CS_RGB || d->out_colorspace == ZJ_CS_YCBCR) return 3;
-    return d->out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0;
-}
-
 bool finite_f32(float v) { return v - v == 0.f; }
 
 // the output's arguments; s[] / b[]: the per-channel factors of the kernel (s_c = scale_c * 2^-16)
 int resize_out_args(unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
                     int channels, float s[3], float b[3])
 {
-    if (out_w == 0 || out_h == 0 || out_w > (unsigned)RESIZE_MAX_OUT || out_h > (unsigned)RESIZE_MAX_OUT) return ZJ_ERR_ARG;
-    if (dtype < ZJ_DTYPE_F32 || dtype > ZJ_DTYPE_U8) return ZJ_ERR_ARG;
+    if (!resized_len(channels, out_w, out_h, dtype)) return ZJ_ERR_ARG; // (the size or the dtype)
     if (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC) return ZJ_ERR_ARG;
     for (int k = 0; k < 3; k++) {
         const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
@@ -797,7 +823,7 @@ int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
                     int in_chw, unsigned out_w, unsigned out_h, int dtype, int nhwc, const float s[3], const float b[3],
                     const uint8_t* flip, int filter, uint8_t* out, hipStream_t st)
 {
-    const size_t img_bytes = (size_t)channels * out_w * out_h * resize_elem_bytes(dtype);
+    const size_t img_bytes = resized_len(channels, out_w, out_h, dtype);
     ResizeParams p{};
     p.out_w = (int)out_w; p.out_h = (int)out_h;
     for (int k = 0; k < 3; k++) { p.scale[k] = s[k]; p.bias[k] = b[k]; }
@@ -860,9 +886,7 @@ size_t zj_resized_out_len(const zj_frame_desc* d, unsigned out_w, unsigned out_h
     const int ch = resize_channels(d);
     if (!ch) return 0;
     if (zero_output(d) ? make_zero_crop(d, 1, 1, 0, cp) : make_crop_plan(d, 1, 1, 0, pl, cp)) return 0;
-    float s[3], b[3];
-    if (resize_out_args(out_w, out_h, dtype, ZJ_TENSOR_NCHW, nullptr, nullptr, ch, s, b)) return 0;
-    return (size_t)ch * out_w * out_h * resize_elem_bytes(dtype);
+    return resized_len(ch, out_w, out_h, dtype);
 }
 
 int zj_resize_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch,
@@ -910,9 +934,33 @@ int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nfr
                                                    scale, bias, flip, ZJ_RESIZE_BILINEAR, d_out, stream);
 }
 
+/* the reduced-size decode's launches, which the prescaled resized crops below use as well */
+// frames [0, nframes) of ONE geometry at one scale, each cut to its own window (win == nullptr: the whole reduced frame);
+// launches of up to SCATTER_MAX frames (grid.z).  Arguments checked by the caller.
 static int scaled_launches(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const ScaledPlan& sp, size_t nframes,
                            const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* win,
-                           uint8_t* const* out, unsigned out_pitch, hipStream_t s);
+                           uint8_t* const* out, unsigned out_pitch, hipStream_t s)
+{
+    const bool chroma = pl.out != OUT_GRAY;
+    for (size_t f0 = 0; f0 < nframes; f0 += SCATTER_MAX) {
+        const int n = (int)(nframes - f0 < (size_t)SCATTER_MAX ? nframes - f0 : (size_t)SCATTER_MAX);
+        if (sp.zero) { // a single-component frame with a colour output: zeros in the windows' rows (zj_crop_out_len's rule)
+            for (int f = 0; f < n; f++) { // (one launch each: with a pitch every window has a plane size of its own)
+                const unsigned origin[2] = {0, 0};
+                CropPlan zc{};
+                zc.w = win ? (int)win[4 * (f0 + f) + 2] : sp.rw; zc.h = win ? (int)win[4 * (f0 + f) + 3] : sp.rh;
+                zc.bpp = sp.bpp; zc.nplanes = sp.nplanes; zc.out_pitch = out_pitch ? out_pitch : (size_t)zc.w * sp.bpp;
+                const int rc = crop_zero_launch(c, 0, zc, origin, 2, out + f0 + f, 0, 1, s);
+                if (rc) return rc;
+            }
+            continue;
+        }
+        ScaledParams p;
+        fill_scaled_params(d, pl, sp, y, chroma ? cb : nullptr, chroma ? cr : nullptr, out, win, out_pitch, f0, n, p);
+        ZJ_HIP(c, launch_scaled(pl.hs, pl.vs, pl.out, sp.sl, p, s));
+    }
+    return ZJ_OK;
+}
 
 int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
                                             const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
@@ -942,7 +990,7 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
     float s[3], b[3];
     if ((rc = resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, ch, s, b))) return rc;
     const bool chroma = pl.out != OUT_GRAY;
-    if (chroma && (!d_cb || !d_cr)) return ZJ_ERR_ARG;
+    if ((rc = check_plane_ptrs(d_y, d_cb, d_cr, chroma, nframes))) return rc;
     for (size_t f = 0; f < nframes; f++) {
         const unsigned* w = windows + 4 * f;
         if (w[2] == 0 || w[3] == 0) return ZJ_ERR_ARG;
@@ -951,13 +999,11 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
         int s0, s1, k0, k1;
         if ((size_t)w[2] > d->width || (size_t)w[3] > d->height) return ZJ_ERR_ARG;
         if ((rc = crop_window(d, pl, cw, w[0], w[1], s0, s1, k0, k1))) return rc;
-        if (!d_y[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
-        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
     }
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const bool chw = pl.out == OUT_RGB_CHW;
-    const size_t img_bytes = (size_t)ch * out_w * out_h * resize_elem_bytes(dtype);
+    const size_t img_bytes = resized_len(ch, out_w, out_h, dtype);
     // per image: its scale and the window the crop stage decodes (scale 1: the window itself)
     std::vector<unsigned> cwin_store;
     std::vector<int> klog;
@@ -1019,31 +1065,10 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
                 py = gy.data(); pcb = chroma ? gcb.data() : nullptr; pcr = chroma ? gcr.data() : nullptr;
                 pout = gout.data(); pwin = gwin.data(); ng = gy.size();
             }
-            if (k > 0) {
-                if (ng && (rc = scaled_launches(c, d, pl, sps[k], ng, py, pcb, pcr, pwin, pout, 0, st))) return rc;
-                continue;
-            }
-            for (size_t f0 = 0; f0 < ng; f0 += SCATTER_MAX) {
-                const int n = (int)(ng - f0 < (size_t)SCATTER_MAX ? ng - f0 : (size_t)SCATTER_MAX);
-                CropParams p;
-                int nstrips = 0, ncols = 0;
-                fill_crop_params_win(d, pl, cp, py, pcb, pcr, pout, pwin, 4, f0, n, p, nstrips, ncols);
-                CropZero z{};
-                z.rows_covered = pl.rows_covered; z.out_pitch = 0; z.nplanes = cp.nplanes; z.bpp = cp.bpp;
-                bool any = false;
-                for (int f = 0; f < n; f++) {
-                    const unsigned* w = pwin + 4 * (f0 + f);
-                    z.fptr[f] = (uint64_t)(uintptr_t)pout[f0 + f];
-                    z.y0[f] = w[1];
-                    z.size[f] = w[2] | (w[3] << 16);
-                    if ((int)w[3] > z.crop_h) z.crop_h = (int)w[3];
-                    if ((int)(w[2] * cp.bpp) > z.nbytes) z.nbytes = (int)(w[2] * cp.bpp);
-                    any = any || (long long)w[1] + w[3] > pl.rows_covered;
-                }
-                z.nframes = n;
-                if (any) ZJ_HIP(c, launch_crop_zero(z, st));
-                ZJ_HIP(c, launch_crop(pl.hs, pl.vs, pl.out, p, st));
-            }
+            if (!ng) continue;
+            if ((rc = k > 0 ? scaled_launches(c, d, pl, sps[k], ng, py, pcb, pcr, pwin, pout, 0, st)
+                            : decode_crops_impl(c, d, pl, cp, ng, py, pcb, pcr, pwin, 4, pout, st)))
+                return rc;
         }
         if ((rc = resize_launches(c, g1 - g0, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h,
                                   dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
@@ -1075,33 +1100,6 @@ size_t zj_scaled_crop_out_len(const zj_frame_desc* d, int scale_log2, unsigned w
     return scaled_window_len(sp, 0, 0, w, h, out_pitch);
 }
 
-// frames [0, nframes) of ONE geometry at one scale, each cut to its own window (win == nullptr: the whole reduced frame);
-// launches of up to SCATTER_MAX frames (grid.z).  Arguments checked by the caller.
-static int scaled_launches(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const ScaledPlan& sp, size_t nframes,
-                           const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* win,
-                           uint8_t* const* out, unsigned out_pitch, hipStream_t s)
-{
-    const bool chroma = pl.out != OUT_GRAY;
-    for (size_t f0 = 0; f0 < nframes; f0 += SCATTER_MAX) {
-        const int n = (int)(nframes - f0 < (size_t)SCATTER_MAX ? nframes - f0 : (size_t)SCATTER_MAX);
-        if (sp.zero) { // a single-component frame with a colour output: zeros in the windows' rows (zj_crop_out_len's rule)
-            for (int f = 0; f < n; f++) {
-                const unsigned w = win ? win[4 * (f0 + f) + 2] : (unsigned)sp.rw, h = win ? win[4 * (f0 + f) + 3] : (unsigned)sp.rh;
-                CropZero z{};
-                z.rows_covered = 0; z.crop_h = (int)h; z.nbytes = (int)(w * sp.bpp); z.out_pitch = (int)(out_pitch ? out_pitch : w * sp.bpp);
-                z.nplanes = sp.nplanes; z.crop_plane = (long long)z.out_pitch * h; z.nframes = 1; z.bpp = sp.bpp;
-                z.fptr[0] = (uint64_t)(uintptr_t)out[f0 + f];
-                ZJ_HIP(c, launch_crop_zero(z, s));
-            }
-            continue;
-        }
-        ScaledParams p;
-        fill_scaled_params(d, pl, sp, y, chroma ? cb : nullptr, chroma ? cr : nullptr, out, win, out_pitch, f0, n, p);
-        ZJ_HIP(c, launch_scaled(pl.hs, pl.vs, pl.out, sp.sl, p, s));
-    }
-    return ZJ_OK;
-}
-
 int zj_decode_crops_scaled_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
                                   const int16_t* const* d_cb, const int16_t* const* d_cr, int scale_log2,
                                   const unsigned* windows, uint8_t* const* d_out, unsigned out_pitch, void* stream)
@@ -1112,15 +1110,12 @@ int zj_decode_crops_scaled_device(zj_ctx* c, const zj_frame_desc* d, size_t nfra
     int rc = make_scaled_plan(d, scale_log2, pl, sp);
     if (rc) return rc;
     const bool chroma = !sp.zero && pl.out != OUT_GRAY;
-    if (!sp.zero && (!d_y || (chroma && (!d_cb || !d_cr)))) return ZJ_ERR_ARG;
+    if (!sp.zero && (rc = check_plane_ptrs(d_y, d_cb, d_cr, chroma, nframes))) return rc;
     for (size_t f = 0; f < nframes; f++) {
         const unsigned whole[4] = {0, 0, (unsigned)sp.rw, (unsigned)sp.rh};
         const unsigned* w = windows ? windows + 4 * f : whole;
         if (!scaled_window_len(sp, w[0], w[1], w[2], w[3], out_pitch)) return ZJ_ERR_ARG;
         if (!d_out[f]) return ZJ_ERR_ARG;
-        if (sp.zero) continue;
-        if (!d_y[f] || (chroma && (!d_cb[f] || !d_cr[f]))) return ZJ_ERR_ARG;
-        if (((uintptr_t)d_y[f] | (chroma ? (uintptr_t)d_cb[f] | (uintptr_t)d_cr[f] : 0)) & 15) return ZJ_ERR_ARG;
     }
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -1144,22 +1139,14 @@ int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, cons
     const bool chroma = !sp.zero && pl.out != OUT_GRAY;
     if (!sp.zero && (!y || (chroma && (!cb || !cr)))) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
-    const int16_t* py = y; const int16_t* pcb = chroma ? cb : nullptr; const int16_t* pcr = chroma ? cr : nullptr;
+    const int16_t* p[3] = {y, chroma ? cb : nullptr, chroma ? cr : nullptr};
     if (!planes_on_device && !sp.zero) {
         const size_t r0 = yy / sp.mh, r1 = ((size_t)yy + h + sp.mh - 1) / sp.mh; // MCU rows [r0, r1)
-        if ((rc = ensure_scratch(c, 0, pl.y_len * 2))) return rc;
-        if (chroma && ((rc = ensure_scratch(c, 1, pl.c_len * 2)) || (rc = ensure_scratch(c, 2, pl.c_len * 2)))) return rc;
         const size_t yrow = (size_t)pl.mcu_x * pl.hs * pl.vs * 64, crow = (size_t)pl.mcu_x * 64; // i16 elements per MCU row
-        ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[0] + r0 * yrow, y + r0 * yrow, (r1 - r0) * yrow * 2, hipMemcpyHostToDevice, c->stream));
-        if (chroma) {
-            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[1] + r0 * crow, cb + r0 * crow, (r1 - r0) * crow * 2, hipMemcpyHostToDevice, c->stream));
-            ZJ_HIP(c, hipMemcpyAsync((int16_t*)c->scratch[2] + r0 * crow, cr + r0 * crow, (r1 - r0) * crow * 2, hipMemcpyHostToDevice, c->stream));
-        }
-        py = (const int16_t*)c->scratch[0];
-        pcb = chroma ? (const int16_t*)c->scratch[1] : nullptr; pcr = chroma ? (const int16_t*)c->scratch[2] : nullptr;
+        if ((rc = upload_plane_rows(c, pl, chroma, y, cb, cr, r0, r1, yrow, crow, p))) return rc;
     }
     const unsigned win[4] = {x, yy, w, h};
-    if ((rc = scaled_launches(c, d, pl, sp, 1, &py, &pcb, &pcr, win, &d_out, out_pitch, c->stream))) return rc;
+    if ((rc = scaled_launches(c, d, pl, sp, 1, &p[0], &p[1], &p[2], win, &d_out, out_pitch, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }

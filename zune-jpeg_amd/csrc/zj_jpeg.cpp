@@ -32,6 +32,7 @@
 
 #include "../../include/zjhip.h"
 #include "zj_crew.h"
+#include "zj_geom.h"
 #include "zj_huff.h"
 
 namespace {
@@ -2783,53 +2784,109 @@ int zj_decoder_finish_pixels_device(zj_decoder* d, zj_ctx* ctx, uint8_t* d_out, 
     return finish_impl(d, ctx, d_out, out_cap, out_len, 1);
 }
 
-int zj_decoder_finish_pixels_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
-                                         uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
+// A window of the decoder's last file into HBM: of the frame at full resolution (reduced false: zjint_crop_frame) or of the
+// frame reduced by 2^k (zjint_scaled_frame; x, y, w, h all 0: the whole reduced frame).  With a scan prepared for the device
+// the entropy stage runs there and the planes in HBM are used; what the device hands back (ZJ_RETRY_CPU), and an all-zero
+// output, whose scan is decoded all the same (a damaged one is an error here too), goes through the CPU walker, whose
+// planes are uploaded by the rows the window needs.
+static int finish_window(zj_decoder* d, zj_ctx* ctx, bool reduced, int k, unsigned x, unsigned y, unsigned w, unsigned h,
+                         uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
 {
-    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
-    if (!zjint_crop_frame || !zjint_scan_to_planes || !zjint_crop_zeros) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    using namespace zj;
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (reduced && (k < 1 || k > 3)) return fail(d, ZJ_ERR_ARG, "scale_log2 is 1, 2 or 3");
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
+    if (reduced && !resize_channels(&fd)) return fail(d, ZJ_ERR_UNSUPPORTED, "reduced outputs have 1 or 3 channels");
     // a single-component file asked for a colour output: zeros, as finish_impl writes them (worker.rs:131)
-    const bool zeros = fd.in_components == 1 && fd.out_colorspace != ZJ_CS_GRAYSCALE;
-    // zj_crop_out_len's arithmetic, which is zj_out_len's for the window (the crop functions check the window in full)
-    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
-    const int ncomp = fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : ((fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : 4);
-    const size_t row = (size_t)w * (chw ? 1 : ncomp), pitch = out_pitch ? (size_t)out_pitch : row;
-    const size_t need = pitch * h * (chw ? 3 : 1);
-    if (out_len) *out_len = need;
-    if (w == 0 || h == 0 || pitch < row || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
-    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
-    if (zeros) {
-        if (d->scan_ready) { // as finish_impl: the scan is decoded all the same, a damaged one is an error here too
-            const uint8_t* src = d->src;
-            const size_t src_len = d->src_len;
-            const int rc2 = decode_all(d, src, src_len, false, false);
-            if (rc2) return rc2;
-        }
-        const int rc = zjint_crop_zeros(ctx, &fd, x, y, w, h, d_out, out_pitch);
-        return rc ? fail(d, rc, "crop zeros") : ZJ_OK;
-    }
+    const bool zeros = zero_output(&fd);
+    const unsigned fw = reduced ? reduced_dim(fd.width, k) : fd.width, fh = reduced ? reduced_dim(fd.height, k) : fd.height;
+    if (reduced && x == 0 && y == 0 && w == 0 && h == 0) { w = fw; h = fh; }
+    // (the callee checks the window in full)
+    const WindowLayout g = window_layout(&fd, w, h, out_pitch);
+    if (out_len) *out_len = g.len;
+    if (!window_inside(g, x, y, w, h, fw, fh)) return fail(d, ZJ_ERR_ARG, reduced ? "not a valid window of the reduced frame" : "not a valid crop window");
+    if (out_cap < g.len) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    const auto window = [&](const int16_t* yp, const int16_t* cb, const int16_t* cr, int on_device) {
+        const int rc = reduced ? zjint_scaled_frame(ctx, &fd, yp, cb, cr, on_device, k, x, y, w, h, d_out, out_pitch)
+                               : zjint_crop_frame(ctx, &fd, yp, cb, cr, on_device, x, y, w, h, d_out, out_pitch);
+        return rc ? fail(d, rc, std::string(reduced ? "reduced decode: " : "crop: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : (int)ZJ_OK;
+    };
     if (d->scan_ready) {
         const int16_t* planes[3] = {nullptr, nullptr, nullptr};
-        unsigned status = 0;
-        const int rc = zjint_scan_to_planes(ctx, &fd, d->blob_store.p, d->blob_len, planes, &status);
-        d->gpu_status = status;
-        if (rc == ZJ_OK) {
-            const int rc2 = zjint_crop_frame(ctx, &fd, planes[0], planes[1], planes[2], 1, x, y, w, h, d_out, out_pitch);
-            return rc2 ? fail(d, rc2, std::string("crop: ") + zj_strerror(rc2) + " " + zj_last_error(ctx)) : ZJ_OK;
+        int rc = ZJ_RETRY_CPU;
+        if (!zeros) {
+            unsigned status = 0;
+            rc = zjint_scan_to_planes(ctx, &fd, d->blob_store.p, d->blob_len, planes, &status);
+            d->gpu_status = status;
         }
+        if (rc == ZJ_OK) return window(planes[0], planes[1], planes[2], 1);
         if (rc != ZJ_RETRY_CPU) return fail(d, rc, std::string("GPU entropy stage: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
-        // handed back: the CPU walker decodes the file, the planes go up strip by strip below
         const uint8_t* src = d->src;
         const size_t src_len = d->src_len;
         const int rc2 = decode_all(d, src, src_len, false, false);
         if (rc2) return rc2;
     }
-    const int rc = zjint_crop_frame(ctx, &fd, d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr,
-                                    d->ncomp == 3 ? d->comps[2].coef : nullptr, 0, x, y, w, h, d_out, out_pitch);
-    return rc ? fail(d, rc, std::string("crop: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+    if (zeros && !reduced) { // (zjint_scaled_frame writes the zeros of a reduced window itself)
+        const int rc = zjint_crop_zeros(ctx, &fd, x, y, w, h, d_out, out_pitch);
+        return rc ? fail(d, rc, "crop zeros") : ZJ_OK;
+    }
+    return window(d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr, d->ncomp == 3 ? d->comps[2].coef : nullptr, 0);
+}
+
+int zj_decoder_finish_pixels_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                         uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!zjint_crop_frame || !zjint_scan_to_planes || !zjint_crop_zeros) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    return finish_window(d, ctx, false, 0, x, y, w, h, d_out, out_cap, out_pitch, out_len);
+}
+
+// The decoder's last prepared file at 1 / 2^scale_log2, cut to the window x, y, w, h of the REDUCED frame (all four 0: the
+// whole reduced frame): zj_decode_crops_scaled_device's contract.  With the CPU walker only the MCU rows the window's blocks
+// lie in are uploaded; with device entropy the planes in HBM are used.
+int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale_log2, unsigned x, unsigned y, unsigned w,
+                                           unsigned h, uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!zjint_scaled_frame || !zjint_scan_to_planes) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    return finish_window(d, ctx, true, scale_log2, x, y, w, h, d_out, out_cap, out_pitch, out_len);
+}
+
+// The window x, y, w, h (full-resolution pixels) resized to out_w x out_h: the crop -- at scale k > 0 the reduced window
+// that covers it, from the reduced-size decode -- into the context's buffer, then the resize
+static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
+                          unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
+                          void* d_out, size_t out_cap, size_t* out_len)
+{
+    using namespace zj;
+    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
+    if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int ch = resize_channels(&fd);
+    if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
+    if (k && zero_output(&fd)) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
+    const size_t need = resized_len(ch, out_w, out_h, dtype);
+    if (out_len) *out_len = need;
+    if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
+    const unsigned full[4] = {x, y, w, h};
+    unsigned win[4] = {x, y, w, h};
+    if (k) prescale_window(full, k, fd.width, fd.height, win);
+    const WindowLayout g = window_layout(&fd, win[2], win[3], 0); // (the crop's own check of the window follows)
+    uint8_t* crop = nullptr;
+    int rc = zjint_resize_scratch(ctx, g.len, &crop);
+    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    size_t got = 0;
+    rc = k ? zj_decoder_finish_pixels_scaled_device(d, ctx, k, win[0], win[1], win[2], win[3], crop, g.len, 0, &got)
+           : zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, g.len, 0, &got);
+    if (rc) return rc;
+    rc = zjint_resize_one(ctx, crop, win[2], win[3], ch, g.nplanes == 3 ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype,
+                          out_layout, scale, bias, flip, filter, d_out);
+    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 
 int zj_decoder_finish_pixels_resized_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
@@ -2846,77 +2903,7 @@ int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder* d, zj_ctx*
                                                           void* d_out, size_t out_cap, size_t* out_len)
 {
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
-    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
-    if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
-    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
-    zj_frame_desc fd;
-    fill_info(d, nullptr, &fd);
-    const int ch = (fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : (fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0);
-    if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
-    // zj_resized_out_len's arithmetic (this file links without the device half of the library in its CPU-only builds)
-    const int esz = dtype == ZJ_DTYPE_F32 ? 4 : (dtype == ZJ_DTYPE_F16 || dtype == ZJ_DTYPE_BF16) ? 2 : (dtype == ZJ_DTYPE_U8 ? 1 : 0);
-    const bool size_ok = out_w >= 1 && out_h >= 1 && out_w <= 8192 && out_h <= 8192;
-    const size_t need = esz && size_ok ? (size_t)ch * out_w * out_h * esz : 0;
-    if (out_len) *out_len = need;
-    if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
-    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
-    // the crop in the context's buffer (zj_decoder_finish_pixels_crop_device checks the window), then the resize
-    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
-    const size_t crop_len = (size_t)w * h * ch;
-    if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
-    uint8_t* crop = nullptr;
-    int rc = zjint_resize_scratch(ctx, crop_len, &crop);
-    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
-    size_t got = 0;
-    if ((rc = zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, crop_len, 0, &got))) return rc;
-    rc = zjint_resize_one(ctx, crop, w, h, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype, out_layout, scale, bias,
-                          flip, filter, d_out);
-    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
-}
-
-// The decoder's last prepared file at 1 / 2^scale_log2, cut to the window x, y, w, h of the REDUCED frame (all four 0: the
-// whole reduced frame): zj_decode_crops_scaled_device's contract.  With the CPU walker only the MCU rows the window's blocks
-// lie in are uploaded; with device entropy the planes in HBM are used.
-int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale_log2, unsigned x, unsigned y, unsigned w,
-                                           unsigned h, uint8_t* d_out, size_t out_cap, unsigned out_pitch, size_t* out_len)
-{
-    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
-    if (!zjint_scaled_frame || !zjint_scan_to_planes) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
-    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
-    if (scale_log2 < 1 || scale_log2 > 3) return fail(d, ZJ_ERR_ARG, "scale_log2 is 1, 2 or 3");
-    zj_frame_desc fd;
-    fill_info(d, nullptr, &fd);
-    const int ncomp = fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : ((fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : 0);
-    if (!ncomp) return fail(d, ZJ_ERR_UNSUPPORTED, "reduced outputs have 1 or 3 channels");
-    const bool zeros = fd.in_components == 1 && fd.out_colorspace != ZJ_CS_GRAYSCALE;
-    // zj_scaled_crop_out_len's arithmetic (zjint_scaled_frame checks the window in full)
-    const unsigned s = 1u << scale_log2, rw = (fd.width + s - 1) >> scale_log2, rh = (fd.height + s - 1) >> scale_log2;
-    if (x == 0 && y == 0 && w == 0 && h == 0) { w = rw; h = rh; }
-    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
-    const size_t row = (size_t)w * (chw ? 1 : ncomp), pitch = out_pitch ? (size_t)out_pitch : row;
-    const size_t need = pitch * h * (chw ? 3 : 1);
-    if (out_len) *out_len = need;
-    if (w == 0 || h == 0 || pitch < row || (size_t)x + w > rw || (size_t)y + h > rh) return fail(d, ZJ_ERR_ARG, "not a valid window of the reduced frame");
-    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
-    if (d->scan_ready) {
-        const int16_t* planes[3] = {nullptr, nullptr, nullptr};
-        unsigned status = 0;
-        int rc = zeros ? (int)ZJ_RETRY_CPU : zjint_scan_to_planes(ctx, &fd, d->blob_store.p, d->blob_len, planes, &status);
-        if (!zeros) d->gpu_status = status;
-        if (rc == ZJ_OK) {
-            const int rc2 = zjint_scaled_frame(ctx, &fd, planes[0], planes[1], planes[2], 1, scale_log2, x, y, w, h, d_out, out_pitch);
-            return rc2 ? fail(d, rc2, std::string("reduced decode: ") + zj_strerror(rc2) + " " + zj_last_error(ctx)) : ZJ_OK;
-        }
-        if (rc != ZJ_RETRY_CPU) return fail(d, rc, std::string("GPU entropy stage: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
-        // handed back (or an all-zero output, whose scan is decoded all the same): the CPU walker decodes the file
-        const uint8_t* src = d->src;
-        const size_t src_len = d->src_len;
-        const int rc2 = decode_all(d, src, src_len, false, false);
-        if (rc2) return rc2;
-    }
-    const int rc = zjint_scaled_frame(ctx, &fd, d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr,
-                                      d->ncomp == 3 ? d->comps[2].coef : nullptr, 0, scale_log2, x, y, w, h, d_out, out_pitch);
-    return rc ? fail(d, rc, std::string("reduced decode: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+    return finish_resized(d, ctx, 0, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len);
 }
 
 // zj_decoder_finish_pixels_resized_crop_filtered_device with a reduced-size decode under the resize
@@ -2928,42 +2915,8 @@ int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder* d, zj_ctx
 {
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
     if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
-    int k = 0; // zj_plan.h: prescale_pick
-    for (int c = 1; c <= max_prescale_log2; c++)
-        if ((w >> c) >= out_w && (h >> c) >= out_h) k = c;
-    if (k == 0 || out_w == 0 || out_h == 0)
-        return zj_decoder_finish_pixels_resized_crop_filtered_device(d, ctx, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias,
-                                                                     flip, filter, d_out, out_cap, out_len);
-    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
-    if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED;
-    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
-    zj_frame_desc fd;
-    fill_info(d, nullptr, &fd);
-    const int ch = (fd.out_colorspace == ZJ_CS_RGB || fd.out_colorspace == ZJ_CS_YCBCR) ? 3 : (fd.out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0);
-    if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
-    if (fd.in_components == 1 && ch == 3) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
-    const int esz = dtype == ZJ_DTYPE_F32 ? 4 : (dtype == ZJ_DTYPE_F16 || dtype == ZJ_DTYPE_BF16) ? 2 : (dtype == ZJ_DTYPE_U8 ? 1 : 0);
-    const size_t need = esz && out_w <= 8192 && out_h <= 8192 ? (size_t)ch * out_w * out_h * esz : 0;
-    if (out_len) *out_len = need;
-    if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
-    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
-    if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
-    // the reduced window (zj_plan.h: prescale_window)
-    const unsigned s = 1u << k, rw = (fd.width + s - 1) >> k, rh = (fd.height + s - 1) >> k;
-    unsigned x1 = (x + w + s - 1) >> k, y1 = (y + h + s - 1) >> k;
-    if (x1 > rw) x1 = rw;
-    if (y1 > rh) y1 = rh;
-    const unsigned cx = x >> k, cy = y >> k, cw = x1 - cx, chh = y1 - cy;
-    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
-    const size_t crop_len = (size_t)cw * chh * ch;
-    uint8_t* crop = nullptr;
-    int rc = zjint_resize_scratch(ctx, crop_len, &crop);
-    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
-    size_t got = 0;
-    if ((rc = zj_decoder_finish_pixels_scaled_device(d, ctx, k, cx, cy, cw, chh, crop, crop_len, 0, &got))) return rc;
-    rc = zjint_resize_one(ctx, crop, cw, chh, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype, out_layout, scale, bias,
-                          flip, filter, d_out);
-    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+    const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
+    return finish_resized(d, ctx, k, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len);
 }
 
 unsigned zj_decoder_gpu_status(const zj_decoder* d) { return d ? d->gpu_status : 0; }

@@ -1,5 +1,6 @@
 // zj_plan.h -- host-side geometry/launch planning shared by the product library (zj_api.cpp) and the
-// CPU emulation harness used by the CPU test-suite (tests/emu).  No device code here.
+// CPU emulation harness used by the CPU test-suite (tests/emu).  No device code here.  The pure size and window rules are
+// zj_geom.h's.
 //
 // Geometry follows src/headers.rs:306-339 (mcu_x, mcu_y, width_stride) and the strip loop of
 // src/mcu_prog.rs:132-246 / src/mcu.rs:139-230 (paths relative to the reference tree).
@@ -10,6 +11,7 @@
 
 #include "../../include/zjhip.h"
 #include "zj_device.h"
+#include "zj_geom.h"
 #include "zj_scaled.h"
 
 namespace zj {
@@ -34,16 +36,6 @@ struct Plan {
     int regular_px;      // !fast: pixels of a row made of ordinary 16-pixel groups; 0: the generic kernels (see make_plan)
     int rows_covered;    // n_strips * strip_rows; rows below stay 0 in the reference (Q6)
 };
-
-inline int ncomp_of(int cs)
-{
-    switch (cs) {
-    case ZJ_CS_RGB: case ZJ_CS_YCBCR: return 3;
-    case ZJ_CS_GRAYSCALE: return 1;
-    case ZJ_CS_CMYK: case ZJ_CS_YCCK: case ZJ_CS_RGBA: case ZJ_CS_RGBX: return 4;
-    default: return 0;
-    }
-}
 
 template <int HS, int VS>
 inline void plan_geo(Plan& pl, bool chroma)
@@ -98,7 +90,7 @@ inline int make_plan(const zj_frame_desc* d, Plan& pl)
     // whole cache lines: DESIGN.md 4.0 "row pitch"); the reference's own layout is the tight one
     pl.row_bytes = pl.out == OUT_RGB_CHW ? (size_t)d->width : (size_t)d->width * nout;
     pl.out_pitch = d->out_pitch ? (size_t)d->out_pitch : pl.row_bytes;
-    if (pl.out_pitch < pl.row_bytes || pl.out_pitch > (1u << 20)) return ZJ_ERR_ARG;
+    if (pl.out_pitch < pl.row_bytes || pl.out_pitch > OUT_PITCH_MAX) return ZJ_ERR_ARG;
     pl.out_len = pl.out_pitch * d->height * (pl.out == OUT_RGB_CHW ? 3 : 1);
     const bool chroma = pl.out != OUT_GRAY;
     if (pl.hs == 1 && pl.vs == 1) plan_geo<1, 1>(pl, chroma);
@@ -193,18 +185,23 @@ inline void fill_params(const zj_frame_desc* d, const Plan& pl, size_t nframes, 
 // (RAG).  The wide generation (variant 1) has no RAG form: its ragged frames take the generic kernels.
 inline int launch_mode(const Plan& pl, int variant) { return pl.fast ? 1 : ((pl.regular_px > 0 && variant != 1) ? 2 : 0); }
 
-// frames [f0, f0 + n) of a scattered batch: their addresses into the launch's table (n <= SCATTER_MAX)
+// frames [f0, f0 + n) of a scattered batch: their addresses into a launch's table, y | cb | cr | out (n <= SCATTER_MAX)
+inline void set_frame_ptrs(uint64_t (&fptr)[SCATTER_MAX][4], const int16_t* const* y, const int16_t* const* cb,
+                           const int16_t* const* cr, uint8_t* const* out, size_t f0, int n)
+{
+    for (int f = 0; f < SCATTER_MAX; f++) {
+        const bool in = f < n;
+        fptr[f][0] = in ? (uint64_t)(uintptr_t)y[f0 + f] : 0;
+        fptr[f][1] = in && cb ? (uint64_t)(uintptr_t)cb[f0 + f] : 0;
+        fptr[f][2] = in && cr ? (uint64_t)(uintptr_t)cr[f0 + f] : 0;
+        fptr[f][3] = in ? (uint64_t)(uintptr_t)out[f0 + f] : 0;
+    }
+}
 inline void set_scatter(Params& p, const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr,
                         uint8_t* const* out, size_t f0, int n)
 {
     p.y = nullptr; p.cb = nullptr; p.cr = nullptr; p.out = nullptr; // y == nullptr marks the launch as scattered (decode_tile)
-    for (int f = 0; f < SCATTER_MAX; f++) {
-        const bool in = f < n;
-        p.fptr[f][0] = in ? (uint64_t)(uintptr_t)y[f0 + f] : 0;
-        p.fptr[f][1] = in && cb ? (uint64_t)(uintptr_t)cb[f0 + f] : 0;
-        p.fptr[f][2] = in && cr ? (uint64_t)(uintptr_t)cr[f0 + f] : 0;
-        p.fptr[f][3] = in ? (uint64_t)(uintptr_t)out[f0 + f] : 0;
-    }
+    set_frame_ptrs(p.fptr, y, cb, cr, out, f0, n);
 }
 
 // ---- crop windows (zj_decode_crops_device; zj_device.h: CropParams) -------------------------------------------------
@@ -237,20 +234,17 @@ inline int make_crop_plan(const zj_frame_desc* d, unsigned w, unsigned h, unsign
 {
     int rc = make_plan(d, pl);
     if (rc) return rc;
-    if (d->out_pitch != 0 || w == 0 || h == 0 || w > d->width || h > d->height) return ZJ_ERR_ARG;
+    const WindowLayout g = window_layout(d, w, h, out_pitch);
+    if (d->out_pitch != 0 || !window_inside(g, 0, 0, w, h, d->width, d->height) || !window_pitch_ok(g)) return ZJ_ERR_ARG;
     cp.w = (int)w; cp.h = (int)h;
-    cp.nplanes = pl.out == OUT_RGB_CHW ? 3 : 1;
-    cp.bpp = pl.out == OUT_RGB_CHW ? 1 : pl.ncomp_out;
+    cp.nplanes = g.nplanes; cp.bpp = g.bpp;
+    cp.out_pitch = g.pitch; cp.out_len = g.len;
     if (pl.hs == 1 && pl.vs == 1) crop_geo<1, 1>(cp, pl.out != OUT_GRAY);
     else if (pl.hs == 2 && pl.vs == 1) crop_geo<2, 1>(cp, pl.out != OUT_GRAY);
     else if (pl.hs == 1 && pl.vs == 2) crop_geo<1, 2>(cp, pl.out != OUT_GRAY);
     else crop_geo<2, 2>(cp, pl.out != OUT_GRAY);
     cp.row_bytes = (int)pl.row_bytes;
     cp.tile_bytes = cp.bpp * cp.twy;
-    const size_t tight = (size_t)w * cp.bpp;
-    cp.out_pitch = out_pitch ? (size_t)out_pitch : tight;
-    if (cp.out_pitch < tight || cp.out_pitch > (1u << 20)) return ZJ_ERR_ARG;
-    cp.out_len = cp.out_pitch * h * cp.nplanes;
     // Who writes the end of a row (store_unit_generic, the rules of the crop kernel's stores): the last two 8-pixel units
     // of an RGB row under the early-tail quirk (Q5) are written at p' and p' + 24, up to 88 bytes left of their own tile,
     // and the zeros after them (Q6) by the last unit's tile.  Every other byte belongs to the tile its pixel lies in.
@@ -278,27 +272,21 @@ inline int make_crop_plan(const zj_frame_desc* d, unsigned w, unsigned h, unsign
     return ZJ_OK;
 }
 
-// The window of an ALL-ZERO output: a single-component frame asked for a colour output, which the reference converts
-// nothing of and returns as zeros (worker.rs:131; the decoder's finish path).  No tile is decoded: the crop is zeros, laid
-// out by zj_out_len's arithmetic -- rows of w x ncomp_of(out_colorspace) bytes, CHW RGB: w bytes in each of 3 planes.
-inline bool zero_output(const zj_frame_desc* d) { return d && d->in_components == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE; }
+// The window of an ALL-ZERO output (zj_geom.h: zero_output).  No tile is decoded: the crop is zeros, laid out as every
+// window is (window_layout).
 inline int make_zero_crop(const zj_frame_desc* d, unsigned w, unsigned h, unsigned out_pitch, CropPlan& cp)
 {
     const int nc = d ? ncomp_of(d->out_colorspace) : 0;
     if (!nc || d->width == 0 || d->height == 0 || d->width > 65535 || d->height > 65535) return ZJ_ERR_ARG;
-    if (d->out_pitch != 0 || w == 0 || h == 0 || w > d->width || h > d->height) return ZJ_ERR_ARG;
-    const bool chw = d->out_layout == ZJ_LAYOUT_CHW && d->out_colorspace == ZJ_CS_RGB;
+    const WindowLayout g = window_layout(d, w, h, out_pitch);
+    if (d->out_pitch != 0 || !window_inside(g, 0, 0, w, h, d->width, d->height) || !window_pitch_ok(g)) return ZJ_ERR_ARG;
     cp = CropPlan{};
     cp.w = (int)w; cp.h = (int)h;
-    cp.bpp = chw ? 1 : nc;
-    cp.nplanes = chw ? 3 : 1;
+    cp.bpp = g.bpp; cp.nplanes = g.nplanes;
+    cp.out_pitch = g.pitch; cp.out_len = g.len;
     cp.row_bytes = (int)d->width * cp.bpp;
     cp.cut_tile[0] = cp.cut_tile[1] = -1;
     cp.hole_tile = -1; cp.hole_lo = cp.hole_hi = cp.row_bytes;
-    const size_t tight = (size_t)w * cp.bpp;
-    cp.out_pitch = out_pitch ? (size_t)out_pitch : tight;
-    if (cp.out_pitch < tight || cp.out_pitch > (1u << 20)) return ZJ_ERR_ARG;
-    cp.out_len = cp.out_pitch * h * cp.nplanes;
     return ZJ_OK;
 }
 
@@ -411,8 +399,7 @@ inline int make_scaled_plan(const zj_frame_desc* d, int scale_log2, Plan& pl, Sc
         sp.nplanes = pl.out == OUT_RGB_CHW ? 3 : 1;
         sp.bpp = pl.out == OUT_RGB_CHW ? 1 : pl.ncomp_out;
     }
-    const unsigned s = 1u << scale_log2;
-    sp.rw = (int)((d->width + s - 1) / s); sp.rh = (int)((d->height + s - 1) / s);
+    sp.rw = (int)reduced_dim(d->width, scale_log2); sp.rh = (int)reduced_dim(d->height, scale_log2);
     const int ln = 8 >> scale_log2, ypm = pl.hs * pl.vs;
     sp.mw = ln * pl.hs; sp.mh = ln * pl.vs;
     sp.tm = pl.out != OUT_GRAY ? (ypm == 4 ? 32 : 64) : 256 / ypm;
@@ -422,10 +409,8 @@ inline int make_scaled_plan(const zj_frame_desc* d, int scale_log2, Plan& pl, Sc
 // a window of the reduced frame whose rows lie out_pitch bytes apart (0: tight): its bytes, 0 = not a valid window
 inline size_t scaled_window_len(const ScaledPlan& sp, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_pitch)
 {
-    if (w == 0 || h == 0 || (size_t)x + w > (size_t)sp.rw || (size_t)y + h > (size_t)sp.rh) return 0;
-    const size_t tight = (size_t)w * sp.bpp, pitch = out_pitch ? (size_t)out_pitch : tight;
-    if (pitch < tight || pitch > (1u << 20)) return 0;
-    return pitch * h * sp.nplanes;
+    const WindowLayout g = window_layout(sp.bpp, sp.nplanes, w, h, out_pitch);
+    return window_inside(g, x, y, w, h, (unsigned)sp.rw, (unsigned)sp.rh) && window_pitch_ok(g) ? g.len : 0;
 }
 
 // the launch's arguments for frames [f0, f0 + n): win = x, y, w, h per frame in reduced pixels (checked by the caller),
@@ -438,14 +423,10 @@ inline void fill_scaled_params(const zj_frame_desc* d, const Plan& pl, const Sca
     p.out_pitch = (int)out_pitch; p.clamp_dc = pl.clamp_dc; p.nframes = n;
     for (int c = 0; c < 3; c++) build_table(d->qt[c], p.tab + TAB_DW * c);
     p.ncols = p.nrows = 0;
+    set_frame_ptrs(p.fptr, y, cb, cr, out, f0, n);
     for (int f = 0; f < SCATTER_MAX; f++) {
-        const bool in = f < n;
-        p.fptr[f][0] = in ? (uint64_t)(uintptr_t)y[f0 + f] : 0;
-        p.fptr[f][1] = in && cb ? (uint64_t)(uintptr_t)cb[f0 + f] : 0;
-        p.fptr[f][2] = in && cr ? (uint64_t)(uintptr_t)cr[f0 + f] : 0;
-        p.fptr[f][3] = in ? (uint64_t)(uintptr_t)out[f0 + f] : 0;
         p.origin[f] = p.size[f] = p.first[f] = 0;
-        if (!in) continue;
+        if (f >= n) continue;
         const unsigned* const wf = win ? win + 4 * (f0 + f) : nullptr;
         const int x = wf ? (int)wf[0] : 0, yy = wf ? (int)wf[1] : 0, w = wf ? (int)wf[2] : sp.rw, h = wf ? (int)wf[3] : sp.rh;
         const int m0 = x / sp.mw, m1 = (x + w + sp.mw - 1) / sp.mw, r0 = yy / sp.mh, r1 = (yy + h + sp.mh - 1) / sp.mh;
@@ -456,28 +437,6 @@ inline void fill_scaled_params(const zj_frame_desc* d, const Plan& pl, const Sca
         if (nc > p.ncols) p.ncols = nc;
         if (r1 - r0 > p.nrows) p.nrows = r1 - r0;
     }
-}
-
-// ---- prescaled resized crops (zj_decode_crops_resized_prescaled_device) ----------------------------------------------
-// the scale of one image: the largest k <= max_log2 with floor(w / 2^k) >= out_w and floor(h / 2^k) >= out_h (0: none) --
-// the resize that follows never enlarges
-inline int prescale_pick(unsigned w, unsigned h, unsigned out_w, unsigned out_h, int max_log2)
-{
-    int k = 0;
-    for (int c = 1; c <= max_log2; c++)
-        if ((w >> c) >= out_w && (h >> c) >= out_h) k = c;
-    return k;
-}
-// the window of the reduced frame that covers the full-resolution window x, y, w, h:
-// [floor(x / s), ceil((x + w) / s)) x [floor(y / s), ceil((y + h) / s)), clipped to the reduced frame
-inline void prescale_window(const unsigned full[4], int k, unsigned width, unsigned height, unsigned red[4])
-{
-    const unsigned s = 1u << k, rw = (width + s - 1) >> k, rh = (height + s - 1) >> k;
-    unsigned x1 = (full[0] + full[2] + s - 1) >> k, y1 = (full[1] + full[3] + s - 1) >> k;
-    if (x1 > rw) x1 = rw;
-    if (y1 > rh) y1 = rh;
-    red[0] = full[0] >> k; red[1] = full[1] >> k;
-    red[2] = x1 - red[0]; red[3] = y1 - red[1];
 }
 
 } // namespace zj

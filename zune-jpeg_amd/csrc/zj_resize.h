@@ -10,6 +10,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "zj_geom.h" // RESIZE_MAX_OUT, resize_elem_bytes: the output's size rules, shared with the front-end
+
 #if defined(ZJ_EMU)
 #ifndef ZJ_DEV
 #define ZJ_DEV inline
@@ -27,14 +29,11 @@
 
 namespace zj {
 
-constexpr int RESIZE_MAX_OUT = 8192;  // out_w, out_h
 constexpr int RESIZE_BATCH = 128;     // images per launch (their pointers, sizes and pitches are kernel arguments)
 constexpr int RESIZE_GROUP = 8;       // output pixels of one row per lane
 constexpr int RESIZE_ITEMS = 1024;    // (row, group) items per workgroup, about
 constexpr int RESIZE_NT = 256;        // threads per workgroup
-enum { RZ_F32 = 0, RZ_F16 = 1, RZ_BF16 = 2, RZ_U8 = 3 };
-
-ZJ_HD constexpr int resize_elem_bytes(const int dt) { return dt == RZ_F32 ? 4 : (dt == RZ_U8 ? 1 : 2); }
+enum { RZ_F32 = ZJ_DTYPE_F32, RZ_F16 = ZJ_DTYPE_F16, RZ_BF16 = ZJ_DTYPE_BF16, RZ_U8 = ZJ_DTYPE_U8 };
 
 // One axis, destination index i of m, source length n (1..65535, m 1..8192):
 //   u = floor((2i + 1) * n * 256 / (2m)) - 128, clamped to [0, (n - 1) * 256]; i0 = u >> 8, f = u & 255,
