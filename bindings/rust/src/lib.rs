@@ -245,6 +245,27 @@ extern "C" {
                                                                   bias: *const f32, flip: c_int, filter: c_int,
                                                                   max_prescale_log2: c_int, d_out: *mut c_void,
                                                                   out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn zj_oriented_size(orientation: c_int, w: c_uint, h: c_uint, ow: *mut c_uint, oh: *mut c_uint) -> c_int;
+    pub fn zj_orient_window(orientation: c_int, frame_w: c_uint, frame_h: c_uint, window: *const c_uint,
+                            stored: *mut c_uint) -> c_int;
+    pub fn zj_orient_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                            channels: c_int, in_layout: c_int, orientation: *const u8, d_out: *const *mut u8,
+                            out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_resized_oriented_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize,
+                                                   d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                                   windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                   out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                                   filter: c_int, max_prescale_log2: c_int, orientation: *const u8,
+                                                   d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_orientation(d: *const zj_decoder) -> c_int;
+    pub fn zj_decoder_finish_pixels_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, d_out: *mut u8, out_cap: usize,
+                                                    out_len: *mut usize, out_w: *mut c_uint, out_h: *mut c_uint) -> c_int;
+    pub fn zj_decoder_finish_pixels_resized_crop_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint,
+                                                                 w: c_uint, h: c_uint, out_w: c_uint, out_h: c_uint,
+                                                                 dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                                 bias: *const f32, flip: c_int, filter: c_int,
+                                                                 max_prescale_log2: c_int, d_out: *mut c_void,
+                                                                 out_cap: usize, out_len: *mut usize) -> c_int;
     pub fn zj_device_pci_bus_id(device: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zj_device_numa_node(device: c_int) -> c_int;
     pub fn zj_bind_thread_to_numa_node(node: c_int) -> c_int;

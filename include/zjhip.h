@@ -341,6 +341,43 @@ ZJ_API int zj_decode_crops_resized_prescaled_device(zj_ctx *ctx, const zj_frame_
                                                     unsigned out_h, int dtype, int out_layout, const float *scale,
                                                     const float *bias, const uint8_t *flip, int filter,
                                                     int max_prescale_log2, void *d_out, void *stream);
+/* EXIF orientation.  o = 1..8 is the Orientation tag; S the stored image, h rows of w pixels -- what the decode
+ * writes, quirks included -- and D the displayed one:
+ *   o  size of D   D[r][c]               o  size of D   D[r][c]
+ *   1  h x w       S[r][c]               5  w x h       S[c][r]
+ *   2  h x w       S[r][w-1-c]           6  w x h       S[h-1-c][r]
+ *   3  h x w       S[h-1-r][w-1-c]       7  w x h       S[h-1-c][w-1-r]
+ *   4  h x w       S[h-1-r][c]           8  w x h       S[c][w-1-r]
+ * (Pillow's FLIP_LEFT_RIGHT, ROTATE_180, FLIP_TOP_BOTTOM, TRANSPOSE, ROTATE_270, TRANSVERSE, ROTATE_90 for 2..8:
+ * ImageOps.exif_transpose.)  A pixel moves as a whole, its bytes keep their order;
+ * ZJ_LAYOUT_CHW: every plane is turned on its own.
+ * zj_oriented_size: the size of D.  zj_orient_window: the window x, y, w, h of D, given for a stored frame of frame_w x
+ * frame_h, as the window of S whose displayed form is exactly D[y : y + h, x : x + w].  ZJ_ERR_ARG: an orientation outside
+ * 1..8; zj_orient_window also: an empty window or one that leaves D. */
+ZJ_API int zj_oriented_size(int orientation, unsigned w, unsigned h, unsigned *ow, unsigned *oh);
+ZJ_API int zj_orient_window(int orientation, unsigned frame_w, unsigned frame_h, const unsigned window[4], unsigned stored[4]);
+/* n u8 images in device memory -> their displayed form: d_in, in_wh (STORED width and height, 1..65535), in_pitch, channels and
+ * in_layout as in zj_resize_device; orientation[i] = 1..8 (NULL: all 1, a plain copy); d_out[i] the first byte of image i's
+ * output, in the same layout, its rows out_pitch[i] bytes apart (NULL or 0: tight; the padding is never written; CHW: the
+ * planes lie out_pitch x displayed height apart).  An image's input and output must not overlap.  One launch per 128 images,
+ * whatever their sizes.  Asynchronous on `stream` (NULL: the context's); nothing is launched after an argument error. */
+ZJ_API int zj_orient_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                            int channels, int in_layout, const uint8_t *orientation, uint8_t *const *d_out,
+                            const unsigned *out_pitch, void *stream);
+/* zj_decode_crops_resized_prescaled_device for frames that are to be shown turned: orientation[f] = 1..8 per frame (NULL: all
+ * 1, and the call IS the prescaled one), windows in DISPLAYED pixels of each frame.  The output is zj_resize_filtered_device
+ * applied to EXACTLY the displayed form of the u8 crop zj_decode_crops_device writes for the stored window (zj_orient_window)
+ * -- the reference's quirks turn with the image; with prescaling, of the reduced crop of that stored window, the scale picked
+ * from the displayed window's sides.  Orientation comes first: `flip` still mirrors the output's columns after everything
+ * else.  Frames with orientation 1 skip the orient stage; the others pass through a second region of the context's buffer.
+ * An orientation outside 1..8 or a window that leaves the displayed frame is ZJ_ERR_ARG and nothing is launched. */
+ZJ_API int zj_decode_crops_resized_oriented_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes,
+                                                   const int16_t *const *d_y, const int16_t *const *d_cb,
+                                                   const int16_t *const *d_cr, const unsigned *windows, unsigned out_w,
+                                                   unsigned out_h, int dtype, int out_layout, const float *scale,
+                                                   const float *bias, const uint8_t *flip, int filter,
+                                                   int max_prescale_log2, const uint8_t *orientation, void *d_out,
+                                                   void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -478,6 +515,26 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder *d,
                                                                   const float *bias, int flip, int filter,
                                                                   int max_prescale_log2, void *d_out, size_t out_cap,
                                                                   size_t *out_len);
+/* EXIF Orientation of the file whose headers were read last (zj_decoder_read_headers / _prepare / _decode_coefficients /
+ * _decode_buffer): 1..8, 1 when the file says nothing usable; 0 before any file.  The first APP1 segment in front of SOS whose
+ * payload begins "Exif\0\0" decides: TIFF header (II or MM), IFD0, the entry with tag 0x0112, type SHORT, count 1.  Anything
+ * else (a bad header, an offset or entry past the segment or the buffer, another type or count, a value outside 1..8) is 1. */
+ZJ_API int zj_decoder_orientation(const zj_decoder *d);
+/* zj_decoder_finish_pixels_device with the file's orientation applied (what an EXIF-aware image loader returns): the whole
+ * DISPLAYED image, tight, in the decoder's colour space and layout; *out_w x *out_h (optional) its size.  Orientation 1
+ * decodes straight into d_out; the others decode into a buffer of the context and are turned from there.  RGBA / RGBX are
+ * ZJ_ERR_UNSUPPORTED.  *out_len = zj_out_len(); out_cap below it is ZJ_ERR_ARG. */
+ZJ_API int zj_decoder_finish_pixels_oriented_device(zj_decoder *d, zj_ctx *ctx, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                                                    unsigned *out_w, unsigned *out_h);
+/* zj_decoder_finish_pixels_resized_crop_prescaled_device with x, y, w, h in DISPLAYED pixels of the file's own orientation
+ * (zj_decode_crops_resized_oriented_device's contract for one image).  With the CPU walker still only the stored window's
+ * strips / MCU rows are uploaded. */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y,
+                                                                 unsigned w, unsigned h, unsigned out_w, unsigned out_h,
+                                                                 int dtype, int out_layout, const float *scale,
+                                                                 const float *bias, int flip, int filter,
+                                                                 int max_prescale_log2, void *d_out, size_t out_cap,
+                                                                 size_t *out_len);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

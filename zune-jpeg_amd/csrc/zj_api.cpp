@@ -14,6 +14,7 @@
 
 #include "../../include/zjhip.h"
 #include "zj_launch.h"
+#include "zj_orient_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
 #include "zj_scaled_launch.h"
@@ -877,6 +878,29 @@ int resize_scratch_done(zj_ctx* c, hipStream_t st)
 size_t crop_bytes(unsigned w, unsigned h, int channels) { return ((size_t)w * h * channels + 15) & ~(size_t)15; }
 
 bool known_filter(int filter) { return filter == ZJ_RESIZE_BILINEAR || filter == ZJ_RESIZE_BILINEAR_AA; }
+
+// images [0, n) -> their displayed form, launches of up to ORIENT_BATCH images; wh: STORED w, h pairs, the
+// pitches resolved, every o[i] 1..8
+int orient_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int channels,
+                    int in_chw, const uint8_t* o, uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
+{
+    OrientParams p{};
+    for (size_t f0 = 0; f0 < n; f0 += ORIENT_BATCH) {
+        const int m = (int)(n - f0 < (size_t)ORIENT_BATCH ? n - f0 : (size_t)ORIENT_BATCH);
+        p.nimg = m;
+        for (int i = 0; i < ORIENT_BATCH; i++) {
+            const size_t f = f0 + i;
+            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
+            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
+            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
+            p.in_pitch[i] = i < m ? in_pitch[f] : 0;
+            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
+            p.o[i] = i < m ? o[f] : 1;
+        }
+        ZJ_HIP(c, launch_orient(channels, in_chw, p, st));
+    }
+    return ZJ_OK;
+}
 } // namespace
 
 size_t zj_resized_out_len(const zj_frame_desc* d, unsigned out_w, unsigned out_h, int dtype)
@@ -973,14 +997,27 @@ int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, s
 
 // Every image at its own scale (zj_plan.h: prescale_pick): scale 1 through the crop kernel exactly as before, the others
 // through the reduced decode at the reduced window (prescale_window); then the resize over the group's crops, in order.
-int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
-                                             const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
-                                             unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
-                                             const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
-                                             void* d_out, void* stream)
+// orientation (nullptr: none, and nothing below differs from the call without it): the windows are in
+// DISPLAYED pixels; each is mapped to its stored window first (orient_window), which is decoded as ever; the crops of the
+// frames with o != 1 are then turned into a second region of the buffer, behind the group's crops, and the resize reads
+// those.  The scale is picked from the displayed window's sides, the ones the resize sees.
+static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                              const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                              unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                              const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                              const uint8_t* orientation, void* d_out, void* stream)
 {
     if (!known_filter(filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
     if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
+    const unsigned* const shown = windows; // the caller's windows: displayed pixels
+    std::vector<unsigned> stored_store;
+    if (orientation) {
+        if (!d->width || !d->height) return ZJ_ERR_ARG;
+        stored_store.resize(4 * nframes);
+        for (size_t f = 0; f < nframes; f++)
+            if (!orient_window(orientation[f], d->width, d->height, shown + 4 * f, stored_store.data() + 4 * f)) return ZJ_ERR_ARG;
+        windows = stored_store.data();
+    }
     const int ch = resize_channels(d);
     if (!ch) return ZJ_ERR_UNSUPPORTED;
     Plan pl;
@@ -1017,13 +1054,15 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
     if (max_prescale_log2 > 0)
         for (size_t f = 0; f < nframes; f++) {
             const unsigned* w = windows + 4 * f;
-            klog[f] = prescale_pick(w[2], w[3], out_w, out_h, max_prescale_log2);
+            klog[f] = prescale_pick(shown[4 * f + 2], shown[4 * f + 3], out_w, out_h, max_prescale_log2);
             if (klog[f]) prescale_window(w, klog[f], d->width, d->height, cwin_w + 4 * f);
         }
     // launch groups: frames whose crops fit RZ_GROUP_CAP together (a larger window alone); the buffer sized for the largest
+    // (a frame that is turned takes its crop's bytes twice: the crop and, in the second region, its displayed form)
+    const auto turned = [&](size_t f) { return orientation && orientation[f] != 1; };
     size_t need = 0;
     for (size_t f = 0, g = 0; f < nframes; f++) {
-        const size_t cb = crop_bytes(cwin[4 * f + 2], cwin[4 * f + 3], ch);
+        const size_t cb = crop_bytes(cwin[4 * f + 2], cwin[4 * f + 3], ch) * (turned(f) ? 2 : 1);
         g = g && g + cb > RZ_GROUP_CAP ? cb : g + cb;
         if (g > need) need = g;
     }
@@ -1035,14 +1074,15 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
     std::vector<uint8_t*> gout;
     std::vector<unsigned> gwin;
     for (size_t g0 = 0; g0 < nframes;) {
-        size_t g1 = g0, off = 0;
+        size_t g1 = g0, off = 0, off2 = 0; // off2: bytes of the second region, the displayed forms
         while (g1 < nframes) {
             const size_t cb = crop_bytes(cwin[4 * g1 + 2], cwin[4 * g1 + 3], ch);
-            if (g1 > g0 && off + cb > RZ_GROUP_CAP) break;
+            if (g1 > g0 && off + off2 + cb * (turned(g1) ? 2 : 1) > RZ_GROUP_CAP) break;
             crops[g1] = buf + off;
             pitch[g1] = cwin[4 * g1 + 2] * (chw ? 1 : ch);
             wh[2 * g1] = cwin[4 * g1 + 2]; wh[2 * g1 + 1] = cwin[4 * g1 + 3];
             off += cb;
+            if (turned(g1)) off2 += cb;
             g1++;
         }
         // the crops of the group, each tight at its own size (CropParams.out_pitch 0); the group before it has been read by
@@ -1070,6 +1110,31 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
                             : decode_crops_impl(c, d, pl, cp, ng, py, pcb, pcr, pwin, 4, pout, st)))
                 return rc;
         }
+        if (off2) {
+            // the turned frames of the group, gathered: crop -> its displayed form, tight, at off + its place in the second
+            // region; the resize then reads that image at its displayed size
+            std::vector<const uint8_t*> oin;
+            std::vector<uint8_t*> oout;
+            std::vector<unsigned> owh, oip, oop;
+            std::vector<uint8_t> oo;
+            size_t at = off;
+            for (size_t f = g0; f < g1; f++) {
+                if (!turned(f)) continue;
+                unsigned dw = 0, dh = 0;
+                orient_size(orientation[f], wh[2 * f], wh[2 * f + 1], &dw, &dh);
+                oin.push_back(crops[f]); oout.push_back(buf + at);
+                owh.push_back(wh[2 * f]); owh.push_back(wh[2 * f + 1]);
+                oip.push_back(pitch[f]); oop.push_back(dw * (chw ? 1 : ch));
+                oo.push_back(orientation[f]);
+                crops[f] = buf + at;
+                wh[2 * f] = dw; wh[2 * f + 1] = dh;
+                pitch[f] = dw * (chw ? 1 : ch);
+                at += crop_bytes(dw, dh, ch);
+            }
+            if ((rc = orient_launches(c, oin.size(), oin.data(), owh.data(), oip.data(), ch, chw, oo.data(), oout.data(),
+                                      oop.data(), st)))
+                return rc;
+        }
         if ((rc = resize_launches(c, g1 - g0, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h,
                                   dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
                                   (uint8_t*)d_out + g0 * img_bytes, st)))
@@ -1077,6 +1142,89 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
         if ((rc = resize_scratch_done(c, st))) return rc;
         g0 = g1;
     }
+    return ZJ_OK;
+}
+
+int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                             const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                             unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                             const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                             void* d_out, void* stream)
+{
+    return crops_resized_impl(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter,
+                              max_prescale_log2, nullptr, d_out, stream);
+}
+
+/* ---- EXIF orientation ----------------------------------------------------------- */
+int zj_decode_crops_resized_oriented_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                            const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                            unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                            const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                            const uint8_t* orientation, void* d_out, void* stream)
+{
+    if (!orientation)
+        return zj_decode_crops_resized_prescaled_device(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout,
+                                                        scale, bias, flip, filter, max_prescale_log2, d_out, stream);
+    return crops_resized_impl(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter,
+                              max_prescale_log2, orientation, d_out, stream);
+}
+
+int zj_oriented_size(int orientation, unsigned w, unsigned h, unsigned* ow, unsigned* oh)
+{
+    unsigned a, b;
+    if (!orient_size(orientation, w, h, &a, &b)) return ZJ_ERR_ARG;
+    if (ow) *ow = a;
+    if (oh) *oh = b;
+    return ZJ_OK;
+}
+
+int zj_orient_window(int orientation, unsigned frame_w, unsigned frame_h, const unsigned window[4], unsigned stored[4])
+{
+    if (!window || !stored) return ZJ_ERR_ARG;
+    unsigned s[4];
+    if (!orient_window(orientation, frame_w, frame_h, window, s)) return ZJ_ERR_ARG;
+    for (int k = 0; k < 4; k++) stored[k] = s[k];
+    return ZJ_OK;
+}
+
+int zj_orient_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch,
+                     int channels, int in_layout, const uint8_t* orientation, uint8_t* const* d_out, const unsigned* out_pitch,
+                     void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
+    if (channels != 1 && channels != 3) return ZJ_ERR_ARG;
+    if (in_layout != ZJ_LAYOUT_HWC && in_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    const bool chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
+    const unsigned bpp = chw ? 1 : (unsigned)channels;
+    std::vector<unsigned> ip(n), op(n);
+    std::vector<uint8_t> o(n, 1);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_in[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        if (orientation) o[f] = orientation[f];
+        unsigned dw, dh;
+        if (!orient_size(o[f], w, h, &dw, &dh)) return ZJ_ERR_ARG;
+        ip[f] = in_pitch && in_pitch[f] ? in_pitch[f] : w * bpp;
+        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : dw * bpp;
+        if (ip[f] < w * bpp || op[f] < dw * bpp || ip[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return orient_launches(c, n, d_in, in_wh, ip.data(), channels, chw, o.data(), d_out, op.data(), st);
+}
+
+// Library-internal (zj_jpeg.cpp: the decoder's oriented outputs): one image turned on the context stream, tight on both
+// sides; the context's crop buffer counts as read by it; synchronised
+int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, int o, uint8_t* d_out)
+{
+    if (!c || o < 1 || o > 8) return ZJ_ERR_ARG;
+    const unsigned wh[2] = {w, h};
+    const uint8_t oo = (uint8_t)o;
+    int rc = zj_orient_device(c, 1, &in, wh, nullptr, channels, in_layout, &oo, &d_out, nullptr, nullptr);
+    if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }
 
@@ -1158,6 +1306,15 @@ int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t** p)
     if (!c || !p) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     return resize_scratch(c, bytes, c->stream, p);
+}
+
+// ... the same buffer once nothing reads it any more: for a writer that is not ordered on the context stream
+int zjint_scratch_idle(zj_ctx* c, size_t bytes, uint8_t** p)
+{
+    const int rc = zjint_resize_scratch(c, bytes, p);
+    if (rc) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
 }
 
 int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, unsigned out_w,

@@ -95,6 +95,45 @@ inline void prescale_window(const unsigned full[4], int k, unsigned width, unsig
     red[2] = x1 - red[0]; red[3] = y1 - red[1];
 }
 
+// ---- EXIF orientation -------------------------------------------------------------------------------
+// o = 1..8 turns the stored image S (h rows of w pixels) into the displayed one D.  D[r][c] = S[sr][sc] with (a, b) =
+// (c, r) for the transposing orientations 5..8, else (r, c); sr = a or h - 1 - a, sc = b or w - 1 - b:
+//   o            1  2  3  4  5  6  7  8
+//   transposes   .  .  .  .  x  x  x  x
+//   rows turned  .  .  x  x  .  x  x  .      (sr = h - 1 - a)
+//   cols turned  .  x  x  .  .  .  x  x      (sc = w - 1 - b)
+// (constexpr: the kernel calls them too)
+constexpr bool orient_valid(const int o) { return o >= 1 && o <= 8; }
+constexpr bool orient_transposes(const int o) { return o >= 5; }
+constexpr bool orient_turns_rows(const int o) { return o == 3 || o == 4 || o == 6 || o == 7; }
+constexpr bool orient_turns_cols(const int o) { return o == 2 || o == 3 || o == 7 || o == 8; }
+
+// size of D for a stored w x h
+inline bool orient_size(int o, unsigned w, unsigned h, unsigned* ow, unsigned* oh)
+{
+    if (!orient_valid(o)) return false;
+    *ow = orient_transposes(o) ? h : w;
+    *oh = orient_transposes(o) ? w : h;
+    return true;
+}
+
+// the window x, y, w, h of D (a stored frame of fw x fh) as a window of S: orienting that stored window gives exactly
+// D[y : y + h, x : x + w].  false: not an orientation, or not a window of D
+inline bool orient_window(int o, unsigned fw, unsigned fh, const unsigned win[4], unsigned stored[4])
+{
+    unsigned dw, dh;
+    if (!orient_size(o, fw, fh, &dw, &dh)) return false;
+    const unsigned x = win[0], y = win[1], w = win[2], h = win[3];
+    if (w == 0 || h == 0 || (size_t)x + w > dw || (size_t)y + h > dh) return false;
+    // displayed columns run along the stored b axis (the stored rows, when transposing), displayed rows along a
+    const unsigned b0 = orient_transposes(o) ? y : x, nb = orient_transposes(o) ? h : w;
+    const unsigned a0 = orient_transposes(o) ? x : y, na = orient_transposes(o) ? w : h;
+    stored[0] = orient_turns_cols(o) ? fw - b0 - nb : b0;
+    stored[1] = orient_turns_rows(o) ? fh - a0 - na : a0;
+    stored[2] = nb; stored[3] = na;
+    return true;
+}
+
 // ---- resized outputs --------------------------------------------------------------------------------
 // bytes of an element of ZJ_DTYPE_* dt, 0: no such dtype (constexpr: the kernels call it with their template argument)
 constexpr int resize_elem_bytes(const int dt)

@@ -470,6 +470,8 @@ struct zj_decoder {
     int err_code = 0;
     int width = 0, height = 0, ncomp = 0, progressive = 0, h_max = 1, v_max = 1, mcu_x = 0, mcu_y = 0;
     int restart_interval = 0;
+    int orientation = 0;     // EXIF Orientation of the last file whose headers were read, 1..8 (1: none said); 0: no file yet
+    bool exif_seen = false;  // an APP1 segment with the Exif signature has been met: it decided, later ones are ignored
     int seen_sof = 0, scans = 0;
     bool coef_valid = false; // the planes hold the coefficients of a complete, successful decode_all
     long long hist_retries = 0; // images decoded a second time for it (tests)
@@ -676,6 +678,38 @@ int parse_sos(zj_decoder* d, Cursor& c)
     return ZJ_OK;
 }
 
+// EXIF Orientation of an APP1 payload of n bytes (what the segment declares, cut to what the buffer holds): -1 when it does
+// not begin "Exif\0\0", else 1..8.  The reference reads that signature and throws the payload away (src/headers.rs:504-523);
+// this only looks -- the marker loop consumes the segment as it always did.  A TIFF header (II*\0 or MM\0*, u32 offset of
+// IFD0 from the header), IFD0 = u16 count + 12-byte entries; the entry wanted has tag 0x0112, type 3 (SHORT), count 1, its
+// value the first two value bytes in the file's byte order.  Anything else -- a bad header, an offset or an entry past n,
+// another type or count, a value outside 1..8 -- is 1.  Sub-IFDs are not followed.  Every read is checked against n.
+int exif_orientation(const uint8_t* p, size_t n)
+{
+    if (n < 6 || memcmp(p, "Exif\0\0", 6) != 0) return -1;
+    const uint8_t* const t = p + 6;
+    const size_t tn = n - 6;
+    if (tn < 8) return 1;
+    bool le;
+    if (t[0] == 'I' && t[1] == 'I' && t[2] == 0x2A && t[3] == 0x00) le = true;
+    else if (t[0] == 'M' && t[1] == 'M' && t[2] == 0x00 && t[3] == 0x2A) le = false;
+    else return 1;
+    const auto u16 = [&](size_t at) { return le ? (unsigned)t[at] | ((unsigned)t[at + 1] << 8) : ((unsigned)t[at] << 8) | (unsigned)t[at + 1]; };
+    const auto u32 = [&](size_t at) { return le ? u16(at) | (u16(at + 2) << 16) : (u16(at) << 16) | u16(at + 2); };
+    const size_t ifd = u32(4);
+    if (ifd > tn || tn - ifd < 2) return 1;
+    const unsigned count = u16(ifd);
+    for (unsigned i = 0; i < count; i++) {
+        const size_t e = ifd + 2 + (size_t)12 * i;
+        if (e > tn || tn - e < 12) return 1;
+        if (u16(e) != 0x0112) continue;
+        if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;
+        const unsigned v = u16(e + 8);
+        return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+}
+
 // marker loop up to and including SOS (decoder.rs:239-301); returns ZJ_OK positioned at the scan data
 int parse_headers(zj_decoder* d, Cursor& c, bool first)
 {
@@ -710,6 +744,10 @@ int parse_headers(zj_decoder* d, Cursor& c, bool first)
                 if (!c.u16(l)) return fail(d, ZJ_ERR_FORMAT, "Exhausted data while reading a marker length");
                 if (l < 2) return fail(d, ZJ_ERR_FORMAT, known ? "Found a marker with invalid length:" + std::to_string(l) + "\n"
                                                                  : "Found a marker with invalid length : " + std::to_string(l));
+                if (m == 0xE1 && !d->exif_seen) { // the first Exif segment decides the orientation
+                    const int o = exif_orientation(c.p, (size_t)(c.end - c.p < l - 2 ? c.end - c.p : l - 2));
+                    if (o > 0) { d->orientation = o; d->exif_seen = true; }
+                }
                 if (c.end - c.p < l - 2) c.p = c.end; else c.p += l - 2;
             }
             if (rc) return rc;
@@ -2502,6 +2540,7 @@ int decode_all_once(zj_decoder* d, const uint8_t* buf, size_t len, bool headers_
 {
     d->err.clear(); d->err_code = 0; d->seen_sof = 0; d->scans = 0; d->restart_interval = 0;
     d->coef_valid = false; d->scan_ready = false; d->src = nullptr; d->src_len = 0;
+    d->orientation = 1; d->exif_seen = false;
     for (int i = 0; i < 4; i++) { d->qt_present[i] = false; d->dc[i].present = false; d->ac[i].present = false; }
     Cursor c{buf, buf + len};
     int rc = parse_headers(d, c, true);
@@ -2585,6 +2624,7 @@ zj_decoder* zj_decoder_new(const zj_options* opt)
 void zj_decoder_free(zj_decoder* d) { delete d; }
 const char* zj_decoder_error(const zj_decoder* d) { return d ? d->err.c_str() : ""; }
 int zj_decoder_parallel_segments(const zj_decoder* d) { return d ? d->dri_parallel_segments : 0; }
+int zj_decoder_orientation(const zj_decoder* d) { return d ? d->orientation : 0; }
 int64_t zj_decoder_parallel_mcus(const zj_decoder* d) { return d ? (int64_t)d->par_scan_mcus : 0; }
 int zj_decoder_set_num_threads(zj_decoder* d, int threads)
 {   // Decoder::set_num_threads (src/decoder.rs:591-603): "Cannot set zero threads to decode image"
@@ -2674,6 +2714,10 @@ __attribute__((weak)) int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t*
 __attribute__((weak)) int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout,
                                            unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                            const float* bias, int flip, int filter, void* d_out);
+// ... and one image turned to its displayed form
+__attribute__((weak)) int zjint_scratch_idle(zj_ctx* c, size_t bytes, uint8_t** p);
+__attribute__((weak)) int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, int o,
+                                           uint8_t* d_out);
 
 // ... and the reduced-size decode of one frame's window
 __attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
@@ -2855,9 +2899,11 @@ int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale
 
 // The window x, y, w, h (full-resolution pixels) resized to out_w x out_h: the crop -- at scale k > 0 the reduced window
 // that covers it, from the reduced-size decode -- into the context's buffer, then the resize
+// o: 1, or the orientation the window is given in: x, y, w, h are then DISPLAYED pixels, the stored window
+// they map to is decoded as ever, turned into the second half of the buffer, and the resize reads that
 static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
                           unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
-                          void* d_out, size_t out_cap, size_t* out_len)
+                          void* d_out, size_t out_cap, size_t* out_len, int o = 1)
 {
     using namespace zj;
     if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
@@ -2872,20 +2918,35 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     if (out_len) *out_len = need;
     if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
     if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    if (o != 1) {
+        if (!zjint_orient_one) return ZJ_ERR_UNSUPPORTED;
+        const unsigned shown[4] = {x, y, w, h};
+        unsigned st[4];
+        if (!orient_window(o, fd.width, fd.height, shown, st)) return fail(d, ZJ_ERR_ARG, "not a valid crop window of the displayed image");
+        x = st[0]; y = st[1]; w = st[2]; h = st[3];
+    }
     if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
     const unsigned full[4] = {x, y, w, h};
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
     const WindowLayout g = window_layout(&fd, win[2], win[3], 0); // (the crop's own check of the window follows)
+    const size_t half = (g.len + 15) & ~(size_t)15;
     uint8_t* crop = nullptr;
-    int rc = zjint_resize_scratch(ctx, g.len, &crop);
+    int rc = zjint_resize_scratch(ctx, o != 1 ? 2 * half : g.len, &crop);
     if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     size_t got = 0;
     rc = k ? zj_decoder_finish_pixels_scaled_device(d, ctx, k, win[0], win[1], win[2], win[3], crop, g.len, 0, &got)
            : zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, g.len, 0, &got);
     if (rc) return rc;
-    rc = zjint_resize_one(ctx, crop, win[2], win[3], ch, g.nplanes == 3 ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, out_w, out_h, dtype,
-                          out_layout, scale, bias, flip, filter, d_out);
+    const int layout = g.nplanes == 3 ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
+    if (o != 1) {
+        rc = zjint_orient_one(ctx, crop, win[2], win[3], ch, layout, o, crop + half);
+        if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+        crop += half;
+        const unsigned sw = win[2], sh = win[3];
+        orient_size(o, sw, sh, &win[2], &win[3]);
+    }
+    rc = zjint_resize_one(ctx, crop, win[2], win[3], ch, layout, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
     return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 
@@ -2917,6 +2978,52 @@ int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder* d, zj_ctx
     if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
     const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
     return finish_resized(d, ctx, k, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len);
+}
+
+// The prescaled call with the window in DISPLAYED pixels of the file's own orientation; a file with
+// orientation 1 takes the prescaled call as it is
+int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w,
+                                                          unsigned h, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                          const float* scale, const float* bias, int flip, int filter,
+                                                          int max_prescale_log2, void* d_out, size_t out_cap, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
+    // (the scale from the displayed window's sides: the ones the resize sees)
+    const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
+    return finish_resized(d, ctx, k, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len,
+                          d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
+}
+
+// The whole displayed image of the prepared file, tight, in the decoder's colour space and layout: orientation 1 decodes
+// straight into d_out; any other decodes into the context's crop buffer and is turned from there
+int zj_decoder_finish_pixels_oriented_device(zj_decoder* d, zj_ctx* ctx, uint8_t* d_out, size_t out_cap, size_t* out_len,
+                                             unsigned* out_w, unsigned* out_h)
+{
+    using namespace zj;
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int ch = resize_channels(&fd);
+    if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "oriented outputs have 1 or 3 channels");
+    const int o = d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
+    unsigned dw = 0, dh = 0;
+    orient_size(o, fd.width, fd.height, &dw, &dh);
+    if (out_w) *out_w = dw;
+    if (out_h) *out_h = dh;
+    if (o == 1) return finish_impl(d, ctx, d_out, out_cap, out_len, 1);
+    if (!zjint_scratch_idle || !zjint_orient_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    const size_t need = zj_out_len(&fd);
+    if (out_len) *out_len = need;
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    uint8_t* stored = nullptr;
+    int rc = zjint_scratch_idle(ctx, need, &stored); // (idle: the decode below runs on streams of its own)
+    if (rc) return fail(d, rc, std::string("orient buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    if ((rc = finish_impl(d, ctx, stored, need, nullptr, 1))) return rc;
+    const bool chw = fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
+    rc = zjint_orient_one(ctx, stored, fd.width, fd.height, ch, chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC, o, d_out);
+    return rc ? fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 
 unsigned zj_decoder_gpu_status(const zj_decoder* d) { return d ? d->gpu_status : 0; }

@@ -169,6 +169,9 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decoder_finish_pixels_resized_crop_filtered_device",
     "zj_scaled_size", "zj_scaled_crop_out_len", "zj_decode_crops_scaled_device", "zj_decode_crops_resized_prescaled_device",
     "zj_decoder_finish_pixels_scaled_device", "zj_decoder_finish_pixels_resized_crop_prescaled_device",
+    "zj_oriented_size", "zj_orient_window", "zj_orient_device", "zj_decode_crops_resized_oriented_device",
+    "zj_decoder_orientation", "zj_decoder_finish_pixels_oriented_device",
+    "zj_decoder_finish_pixels_resized_crop_oriented_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -327,6 +330,17 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_prescaled_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                                                          C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int,
                                                                          C.c_int, C.c_int, vp, sz, C.POINTER(sz)]
+    L.zj_oriented_size.argtypes = [C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    L.zj_orient_window.argtypes = [C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    L.zj_orient_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.zj_decode_crops_resized_oriented_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
+                                                          C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.zj_decoder_orientation.argtypes = [vp]
+    L.zj_decoder_finish_pixels_oriented_device.argtypes = [vp, vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint),
+                                                           C.POINTER(C.c_uint)]
+    L.zj_decoder_finish_pixels_resized_crop_oriented_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                                                        C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int,
+                                                                        C.c_int, C.c_int, vp, sz, C.POINTER(sz)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -388,6 +402,22 @@ def scaled_size(desc, scale):
 def scaled_crop_out_len(desc, scale, w, h, out_pitch=0):
     """bytes of a w x h window of the frame decoded at 1/scale (zj_scaled_crop_out_len); 0: not a valid size"""
     return lib().zj_scaled_crop_out_len(C.byref(desc), scale_log2(scale), w, h, out_pitch)
+
+
+def oriented_size(orientation, w, h):
+    """(w, h) of the displayed form of a stored w x h image under EXIF orientation 1..8 (zj_oriented_size)"""
+    ow, oh = C.c_uint(0), C.c_uint(0)
+    _check(lib().zj_oriented_size(int(orientation), w, h, C.byref(ow), C.byref(oh)), "zj_oriented_size")
+    return ow.value, oh.value
+
+
+def orient_window(orientation, frame_w, frame_h, window):
+    """The window (x, y, w, h) of the DISPLAYED image of a stored frame_w x frame_h frame as a window of the stored one
+    (zj_orient_window)"""
+    win = (C.c_uint * 4)(*[int(v) for v in window])
+    st = (C.c_uint * 4)()
+    _check(lib().zj_orient_window(int(orientation), frame_w, frame_h, win, st), "zj_orient_window")
+    return tuple(st)
 
 
 def _floats(v):
@@ -577,13 +607,29 @@ class Context:
         else:
             _check(lib().zj_resize_device(*args, d_out, stream), "zj_resize_device", self._h)
 
+    def orient_device(self, d_in, sizes, channels, in_layout, orientations, d_out, in_pitches=None, out_pitches=None,
+                      stream=None):
+        """EXIF orientation (zj_orient_device): d_in = device pointers of u8 images, sizes = one STORED (w, h) each,
+        orientations = one of 1..8 each (None: all 1, a copy), d_out = one device pointer each for the displayed image
+        (oriented_size); pitches = bytes between rows (None: tight).  Input and output must not overlap.  Asynchronous
+        on `stream`."""
+        n = len(d_in)
+        if len(sizes) != n or len(d_out) != n or (orientations is not None and len(orientations) != n):
+            raise ValueError("one size, orientation and output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+        ori = (C.c_uint8 * n)(*[int(o) for o in orientations]) if orientations is not None else None
+        _check(lib().zj_orient_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), channels, in_layout, ori,
+                                      (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_orient_device", self._h)
+
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
-                                    bias=None, flips=None, stream=None, antialias=False, max_prescale=1):
+                                    bias=None, flips=None, stream=None, antialias=False, max_prescale=1, orientations=None):
         """Resized crop windows (zj_decode_crops_resized_device): pointers as in decode_crops_device, windows = one
         (x, y, w, h) per frame; the dense output at d_out.  antialias: the triangle filter
         (zj_decode_crops_resized_filtered_device, RESIZE_BILINEAR_AA).  max_prescale = 2, 4, 8: a reduced-size decode of
         up to that scale under the resize wherever it does not enlarge (zj_decode_crops_resized_prescaled_device); 1: none,
-        today's bytes.  Asynchronous on `stream`."""
+        today's bytes.  orientations: one EXIF orientation 1..8 per frame, the windows then in DISPLAYED pixels
+        (zj_decode_crops_resized_oriented_device); None: today's call.  Asynchronous on `stream`."""
         n = len(d_y)
         scale_log2(max_prescale)
         if len(windows) != n:
@@ -592,7 +638,14 @@ class Context:
         win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
         args = (self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w, out_h, dtype, out_layout,
                 _floats(scale), _floats(bias), _flips(flips, n))
-        if max_prescale != 1:
+        if orientations is not None:
+            if len(orientations) != n:
+                raise ValueError("one orientation per frame")
+            ori = (C.c_uint8 * n)(*[int(o) for o in orientations])
+            _check(lib().zj_decode_crops_resized_oriented_device(*args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR,
+                                                                 scale_log2(max_prescale), ori, d_out, stream),
+                   "zj_decode_crops_resized_oriented_device", self._h)
+        elif max_prescale != 1:
             _check(lib().zj_decode_crops_resized_prescaled_device(*args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR,
                                                                   scale_log2(max_prescale), d_out, stream),
                    "zj_decode_crops_resized_prescaled_device", self._h)
@@ -877,19 +930,29 @@ class Decoder:
             self._raise(rc)
         return n.value
 
+    @property
+    def orientation(self):
+        """EXIF Orientation (1..8; 1: the file says nothing usable) of the file whose headers were read last; 0: none yet."""
+        return int(lib().zj_decoder_orientation(self._d))
+
     def finish_pixels_resized_crop_device(self, x, y, w, h, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
-                                          flip=False, antialias=False, max_prescale=1):
+                                          flip=False, antialias=False, max_prescale=1, apply_orientation=False):
         """Stage 2 cut to the w x h window at (x, y) and resized (the contract of zj_decode_crops_resized_device), left in
         HBM at device pointer d_out; returns the output's length in bytes.  antialias: the triangle filter
         (zj_decoder_finish_pixels_resized_crop_filtered_device, RESIZE_BILINEAR_AA).  max_prescale = 2, 4, 8: a
-        reduced-size decode under the resize (zj_decoder_finish_pixels_resized_crop_prescaled_device); 1: none."""
+        reduced-size decode under the resize (zj_decoder_finish_pixels_resized_crop_prescaled_device); 1: none.
+        apply_orientation: the window is in DISPLAYED pixels of the file's EXIF orientation and so is the output
+        (zj_decoder_finish_pixels_resized_crop_oriented_device); False: today's call."""
         if self._ctx is None:
             self._ctx = Context()
         n = C.c_size_t(0)
         k = scale_log2(max_prescale)
         args = (self._d, self._ctx.handle, x, y, w, h, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
                 1 if flip else 0)
-        if k:
+        if apply_orientation:
+            rc = lib().zj_decoder_finish_pixels_resized_crop_oriented_device(
+                *args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR, k, d_out, cap, C.byref(n))
+        elif k:
             rc = lib().zj_decoder_finish_pixels_resized_crop_prescaled_device(
                 *args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR, k, d_out, cap, C.byref(n))
         elif antialias:
@@ -901,11 +964,20 @@ class Decoder:
             self._raise(rc)
         return n.value
 
-    def finish_pixels_device(self, d_out, cap):
-        """Stage 2 with the pixels left in HBM at device pointer d_out; returns their length in bytes."""
+    def finish_pixels_device(self, d_out, cap, apply_orientation=False):
+        """Stage 2 with the pixels left in HBM at device pointer d_out; returns their length in bytes.
+        apply_orientation: the DISPLAYED image of the file's EXIF orientation
+        (zj_decoder_finish_pixels_oriented_device); returns (length, width, height) of it."""
         if self._ctx is None:
             self._ctx = Context()
         n = C.c_size_t(0)
+        if apply_orientation:
+            w, h = C.c_uint(0), C.c_uint(0)
+            rc = lib().zj_decoder_finish_pixels_oriented_device(self._d, self._ctx.handle, d_out, cap, C.byref(n), C.byref(w),
+                                                                C.byref(h))
+            if rc:
+                self._raise(rc)
+            return n.value, w.value, h.value
         rc = lib().zj_decoder_finish_pixels_device(self._d, self._ctx.handle, d_out, cap, C.byref(n))
         if rc:
             self._raise(rc)

@@ -153,7 +153,7 @@ def _on_stream(s, cur, tensors):
 
 
 def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
-                                   flips=None, stream=None, antialias=False, max_prescale=1):
+                                   flips=None, stream=None, antialias=False, max_prescale=1, orientations=None):
     """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
     per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
@@ -162,7 +162,9 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     antialias: the triangle filter of F.interpolate(antialias=True) instead of plain bilinear.
     max_prescale = 2, 4 or 8: every window is decoded at the largest reduced size (1/2, 1/4, 1/8, up to 1/max_prescale)
     that still is at least the output's, and resized from there; 1 (default): none.  Anything else is a
-    ValueError.  Stream and allocator rules as decode_to_tensor."""
+    ValueError.  orientations: one EXIF orientation 1..8 per frame; the windows are then in DISPLAYED pixels of the frames
+    and the crops are turned before the resize; None (default): none.  Stream and allocator rules as
+    decode_to_tensor."""
     import torch
     from .host import scale_log2
     scale_log2(max_prescale)
@@ -185,7 +187,7 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
                                     [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
                                     TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
-                                    s.cuda_stream, antialias, max_prescale)
+                                    s.cuda_stream, antialias, max_prescale, orientations)
     return out
 
 
@@ -227,16 +229,10 @@ def decode_scaled_to_tensor(ctx, desc, frames, scale, windows=None, stream=None)
     return crop_view_of(desc, storage, n, w, h)
 
 
-def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
-                     stream=None, antialias=False):
-    """u8 CUDA images of their own sizes resized and normalised into ONE dense tensor (zj_resize_device): images =
-    [H, W, C] or [H, W] tensors (in_layout "HWC"), or [3, H, W] ("CHW"); rows may be strided, pixels not.  Output,
-    mean / std, flips, streams and antialias as decode_resized_crops_to_tensor."""
+def _u8_images(images, in_layout):
+    """images as the u8 entry points take them: (tensors, (w, h) each, row pitch each, channels)"""
     import torch
-    dtype = torch.bfloat16 if dtype is None else dtype
-    code = _resize_dtype(dtype)
-    n = len(images)
-    if n == 0:
+    if len(images) == 0:
         raise ValueError("at least one image")
     imgs, sizes, pitches = [], [], []
     for im in images:
@@ -262,6 +258,45 @@ def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HW
     channels = 3 if in_layout == "CHW" else imgs[0].shape[2]
     if any((3 if in_layout == "CHW" else im.shape[2]) != channels for im in imgs):
         raise ValueError("every image has the same channels")
+    return imgs, sizes, pitches, channels
+
+
+def orient_to_tensor(ctx, images, orientations, in_layout="HWC", stream=None):
+    """u8 CUDA images turned to their displayed form (zj_orient_device): images as resize_to_tensor takes
+    them, orientations = one EXIF orientation 1..8 each.  Returns a list of new contiguous tensors, [H', W', C] ([H', W'] for
+    a two-dimensional input) or [3, H', W'], H' x W' the displayed size.  Streams as decode_to_tensor."""
+    import torch
+    from .host import oriented_size
+    imgs, sizes, pitches, channels = _u8_images(images, in_layout)
+    if len(orientations) != len(imgs):
+        raise ValueError("one orientation per image")
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    outs = []
+    with torch.cuda.stream(s):
+        for (w, h), o in zip(sizes, orientations):
+            dw, dh = oriented_size(o, w, h)
+            outs.append(torch.empty((3, dh, dw) if in_layout == "CHW" else (dh, dw, channels), dtype=torch.uint8, device=dev))
+    _on_stream(s, cur, imgs)
+    ctx.orient_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
+                      orientations, [o.data_ptr() for o in outs], pitches, None, s.cuda_stream)
+    return [o.squeeze(-1) if in_layout != "CHW" and im.dim() == 2 else o for o, im in zip(outs, images)]
+
+
+def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
+                     stream=None, antialias=False, orientations=None):
+    """u8 CUDA images of their own sizes resized and normalised into ONE dense tensor (zj_resize_device): images =
+    [H, W, C] or [H, W] tensors (in_layout "HWC"), or [3, H, W] ("CHW"); rows may be strided, pixels not.  Output,
+    mean / std, flips, streams and antialias as decode_resized_crops_to_tensor.  orientations: one EXIF orientation 1..8
+    per image, applied first (orient_to_tensor); None: none."""
+    import torch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    if orientations is not None:
+        images = orient_to_tensor(ctx, images, orientations, in_layout, stream)
+    imgs, sizes, pitches, channels = _u8_images(images, in_layout)
+    n = len(imgs)
     scale, bias = normalize_factors(channels, mean, std)
     dev = imgs[0].device
     cur = torch.cuda.current_stream(dev)
