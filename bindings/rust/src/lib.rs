@@ -30,6 +30,7 @@ pub const ZJ_TENSOR_NCHW: c_int = 0;
 pub const ZJ_TENSOR_NHWC: c_int = 1;
 pub const ZJ_RESIZE_BILINEAR: c_int = 0;
 pub const ZJ_RESIZE_BILINEAR_AA: c_int = 1;
+pub const ZJ_RESIZE_BICUBIC_AA: c_int = 4;
 
 /// `ColorSpace`, `src/misc.rs:88-106` (same discriminants).
 #[repr(i32)]

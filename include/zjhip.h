@@ -282,17 +282,25 @@ ZJ_API int zj_decode_crops_resized_device(zj_ctx *ctx, const zj_frame_desc *d, s
                                           const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *windows,
                                           unsigned out_w, unsigned out_h, int dtype, int out_layout, const float *scale,
                                           const float *bias, const uint8_t *flip, void *d_out, void *stream);
-/* Resize filters of the *_filtered_device entry points (DESIGN.md 3.5, 3.6):
+/* Resize filters of the *_filtered_device entry points (DESIGN.md 3.5, 3.6, 3.9):
  *   ZJ_RESIZE_BILINEAR     the bilinear definition above: the entry points without a filter, byte for byte
  *   ZJ_RESIZE_BILINEAR_AA  antialiased: the triangle filter of Pillow's bilinear / F.interpolate(antialias=True), in exact
  *                          integers.  Every source pixel under an output's support contributes, with weights in units of
  *                          2^-14 that sum to exactly 2^14 per output; the vertical pass runs first and rounds its sums to
  *                          1/256, the horizontal pass gives the same v (0 .. 255 x 65536) the conversions above take.  A
  *                          window of exactly out_w x out_h gives the crop itself, as the bilinear filter does.
+ *   ZJ_RESIZE_BICUBIC_AA   antialiased bicubic: Keys' cubic with a = -1/2 over a support of 2 max(1, n / m) source pixels
+ *                          each side, the filter of Pillow's BICUBIC / F.interpolate(mode="bicubic", antialias=True), in
+ *                          exact integers.  The weights (units of 2^-14, some negative) sum to exactly 2^14 per output; the
+ *                          vertical pass runs first and keeps its signed sums in 1/256 unclamped, the horizontal pass's v is
+ *                          clamped to 0 .. 255 x 65536 and goes through the conversions above.  A window of exactly
+ *                          out_w x out_h gives the crop itself.  No limit on the downscale ratio.  The same argument checks,
+ *                          in the same order, as ZJ_RESIZE_BILINEAR_AA.  (The values 2 and 3 are not filters.)
  * Any other filter is ZJ_ERR_ARG and nothing is launched.  The other arguments are those of the entry point without a
  * filter. */
 #define ZJ_RESIZE_BILINEAR 0
 #define ZJ_RESIZE_BILINEAR_AA 1
+#define ZJ_RESIZE_BICUBIC_AA 4
 ZJ_API int zj_resize_filtered_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh,
                                      const unsigned *in_pitch, int channels, int in_layout, unsigned out_w, unsigned out_h,
                                      int dtype, int out_layout, const float *scale, const float *bias, const uint8_t *flip,

@@ -17,7 +17,10 @@ source pixels under it).
  against max_prescale=1 in the same process, alternating, for the bilinear and the antialiased filter (or,
 with --antialias, that one alone), and gives the largest difference between the two outputs.
 
-usage: python tools/resize_bench.py [--part a|b|all] [--iters N] [--reps R] [--antialias] [--max-prescale S]"""
+--filter bicubic runs the same parts with the bicubic antialiased filter (ZJ_RESIZE_BICUBIC_AA, profiles/resize_bicubic.txt).
+
+usage: python tools/resize_bench.py [--part a|b|all] [--iters N] [--reps R] [--antialias] [--filter bilinear|bicubic]
+                                    [--max-prescale S]"""
 import argparse
 import importlib
 import json
@@ -82,7 +85,7 @@ def part_a(a, zj, torch, ctx, s):
     scale, bias = tensors.normalize_factors(3, MEAN, STD)
     ptrs, sizes = [c.data_ptr() for c in crops], [(w, h) for (_, _, w, h) in wins]
     fn = lambda: ctx.resize_device(ptrs, sizes, 3, zj.LAYOUT_HWC, OUT, OUT, zj.DTYPE_BF16, zj.TENSOR_NCHW, out.data_ptr(),
-                                   scale, bias, None, None, s.cuda_stream, antialias=a.antialias)
+                                   scale, bias, None, None, s.cuda_stream, antialias=a.antialias, interpolation=a.filter)
     timed = timer(torch, s, a.iters)
     ts = [timed(fn) for _ in range(a.reps)]
     written = out.numel() * 2
@@ -96,6 +99,8 @@ def part_a(a, zj, torch, ctx, s):
         read += len(set(x0) | set(x1)) * len(set(y0) | set(y1)) * 3
     med = spread(ts)["median"]
     fname = "zj_resize_filtered_device (ZJ_RESIZE_BILINEAR_AA)" if a.antialias else "zj_resize_device"
+    if a.filter == "bicubic":
+        fname = "zj_resize_filtered_device (ZJ_RESIZE_BICUBIC_AA)"
     return {"part": "a", "what": f"{fname} {N} RandomResizedCrop u8 HWC crops of {W}x{H} -> {OUT}x{OUT} bf16 NCHW",
             "iters": a.iters, "reps": a.reps, "ms": spread(ts), "crop_bytes": sum(w * h * 3 for (_, _, w, h) in wins),
             "bytes_written": written, "bytes_read_touched": read,
@@ -120,7 +125,7 @@ def part_b(a, zj, torch, ctx, s):
     def ours():
         with torch.cuda.stream(s):
             return tensors.decode_resized_crops_to_tensor(ctx, d, frames, wins, (OUT, OUT), dtype=torch.bfloat16, mean=MEAN,
-                                                          std=STD, stream=s, antialias=a.antialias)
+                                                          std=STD, stream=s, antialias=a.antialias, interpolation=a.filter)
 
     groups = {}
     for i, (x, y, w, h) in enumerate(wins):
@@ -135,7 +140,7 @@ def part_b(a, zj, torch, ctx, s):
                 crops = tensors.decode_crops_to_tensor(ctx, d, [frames[i] for i in idx], [wins[i][:2] for i in idx], (w, h),
                                                        stream=s)
                 x = crops.permute(0, 3, 1, 2).float()
-                y = F.interpolate(x, size=(OUT, OUT), mode="bilinear", align_corners=False, antialias=a.antialias)
+                y = F.interpolate(x, size=(OUT, OUT), mode=a.filter, align_corners=False, antialias=a.antialias)
                 y = (y / 255 - mean) / std
                 out[idx] = y.to(torch.bfloat16)
             return out
@@ -149,7 +154,7 @@ def part_b(a, zj, torch, ctx, s):
     torch.cuda.synchronize()
     diff = (o.float() - t.float()).abs().max().item()
     mo, mt = spread(t_ours)["median"], spread(t_torch)["median"]
-    return {"part": "b", "antialias": a.antialias, "what": f"decode_resized_crops_to_tensor, {N} resident {W}x{H} 4:2:0 frames, RandomResizedCrop "
+    return {"part": "b", "antialias": a.antialias, "filter": a.filter, "what": f"decode_resized_crops_to_tensor, {N} resident {W}x{H} 4:2:0 frames, RandomResizedCrop "
             f"windows -> {OUT}x{OUT} bf16 NCHW normalised", "iters": a.iters, "reps": a.reps, "distinct_sizes": len(groups),
             "ours_ms": spread(t_ours), "torch_path_ms": spread(t_torch), "speedup_median": round(mt / mo, 2),
             "max_abs_diff_vs_torch": round(diff, 4)}
@@ -184,7 +189,8 @@ def part_prescale(a, zj, torch, ctx, s):
         def run(mp):
             with torch.cuda.stream(s):
                 return tensors.decode_resized_crops_to_tensor(ctx, d, frames, wins, (OUT, OUT), dtype=torch.bfloat16, mean=MEAN,
-                                                              std=STD, stream=s, antialias=aa, max_prescale=mp)
+                                                              std=STD, stream=s, antialias=aa, max_prescale=mp,
+                                                              interpolation=a.filter)
         t_plain, t_pre = [], []
         for _ in range(a.reps):
             t_plain.append(timed(lambda: run(1)))
@@ -192,7 +198,7 @@ def part_prescale(a, zj, torch, ctx, s):
         o, q = run(1), run(a.max_prescale)
         torch.cuda.synchronize()
         mp_, mq = spread(t_plain)["median"], spread(t_pre)["median"]
-        res.append({"part": "prescale", "windows": a.windows, "antialias": aa, "max_prescale": a.max_prescale,
+        res.append({"part": "prescale", "windows": a.windows, "antialias": aa, "filter": a.filter, "max_prescale": a.max_prescale,
                     "what": f"decode_resized_crops_to_tensor, {N} resident {W}x{H} 4:2:0 frames, RandomResizedCrop windows -> "
                             f"{OUT}x{OUT} bf16 NCHW normalised", "iters": a.iters, "reps": a.reps,
                     "images_per_scale": {str(k): v for k, v in sorted(scales.items())},
@@ -207,10 +213,14 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--antialias", action="store_true")
+    ap.add_argument("--filter", default="bilinear", choices=["bilinear", "bicubic"],
+                    help="bicubic: ZJ_RESIZE_BICUBIC_AA (DESIGN.md 3.9, profiles/resize_bicubic.txt); implies --antialias")
     ap.add_argument("--max-prescale", type=int, default=1, choices=[1, 2, 4, 8])
     ap.add_argument("--windows", default="rrc", choices=["rrc", "half"],
                     help="with --max-prescale: RandomResizedCrop windows, or windows of 448..895 pixels (all decode at 1/2)")
     a = ap.parse_args()
+    if a.filter == "bicubic":
+        a.antialias = True
     import torch
     zj = importlib.import_module("zune-jpeg_amd")
     ctx = zj.Context(zj.BACKEND_HIP, 0)

@@ -844,8 +844,9 @@ int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
             p.pitch[i] = i < m ? pitch[f] : 0;
             if (i < m && flip && flip[f]) p.flip[i >> 5] |= 1u << (i & 31);
         }
-        ZJ_HIP(c, filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(channels, in_chw, dtype, nhwc, p, st)
-                                                  : launch_resize(channels, in_chw, dtype, nhwc, p, st));
+        ZJ_HIP(c, filter == ZJ_RESIZE_BICUBIC_AA    ? launch_resize_bicubic(channels, in_chw, dtype, nhwc, p, st)
+                  : filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(channels, in_chw, dtype, nhwc, p, st)
+                                                    : launch_resize(channels, in_chw, dtype, nhwc, p, st));
     }
     return ZJ_OK;
 }
@@ -877,7 +878,10 @@ int resize_scratch_done(zj_ctx* c, hipStream_t st)
 
 size_t crop_bytes(unsigned w, unsigned h, int channels) { return ((size_t)w * h * channels + 15) & ~(size_t)15; }
 
-bool known_filter(int filter) { return filter == ZJ_RESIZE_BILINEAR || filter == ZJ_RESIZE_BILINEAR_AA; }
+bool known_filter(int filter)
+{
+    return filter == ZJ_RESIZE_BILINEAR || filter == ZJ_RESIZE_BILINEAR_AA || filter == ZJ_RESIZE_BICUBIC_AA;
+}
 
 // images [0, n) -> their displayed form, launches of up to ORIENT_BATCH images; wh: STORED w, h pairs, the
 // pitches resolved, every o[i] 1..8

@@ -2906,7 +2906,7 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
                           void* d_out, size_t out_cap, size_t* out_len, int o = 1)
 {
     using namespace zj;
-    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
+    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA && filter != ZJ_RESIZE_BICUBIC_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
     if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     zj_frame_desc fd;

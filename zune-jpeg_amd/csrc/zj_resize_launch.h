@@ -10,4 +10,6 @@ namespace zj {
 hipError_t launch_resize(int channels, int in_chw, int dtype, int nhwc, const ResizeParams& p, hipStream_t s);
 // the antialiased filter (zj_resize_aa.hip): the same arguments; p.rows and p.groups are not read
 hipError_t launch_resize_aa(int channels, int in_chw, int dtype, int nhwc, const ResizeParams& p, hipStream_t s);
+// the bicubic antialiased filter (zj_resize_bicubic.hip): as launch_resize_aa
+hipError_t launch_resize_bicubic(int channels, int in_chw, int dtype, int nhwc, const ResizeParams& p, hipStream_t s);
 } // namespace zj

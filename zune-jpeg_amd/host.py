@@ -67,6 +67,21 @@ LAYOUT_HWC, LAYOUT_CHW = 0, 1
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8 = 0, 1, 2, 3  # zj_resize_device and the resized crops: the output's dtype
 TENSOR_NCHW, TENSOR_NHWC = 0, 1                          # ... and its layout
 RESIZE_BILINEAR, RESIZE_BILINEAR_AA = 0, 1               # ... and its filter (the *_filtered_device entry points)
+RESIZE_BICUBIC_AA = 4                                    # (2 and 3 are not filters)
+
+
+def resize_filter(antialias=False, interpolation="bilinear"):
+    """The RESIZE_* filter of the Python keywords: "bilinear" plain or antialiased (the triangle filter), "bicubic" only
+    antialiased (Keys' cubic, a = -1/2, over the scaled support: Pillow's BICUBIC, F.interpolate(mode="bicubic",
+    antialias=True))."""
+    if interpolation == "bilinear":
+        return RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR
+    if interpolation == "bicubic":
+        if not antialias:
+            raise ValueError('interpolation="bicubic" needs antialias=True: supported are "bilinear" (antialias False or '
+                             'True) and "bicubic" with antialias=True; the plain 4-tap bicubic is another filter')
+        return RESIZE_BICUBIC_AA
+    raise ValueError(f'interpolation must be "bilinear" or "bicubic", not {interpolation!r}')
 
 
 class FrameDesc(C.Structure):  # zj_frame_desc
@@ -590,10 +605,12 @@ class Context:
                                             arr(d_out), out_pitch, stream), "zj_decode_crops_device", self._h)
 
     def resize_device(self, d_in, sizes, channels, in_layout, out_w, out_h, dtype, out_layout, d_out, scale=None, bias=None,
-                      flips=None, pitches=None, stream=None, antialias=False):
+                      flips=None, pitches=None, stream=None, antialias=False, interpolation="bilinear"):
         """Resize + normalise (zj_resize_device): d_in = device pointers of u8 images, sizes = one (w, h) each, pitches =
         bytes between rows (None: tight); the dense output at d_out.  antialias: the triangle filter
-        (zj_resize_filtered_device, RESIZE_BILINEAR_AA).  Asynchronous on `stream`."""
+        (zj_resize_filtered_device, RESIZE_BILINEAR_AA); with interpolation="bicubic" the bicubic one (RESIZE_BICUBIC_AA,
+        see resize_filter).  Asynchronous on `stream`."""
+        filt = resize_filter(antialias, interpolation)
         n = len(d_in)
         if len(sizes) != n or (pitches is not None and len(pitches) != n):
             raise ValueError("one size (and pitch) per image")
@@ -601,9 +618,8 @@ class Context:
         pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
         args = (self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, in_layout, out_w, out_h, dtype, out_layout,
                 _floats(scale), _floats(bias), _flips(flips, n))
-        if antialias:
-            _check(lib().zj_resize_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, stream), "zj_resize_filtered_device",
-                   self._h)
+        if filt != RESIZE_BILINEAR:
+            _check(lib().zj_resize_filtered_device(*args, filt, d_out, stream), "zj_resize_filtered_device", self._h)
         else:
             _check(lib().zj_resize_device(*args, d_out, stream), "zj_resize_device", self._h)
 
@@ -623,13 +639,16 @@ class Context:
                                       (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_orient_device", self._h)
 
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
-                                    bias=None, flips=None, stream=None, antialias=False, max_prescale=1, orientations=None):
+                                    bias=None, flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,
+                                    interpolation="bilinear"):
         """Resized crop windows (zj_decode_crops_resized_device): pointers as in decode_crops_device, windows = one
         (x, y, w, h) per frame; the dense output at d_out.  antialias: the triangle filter
         (zj_decode_crops_resized_filtered_device, RESIZE_BILINEAR_AA).  max_prescale = 2, 4, 8: a reduced-size decode of
         up to that scale under the resize wherever it does not enlarge (zj_decode_crops_resized_prescaled_device); 1: none,
         today's bytes.  orientations: one EXIF orientation 1..8 per frame, the windows then in DISPLAYED pixels
-        (zj_decode_crops_resized_oriented_device); None: today's call.  Asynchronous on `stream`."""
+        (zj_decode_crops_resized_oriented_device); None: today's call.  interpolation="bicubic" (with antialias=True):
+        RESIZE_BICUBIC_AA in the same calls (see resize_filter).  Asynchronous on `stream`."""
+        filt = resize_filter(antialias, interpolation)
         n = len(d_y)
         scale_log2(max_prescale)
         if len(windows) != n:
@@ -642,15 +661,13 @@ class Context:
             if len(orientations) != n:
                 raise ValueError("one orientation per frame")
             ori = (C.c_uint8 * n)(*[int(o) for o in orientations])
-            _check(lib().zj_decode_crops_resized_oriented_device(*args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR,
-                                                                 scale_log2(max_prescale), ori, d_out, stream),
+            _check(lib().zj_decode_crops_resized_oriented_device(*args, filt, scale_log2(max_prescale), ori, d_out, stream),
                    "zj_decode_crops_resized_oriented_device", self._h)
         elif max_prescale != 1:
-            _check(lib().zj_decode_crops_resized_prescaled_device(*args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR,
-                                                                  scale_log2(max_prescale), d_out, stream),
+            _check(lib().zj_decode_crops_resized_prescaled_device(*args, filt, scale_log2(max_prescale), d_out, stream),
                    "zj_decode_crops_resized_prescaled_device", self._h)
-        elif antialias:
-            _check(lib().zj_decode_crops_resized_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, stream),
+        elif filt != RESIZE_BILINEAR:
+            _check(lib().zj_decode_crops_resized_filtered_device(*args, filt, d_out, stream),
                    "zj_decode_crops_resized_filtered_device", self._h)
         else:
             _check(lib().zj_decode_crops_resized_device(*args, d_out, stream), "zj_decode_crops_resized_device", self._h)
@@ -936,13 +953,16 @@ class Decoder:
         return int(lib().zj_decoder_orientation(self._d))
 
     def finish_pixels_resized_crop_device(self, x, y, w, h, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
-                                          flip=False, antialias=False, max_prescale=1, apply_orientation=False):
+                                          flip=False, antialias=False, max_prescale=1, apply_orientation=False,
+                                          interpolation="bilinear"):
         """Stage 2 cut to the w x h window at (x, y) and resized (the contract of zj_decode_crops_resized_device), left in
         HBM at device pointer d_out; returns the output's length in bytes.  antialias: the triangle filter
         (zj_decoder_finish_pixels_resized_crop_filtered_device, RESIZE_BILINEAR_AA).  max_prescale = 2, 4, 8: a
         reduced-size decode under the resize (zj_decoder_finish_pixels_resized_crop_prescaled_device); 1: none.
         apply_orientation: the window is in DISPLAYED pixels of the file's EXIF orientation and so is the output
-        (zj_decoder_finish_pixels_resized_crop_oriented_device); False: today's call."""
+        (zj_decoder_finish_pixels_resized_crop_oriented_device); False: today's call.  interpolation="bicubic" (with
+        antialias=True): RESIZE_BICUBIC_AA in the same calls (see resize_filter)."""
+        filt = resize_filter(antialias, interpolation)
         if self._ctx is None:
             self._ctx = Context()
         n = C.c_size_t(0)
@@ -950,14 +970,11 @@ class Decoder:
         args = (self._d, self._ctx.handle, x, y, w, h, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
                 1 if flip else 0)
         if apply_orientation:
-            rc = lib().zj_decoder_finish_pixels_resized_crop_oriented_device(
-                *args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR, k, d_out, cap, C.byref(n))
+            rc = lib().zj_decoder_finish_pixels_resized_crop_oriented_device(*args, filt, k, d_out, cap, C.byref(n))
         elif k:
-            rc = lib().zj_decoder_finish_pixels_resized_crop_prescaled_device(
-                *args, RESIZE_BILINEAR_AA if antialias else RESIZE_BILINEAR, k, d_out, cap, C.byref(n))
-        elif antialias:
-            rc = lib().zj_decoder_finish_pixels_resized_crop_filtered_device(*args, RESIZE_BILINEAR_AA, d_out, cap,
-                                                                             C.byref(n))
+            rc = lib().zj_decoder_finish_pixels_resized_crop_prescaled_device(*args, filt, k, d_out, cap, C.byref(n))
+        elif filt != RESIZE_BILINEAR:
+            rc = lib().zj_decoder_finish_pixels_resized_crop_filtered_device(*args, filt, d_out, cap, C.byref(n))
         else:
             rc = lib().zj_decoder_finish_pixels_resized_crop_device(*args, d_out, cap, C.byref(n))
         if rc:

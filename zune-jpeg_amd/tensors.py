@@ -153,21 +153,25 @@ def _on_stream(s, cur, tensors):
 
 
 def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
-                                   flips=None, stream=None, antialias=False, max_prescale=1, orientations=None):
+                                   flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,
+                                   interpolation="bilinear"):
     """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
     per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
     ("NHWC") of `dtype` (default bfloat16); C = 3 for RGB / YCbCr, 1 for GRAYSCALE.  mean / std: torchvision's Normalize
     of the [0, 1] image (None: the [0, 1] image itself); unused for uint8.  flips: one bool per frame (horizontal).
     antialias: the triangle filter of F.interpolate(antialias=True) instead of plain bilinear.
+    interpolation: "bilinear" (default) or, with antialias=True only, "bicubic": the filter of F.interpolate(mode="bicubic",
+    antialias=True) and Pillow's BICUBIC; anything else is a ValueError.
     max_prescale = 2, 4 or 8: every window is decoded at the largest reduced size (1/2, 1/4, 1/8, up to 1/max_prescale)
     that still is at least the output's, and resized from there; 1 (default): none.  Anything else is a
     ValueError.  orientations: one EXIF orientation 1..8 per frame; the windows are then in DISPLAYED pixels of the frames
     and the crops are turned before the resize; None (default): none.  Stream and allocator rules as
     decode_to_tensor."""
     import torch
-    from .host import scale_log2
+    from .host import resize_filter, scale_log2
     scale_log2(max_prescale)
+    resize_filter(antialias, interpolation)
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
     n = len(frames)
@@ -187,7 +191,7 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
                                     [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
                                     TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
-                                    s.cuda_stream, antialias, max_prescale, orientations)
+                                    s.cuda_stream, antialias, max_prescale, orientations, interpolation)
     return out
 
 
@@ -285,12 +289,14 @@ def orient_to_tensor(ctx, images, orientations, in_layout="HWC", stream=None):
 
 
 def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
-                     stream=None, antialias=False, orientations=None):
+                     stream=None, antialias=False, orientations=None, interpolation="bilinear"):
     """u8 CUDA images of their own sizes resized and normalised into ONE dense tensor (zj_resize_device): images =
     [H, W, C] or [H, W] tensors (in_layout "HWC"), or [3, H, W] ("CHW"); rows may be strided, pixels not.  Output,
-    mean / std, flips, streams and antialias as decode_resized_crops_to_tensor.  orientations: one EXIF orientation 1..8
-    per image, applied first (orient_to_tensor); None: none."""
+    mean / std, flips, streams, antialias and interpolation as decode_resized_crops_to_tensor.  orientations: one EXIF
+    orientation 1..8 per image, applied first (orient_to_tensor); None: none."""
     import torch
+    from .host import resize_filter
+    resize_filter(antialias, interpolation)
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
     if orientations is not None:
@@ -305,5 +311,5 @@ def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HW
     _on_stream(s, cur, imgs)
     ctx.resize_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
                       size[0], size[1], code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias,
-                      flips, pitches, s.cuda_stream, antialias)
+                      flips, pitches, s.cuda_stream, antialias, interpolation)
     return out
