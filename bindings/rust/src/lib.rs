@@ -258,6 +258,18 @@ extern "C" {
                                                    out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
                                                    filter: c_int, max_prescale_log2: c_int, orientation: *const u8,
                                                    d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_resized_mixed_device(ctx: *mut zj_ctx, descs: *const zj_frame_desc, nframes: usize,
+                                                d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                                windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                                filter: c_int, max_prescale_log2: c_int, orientation: *const u8,
+                                                d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_resized_crop_batch_device(ds: *const *mut zj_decoder, n: usize, ctx: *mut zj_ctx,
+                                                              windows: *const c_uint, out_w: c_uint, out_h: c_uint,
+                                                              dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                              bias: *const f32, flip: *const u8, filter: c_int,
+                                                              max_prescale_log2: c_int, apply_orientation: c_int,
+                                                              d_out: *mut c_void, out_cap: usize, rcs: *mut c_int) -> c_int;
     pub fn zj_decoder_orientation(d: *const zj_decoder) -> c_int;
     pub fn zj_decoder_finish_pixels_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, d_out: *mut u8, out_cap: usize,
                                                     out_len: *mut usize, out_w: *mut c_uint, out_h: *mut c_uint) -> c_int;

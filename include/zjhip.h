@@ -386,6 +386,25 @@ ZJ_API int zj_decode_crops_resized_oriented_device(zj_ctx *ctx, const zj_frame_d
                                                    const float *bias, const uint8_t *flip, int filter,
                                                    int max_prescale_log2, const uint8_t *orientation, void *d_out,
                                                    void *stream);
+/* ---- frames of MIXED geometry into one resized-crop tensor ---------------------------------------------
+ * zj_decode_crops_resized_oriented_device for frames that each bring their own descriptor: frame f is described by descs[f].
+ * Width and height, h_max and v_max, the quantisation tables, flags and in_components may differ per frame; out_colorspace
+ * and out_layout must be the same in all descriptors (ZJ_ERR_ARG otherwise) and out_pitch 0.
+ * DEFINITION: image f of the output equals, byte for byte, what zj_decode_crops_resized_oriented_device(ctx, &descs[f], 1, ...)
+ * writes for that frame alone, with the same window, filter, prescale, orientation and flip.
+ * All frames are checked before anything is launched; on a failed check the call returns the status the single-frame call
+ * would return for the first failing frame and launches nothing.  The crops pass through the context's buffer in groups, as
+ * in the one-geometry call; per group the crop stage is at most one launch per sampling mode present, one reduced-decode
+ * launch per (sampling mode, scale) present and one launch for the rows below the frames' last complete strips -- the
+ * frames' geometry travels in a table in device memory that the call uploads on `stream` -- then the orient and resize
+ * launches, one per 128 images.  Not limited to ZJ_SCATTER_MAX frames per launch.  Asynchronous on `stream` (NULL: the
+ * context's). */
+ZJ_API int zj_decode_crops_resized_mixed_device(zj_ctx *ctx, const zj_frame_desc *descs /* [nframes] */, size_t nframes,
+                                                const int16_t *const *d_y, const int16_t *const *d_cb,
+                                                const int16_t *const *d_cr, const unsigned *windows, unsigned out_w,
+                                                unsigned out_h, int dtype, int out_layout, const float *scale,
+                                                const float *bias, const uint8_t *flip, int filter, int max_prescale_log2,
+                                                const uint8_t *orientation, void *d_out, void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -543,6 +562,23 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder *d, 
                                                                  const float *bias, int flip, int filter,
                                                                  int max_prescale_log2, void *d_out, size_t out_cap,
                                                                  size_t *out_len);
+/* n decoders after zj_decoder_prepare or zj_decoder_decode_coefficients, each with its own file of any size, into one
+ * resized-crop tensor: image k lands at d_out + k * zj_resized_out_len().  windows[4k .. 4k + 3] = x, y, w, h in DISPLAYED
+ * pixels of file k's own orientation when apply_orientation is set, else in stored pixels.
+ * DEFINITION: image k equals what zj_decoder_finish_pixels_resized_crop_oriented_device gives for decoder k alone (without
+ * apply_orientation: the _prescaled_ call), and rcs[k] is that call's status.  A file that fails leaves its image's bytes
+ * untouched and does not stop the others.  The call itself returns non-zero only for null arguments, out_cap below n images,
+ * or decoders whose output colour space or layout differ.
+ * Files the CPU walker decoded: only the plane rows each window needs are uploaded, all files of a launch group into one
+ * arena of the context, all uploads queued before the group's mixed-geometry launches
+ * (zj_decode_crops_resized_mixed_device).  Decoders with a scan left for the device (zj_options.entropy), and all-zero
+ * outputs, are finished one by one through the single-file call.  Stream ordering as zj_decoder_finish_pixels_device. */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx,
+                                                              const unsigned *windows, unsigned out_w, unsigned out_h,
+                                                              int dtype, int out_layout, const float *scale,
+                                                              const float *bias, const uint8_t *flip, int filter,
+                                                              int max_prescale_log2, int apply_orientation, void *d_out,
+                                                              size_t out_cap, int *rcs);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

@@ -14,6 +14,7 @@
 
 #include "../../include/zjhip.h"
 #include "zj_launch.h"
+#include "zj_mixed_launch.h"
 #include "zj_orient_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
@@ -84,6 +85,14 @@ struct zj_ctx {
     // resize that read it, recorded on whichever stream that call ran on (the next user waits for it on ITS stream)
     void* rz_buf = nullptr; size_t rz_cap = 0;
     hipEvent_t rz_done = nullptr; bool rz_used = false;
+    // mixed-geometry crops (zj_decode_crops_resized_mixed_device): the per-frame records of a launch group,
+    // built in pinned staging and copied to the device table on the caller's stream.  mx_up: after the last copy out of the
+    // staging (the host waits for it before writing the staging again); mx_done: after the last launch that read the device
+    // table, on whichever stream that ran (the next copy into it waits for it on ITS stream).  mx_arena: the plane rows of a
+    // decoder batch's files (zj_decoder_finish_pixels_resized_crop_batch_device), on the context stream only.
+    void* mx_host = nullptr; void* mx_dev = nullptr; size_t mx_cap = 0;
+    hipEvent_t mx_up = nullptr, mx_done = nullptr; bool mx_used = false;
+    void* mx_arena = nullptr; void* mx_stage = nullptr; size_t mx_arena_cap = 0; // (mx_stage: pinned, the same size)
     bool scan_planes_only = false; // zjint_scan_to_planes: the entropy stage alone, the planes stay in the slot (crop windows)
     int huff_rounds = 0;          // synchronisation rounds of the last scan
     int huff_plane_slot = 0;
@@ -221,6 +230,12 @@ void zj_ctx_destroy(zj_ctx* c)
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->rz_done) { if (c->rz_used) (void)hipEventSynchronize(c->rz_done); (void)hipEventDestroy(c->rz_done); }
     if (c->rz_buf) (void)hipFree(c->rz_buf);
+    if (c->mx_done) { if (c->mx_used) (void)hipEventSynchronize(c->mx_done); (void)hipEventDestroy(c->mx_done); }
+    if (c->mx_up) (void)hipEventDestroy(c->mx_up);
+    if (c->mx_dev) (void)hipFree(c->mx_dev);
+    if (c->mx_host) (void)hipHostFree(c->mx_host);
+    if (c->mx_arena) (void)hipFree(c->mx_arena);
+    if (c->mx_stage) (void)hipHostFree(c->mx_stage);
 
     for (hipStream_t st : {c->s_up, c->s_run, c->s_down})
         if (st) (void)hipStreamSynchronize(st);
@@ -1171,6 +1186,215 @@ int zj_decode_crops_resized_oriented_device(zj_ctx* c, const zj_frame_desc* d, s
                                                         scale, bias, flip, filter, max_prescale_log2, d_out, stream);
     return crops_resized_impl(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter,
                               max_prescale_log2, orientation, d_out, stream);
+}
+
+/* ---- mixed-geometry resized crops ----------------------------------------------- */
+namespace {
+// the pinned staging and the device table, at least `bytes` each, the staging free for the host to write: the last copy out
+// of it has finished; growing them waits for the last launch that read the device table as well
+int mixed_tables(zj_ctx* c, size_t bytes)
+{
+    if (!c->mx_up) {
+        ZJ_HIP(c, hipEventCreateWithFlags(&c->mx_up, hipEventDisableTiming));
+        ZJ_HIP(c, hipEventCreateWithFlags(&c->mx_done, hipEventDisableTiming));
+    }
+    if (c->mx_used) ZJ_HIP(c, hipEventSynchronize(c->mx_up));
+    if (bytes <= c->mx_cap) return ZJ_OK;
+    if (c->mx_used) ZJ_HIP(c, hipEventSynchronize(c->mx_done));
+    if (c->mx_dev) { ZJ_HIP(c, hipFree(c->mx_dev)); c->mx_dev = nullptr; }
+    if (c->mx_host) { ZJ_HIP(c, hipHostFree(c->mx_host)); c->mx_host = nullptr; }
+    c->mx_cap = 0;
+    const size_t cap = bytes + bytes / 4 + 4096;
+    ZJ_HIP(c, hipHostMalloc(&c->mx_host, cap, hipHostMallocDefault));
+    ZJ_HIP(c, hipMalloc(&c->mx_dev, cap));
+    c->mx_cap = cap;
+    return ZJ_OK;
+}
+
+// The call behind both mixed entry points.  host_planes: y / cb / cr are the CPU walker's planes in host memory; the rows
+// each frame's window needs go into the context's arena, a group's uploads all queued before its launches (the planes must
+// stay as they are until the stream has run: the caller synchronises).  Otherwise they are device planes.
+int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
+                             const int16_t* const* d_cb, const int16_t* const* d_cr, bool host_planes, const unsigned* windows,
+                             unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                             const uint8_t* flip, int filter, int max_prescale_log2, const uint8_t* orientation, void* d_out,
+                             void* stream)
+{
+    if (!known_filter(filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
+    if (!c || !descs || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
+    if (!mixed_descs_agree(descs, nframes)) return ZJ_ERR_ARG;
+    // every frame's checks, in the one-geometry call's order, before anything is launched
+    std::vector<MixedFrame> fr(nframes);
+    float s[3], b[3];
+    const int ch = resize_channels(&descs[0]);
+    const int out_rc = ch ? resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, ch, s, b) : 0;
+    for (size_t f = 0; f < nframes; f++) {
+        const zj_frame_desc* const d = &descs[f];
+        int rc = mixed_frame_plan(d, windows + 4 * f, orientation ? (orientation[f] ? orientation[f] : -1) : 0, fr[f]);
+        if (rc) return rc;
+        if (out_rc) return out_rc;
+        const bool chroma = fr[f].pl.out != OUT_GRAY;
+        if (chroma && (!d_cb || !d_cr)) return ZJ_ERR_ARG;
+        if ((rc = check_plane_ptrs(d_y + f, chroma ? d_cb + f : nullptr, chroma ? d_cr + f : nullptr, chroma, 1))) return rc;
+        if ((rc = mixed_frame_window(d, windows + 4 * f, out_w, out_h, max_prescale_log2, fr[f]))) return rc;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const bool chw = fr[0].pl.out == OUT_RGB_CHW;
+    const size_t img_bytes = resized_len(ch, out_w, out_h, dtype);
+    // launch groups as crops_resized_impl forms them
+    const auto turned = [&](size_t f) { return fr[f].o != 1; };
+    const auto cbytes = [&](size_t f) { return crop_bytes(fr[f].cwin[2], fr[f].cwin[3], ch); };
+    size_t need = 0;
+    for (size_t f = 0, g = 0; f < nframes; f++) {
+        const size_t cb = cbytes(f) * (turned(f) ? 2 : 1);
+        g = g && g + cb > RZ_GROUP_CAP ? cb : g + cb;
+        if (g > need) need = g;
+    }
+    uint8_t* buf = nullptr;
+    int rc;
+    if ((rc = resize_scratch(c, need, st, &buf))) return rc;
+    std::vector<uint8_t*> crops(nframes);
+    std::vector<unsigned> pitch(nframes), wh(2 * nframes);
+    std::vector<const int16_t*> py(nframes), pcb(nframes), pcr(nframes);
+    MixedTables tabs;
+    for (size_t g0 = 0; g0 < nframes;) {
+        size_t g1 = g0, off = 0, off2 = 0;
+        while (g1 < nframes) {
+            const size_t cb = cbytes(g1);
+            if (g1 > g0 && off + off2 + cb * (turned(g1) ? 2 : 1) > RZ_GROUP_CAP) break;
+            crops[g1] = buf + off;
+            pitch[g1] = fr[g1].cwin[2] * (chw ? 1 : ch);
+            wh[2 * g1] = fr[g1].cwin[2]; wh[2 * g1 + 1] = fr[g1].cwin[3];
+            off += cb;
+            if (turned(g1)) off2 += cb;
+            g1++;
+        }
+        const size_t ng = g1 - g0;
+        // (first: it waits until the copies out of the pinned staging, the planes' and the tables', have finished)
+        if ((rc = mixed_tables(c, mixed_table_bytes(fr.data() + g0, ng)))) return rc;
+        if (host_planes) {
+            // The rows each window needs (mixed_plane_rows), packed: host planes -> pinned staging -> ONE copy into the arena.
+            // A frame's plane address is the one its row 0 would have: every address a lane forms lies in a strip or MCU
+            // row of its own window (zj_device.h: locate, halo_locate; zj_scaled.h: scaled_block_loc), all of them uploaded.
+            size_t total = 0;
+            for (size_t f = g0; f < g1; f++) {
+                size_t r0, r1, yrow, crow;
+                mixed_plane_rows(&descs[f], fr[f], r0, r1, yrow, crow);
+                total += (r1 - r0) * (yrow + (fr[f].pl.out != OUT_GRAY ? 2 * crow : 0)) * 2;
+            }
+            if (total > c->mx_arena_cap) {
+                ZJ_HIP(c, hipStreamSynchronize(st));
+                if (c->mx_arena) { ZJ_HIP(c, hipFree(c->mx_arena)); c->mx_arena = nullptr; }
+                if (c->mx_stage) { ZJ_HIP(c, hipHostFree(c->mx_stage)); c->mx_stage = nullptr; }
+                c->mx_arena_cap = 0;
+                const size_t cap = total + total / 4 + 4096;
+                ZJ_HIP(c, hipHostMalloc(&c->mx_stage, cap, hipHostMallocDefault));
+                ZJ_HIP(c, hipMalloc(&c->mx_arena, cap));
+                c->mx_arena_cap = cap;
+            }
+            size_t at = 0; // i16 elements into staging and arena alike
+            for (size_t f = g0; f < g1; f++) {
+                size_t r0, r1, yrow, crow;
+                mixed_plane_rows(&descs[f], fr[f], r0, r1, yrow, crow);
+                const bool chroma = fr[f].pl.out != OUT_GRAY;
+                const int16_t* const src[3] = {d_y[f], chroma ? d_cb[f] : nullptr, chroma ? d_cr[f] : nullptr};
+                const int16_t** const dst[3] = {&py[f], &pcb[f], &pcr[f]};
+                for (int k = 0; k < 3; k++) {
+                    const size_t row = k ? crow : yrow, n = (r1 - r0) * row;
+                    *dst[k] = nullptr;
+                    if (!src[k]) continue;
+                    *dst[k] = (const int16_t*)((uintptr_t)c->mx_arena + 2 * at - 2 * r0 * row);
+                    if (n) memcpy((int16_t*)c->mx_stage + at, src[k] + r0 * row, n * 2);
+                    at += n;
+                }
+            }
+            if (at) ZJ_HIP(c, hipMemcpyAsync(c->mx_arena, c->mx_stage, at * 2, hipMemcpyHostToDevice, st));
+        } else {
+            for (size_t f = g0; f < g1; f++) {
+                const bool chroma = fr[f].pl.out != OUT_GRAY;
+                py[f] = d_y[f]; pcb[f] = chroma ? d_cb[f] : nullptr; pcr[f] = chroma ? d_cr[f] : nullptr;
+            }
+        }
+        // the group's records: staging -> device table, then one launch per run
+        mixed_fill_tables(descs + g0, fr.data() + g0, ng, py.data() + g0, pcb.data() + g0, pcr.data() + g0, crops.data() + g0,
+                          (uint8_t*)c->mx_host, tabs);
+        if (c->mx_used) ZJ_HIP(c, hipStreamWaitEvent(st, c->mx_done, 0));
+        ZJ_HIP(c, hipMemcpyAsync(c->mx_dev, c->mx_host, tabs.bytes, hipMemcpyHostToDevice, st));
+        ZJ_HIP(c, hipEventRecord(c->mx_up, st));
+        c->mx_used = true;
+        const uint8_t* const tab = (const uint8_t*)c->mx_dev;
+        hipError_t e = hipSuccess;
+        if (tabs.zero.n) e = launch_crop_zero_mixed((const MixedZero*)(tab + tabs.zero.off), tabs.zero.n, tabs.zero.gx, tabs.zero.gy, st);
+        for (size_t i = 0; e == hipSuccess && i < tabs.crop.size(); i++) {
+            const MixedLaunch& l = tabs.crop[i];
+            e = launch_crop_mixed(l.hs, l.vs, l.out, (const CropParams*)(tab + l.off), l.n, l.gx, l.gy, st);
+        }
+        for (size_t i = 0; e == hipSuccess && i < tabs.scaled.size(); i++) {
+            const MixedLaunch& l = tabs.scaled[i];
+            e = launch_scaled_mixed(l.hs, l.vs, l.out, l.sl, (const ScaledParams*)(tab + l.off), l.n, l.gx, l.gy, st);
+        }
+        // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
+        (void)hipEventRecord(c->mx_done, st);
+        ZJ_HIP(c, e);
+        if (off2) { // the turned frames: crop -> its displayed form in the second region (crops_resized_impl)
+            std::vector<const uint8_t*> oin;
+            std::vector<uint8_t*> oout;
+            std::vector<unsigned> owh, oip, oop;
+            std::vector<uint8_t> oo;
+            size_t at = off;
+            for (size_t f = g0; f < g1; f++) {
+                if (!turned(f)) continue;
+                unsigned dw = 0, dh = 0;
+                orient_size(fr[f].o, wh[2 * f], wh[2 * f + 1], &dw, &dh);
+                oin.push_back(crops[f]); oout.push_back(buf + at);
+                owh.push_back(wh[2 * f]); owh.push_back(wh[2 * f + 1]);
+                oip.push_back(pitch[f]); oop.push_back(dw * (chw ? 1 : ch));
+                oo.push_back((uint8_t)fr[f].o);
+                crops[f] = buf + at;
+                wh[2 * f] = dw; wh[2 * f + 1] = dh;
+                pitch[f] = dw * (chw ? 1 : ch);
+                at += crop_bytes(dw, dh, ch);
+            }
+            if ((rc = orient_launches(c, oin.size(), oin.data(), owh.data(), oip.data(), ch, chw, oo.data(), oout.data(),
+                                      oop.data(), st)))
+                return rc;
+        }
+        if ((rc = resize_launches(c, ng, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h, dtype,
+                                  out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
+                                  (uint8_t*)d_out + g0 * img_bytes, st)))
+            return rc;
+        if ((rc = resize_scratch_done(c, st))) return rc;
+        g0 = g1;
+    }
+    return ZJ_OK;
+}
+} // namespace
+
+int zj_decode_crops_resized_mixed_device(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
+                                         const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                         const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                         const uint8_t* orientation, void* d_out, void* stream)
+{
+    return crops_resized_mixed_impl(c, descs, nframes, d_y, d_cb, d_cr, false, windows, out_w, out_h, dtype, out_layout, scale, bias,
+                                    flip, filter, max_prescale_log2, orientation, d_out, stream);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_resized_crop_batch_device): the same over the CPU walker's planes
+// in host memory, on the context stream, synchronised (the planes are free again when it returns)
+int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                   const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows, unsigned out_w,
+                                   unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                                   const uint8_t* flip, int filter, int max_prescale_log2, const uint8_t* orientation, void* d_out)
+{
+    const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows, out_w, out_h, dtype, out_layout, scale, bias,
+                                            flip, filter, max_prescale_log2, orientation, d_out, nullptr);
+    if (c && c->stream) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
+    }
+    return rc;
 }
 
 int zj_oriented_size(int orientation, unsigned w, unsigned h, unsigned* ow, unsigned* oh)

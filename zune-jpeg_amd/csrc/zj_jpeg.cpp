@@ -2719,6 +2719,13 @@ __attribute__((weak)) int zjint_scratch_idle(zj_ctx* c, size_t bytes, uint8_t** 
 __attribute__((weak)) int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, int o,
                                            uint8_t* d_out);
 
+// ... and the resized crops of several files' planes in host memory, each of its own geometry
+__attribute__((weak)) int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                                         const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
+                                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                                         const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                                         const uint8_t* orientation, void* d_out);
+
 // ... and the reduced-size decode of one frame's window
 __attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
                                              int planes_on_device, int scale_log2, unsigned x, unsigned yy, unsigned w, unsigned h,
@@ -2901,17 +2908,17 @@ int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale
 // that covers it, from the reduced-size decode -- into the context's buffer, then the resize
 // o: 1, or the orientation the window is given in: x, y, w, h are then DISPLAYED pixels, the stored window
 // they map to is decoded as ever, turned into the second half of the buffer, and the resize reads that
-static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
-                          unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
-                          void* d_out, size_t out_cap, size_t* out_len, int o = 1)
+// finish_resized's checks of its arguments, up to the stored window x, y, w, h (given in displayed pixels when o != 1); fd, ch:
+// the file's descriptor and channel count
+static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsigned& w, unsigned& h, unsigned out_w, unsigned out_h,
+                          int dtype, int filter, size_t out_cap, size_t* out_len, int o, zj_frame_desc& fd, int& ch)
 {
     using namespace zj;
     if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA && filter != ZJ_RESIZE_BICUBIC_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
     if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
-    zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
-    const int ch = resize_channels(&fd);
+    ch = resize_channels(&fd);
     if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
     if (k && zero_output(&fd)) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
     const size_t need = resized_len(ch, out_w, out_h, dtype);
@@ -2926,13 +2933,25 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
         x = st[0]; y = st[1]; w = st[2]; h = st[3];
     }
     if (w == 0 || h == 0 || (size_t)x + w > fd.width || (size_t)y + h > fd.height) return fail(d, ZJ_ERR_ARG, "not a valid crop window");
+    return ZJ_OK;
+}
+
+static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
+                          unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
+                          void* d_out, size_t out_cap, size_t* out_len, int o = 1)
+{
+    using namespace zj;
+    zj_frame_desc fd;
+    int ch = 0;
+    int rc = resized_checks(d, k, x, y, w, h, out_w, out_h, dtype, filter, out_cap, out_len, o, fd, ch);
+    if (rc) return rc;
     const unsigned full[4] = {x, y, w, h};
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
     const WindowLayout g = window_layout(&fd, win[2], win[3], 0); // (the crop's own check of the window follows)
     const size_t half = (g.len + 15) & ~(size_t)15;
     uint8_t* crop = nullptr;
-    int rc = zjint_resize_scratch(ctx, o != 1 ? 2 * half : g.len, &crop);
+    rc = zjint_resize_scratch(ctx, o != 1 ? 2 * half : g.len, &crop);
     if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     size_t got = 0;
     rc = k ? zj_decoder_finish_pixels_scaled_device(d, ctx, k, win[0], win[1], win[2], win[3], crop, g.len, 0, &got)
@@ -2993,6 +3012,70 @@ int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder* d, zj_ctx*
     const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
     return finish_resized(d, ctx, k, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len,
                           d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
+}
+
+// Several prepared files of any sizes into one resized-crop tensor.  The files the CPU walker decoded go
+// through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan left for the device, and one
+// whose output is all zeros, is finished through the single-file call, which gives the same bytes.
+int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* windows,
+                                                       unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                       const float* scale, const float* bias, const uint8_t* flip, int filter,
+                                                       int max_prescale_log2, int apply_orientation, void* d_out, size_t out_cap,
+                                                       int* rcs)
+{
+    using namespace zj;
+    if (!ds || !n || !ctx || !windows || !d_out || !rcs) return ZJ_ERR_ARG;
+    if (!zjint_crops_resized_mixed_host) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    const zj_decoder* first = nullptr;
+    for (size_t k = 0; k < n; k++) {
+        if (!ds[k]) continue;
+        if (!first) first = ds[k];
+        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
+    }
+    if (!first) return ZJ_ERR_ARG;
+    zj_frame_desc fd0{};
+    fd0.out_colorspace = (uint32_t)first->out_colorspace;
+    const size_t img = resized_len(resize_channels(&fd0), out_w, out_h, dtype); // (0: every file's own call says why)
+    if (img && out_cap / img < n) return ZJ_ERR_ARG;
+    const auto single = [&](size_t k) {
+        const unsigned* const w = windows + 4 * k;
+        void* const o = (uint8_t*)d_out + k * img;
+        const int fl = flip ? flip[k] : 0;
+        return apply_orientation ? zj_decoder_finish_pixels_resized_crop_oriented_device(ds[k], ctx, w[0], w[1], w[2], w[3], out_w, out_h, dtype, out_layout, scale, bias, fl, filter, max_prescale_log2, o, img, nullptr)
+                                 : zj_decoder_finish_pixels_resized_crop_prescaled_device(ds[k], ctx, w[0], w[1], w[2], w[3], out_w, out_h, dtype, out_layout, scale, bias, fl, filter, max_prescale_log2, o, img, nullptr);
+    };
+    std::vector<zj_frame_desc> fds(n);
+    std::vector<const int16_t*> py(n), pcb(n), pcr(n);
+    std::vector<uint8_t> ori(n, 1);
+    std::vector<char> mixed(n, 0);
+    for (size_t k = 0; k < n; k++) {
+        zj_decoder* const d = ds[k];
+        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
+        if (max_prescale_log2 < 0 || max_prescale_log2 > 3 || !img) { rcs[k] = single(k); continue; }
+        const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
+        unsigned x = windows[4 * k], y = windows[4 * k + 1], w = windows[4 * k + 2], h = windows[4 * k + 3];
+        const int kk = prescale_pick(w, h, out_w, out_h, max_prescale_log2);
+        int ch = 0;
+        if ((rcs[k] = resized_checks(d, kk, x, y, w, h, out_w, out_h, dtype, filter, img, nullptr, o, fds[k], ch))) continue;
+        if (d->scan_ready || !d->coef_valid || zero_output(&fds[k])) { rcs[k] = single(k); continue; }
+        py[k] = d->comps[0].coef;
+        pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
+        ori[k] = (uint8_t)o;
+        mixed[k] = 1;
+    }
+    for (size_t k0 = 0; k0 < n;) {
+        if (!mixed[k0]) { k0++; continue; }
+        size_t k1 = k0;
+        while (k1 < n && mixed[k1]) k1++;
+        const int rc = zjint_crops_resized_mixed_host(ctx, fds.data() + k0, k1 - k0, py.data() + k0, pcb.data() + k0, pcr.data() + k0,
+                                                      windows + 4 * k0, out_w, out_h, dtype, out_layout, scale, bias,
+                                                      flip ? flip + k0 : nullptr, filter, max_prescale_log2,
+                                                      apply_orientation ? ori.data() + k0 : nullptr, (uint8_t*)d_out + k0 * img);
+        // a run that is refused has launched nothing: each of its files through its own call, which names the failing one
+        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(k) : (int)ZJ_OK;
+        k0 = k1;
+    }
+    return ZJ_OK;
 }
 
 // The whole displayed image of the prepared file, tight, in the decoder's colour space and layout: orientation 1 decodes

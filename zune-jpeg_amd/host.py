@@ -187,6 +187,7 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_oriented_size", "zj_orient_window", "zj_orient_device", "zj_decode_crops_resized_oriented_device",
     "zj_decoder_orientation", "zj_decoder_finish_pixels_oriented_device",
     "zj_decoder_finish_pixels_resized_crop_oriented_device",
+    "zj_decode_crops_resized_mixed_device", "zj_decoder_finish_pixels_resized_crop_batch_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -356,6 +357,11 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_oriented_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                                                         C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int,
                                                                         C.c_int, C.c_int, vp, sz, C.POINTER(sz)]
+    L.zj_decode_crops_resized_mixed_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
+                                                       C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.zj_decoder_finish_pixels_resized_crop_batch_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int, vp,
+                                                                     vp, vp, C.c_int, C.c_int, C.c_int, vp, sz,
+                                                                     C.POINTER(C.c_int)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -671,6 +677,25 @@ class Context:
                    "zj_decode_crops_resized_filtered_device", self._h)
         else:
             _check(lib().zj_decode_crops_resized_device(*args, d_out, stream), "zj_decode_crops_resized_device", self._h)
+
+    def decode_crops_resized_mixed_device(self, descs, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out,
+                                          scale=None, bias=None, flips=None, stream=None, antialias=False, max_prescale=1,
+                                          orientations=None, interpolation="bilinear"):
+        """Resized crop windows of frames of MIXED geometry (zj_decode_crops_resized_mixed_device): descs = one FrameDesc
+        per frame (sizes, sampling, tables, flags and in_components their own; out_colorspace and out_layout the same in
+        all); the other arguments as decode_crops_resized_device.  Image f equals that call's for frame f alone.
+        Asynchronous on `stream`."""
+        filt = resize_filter(antialias, interpolation)
+        n = len(d_y)
+        if len(descs) != n or len(windows) != n or (orientations is not None and len(orientations) != n):
+            raise ValueError("one descriptor, window (and orientation) per frame")
+        arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
+        win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
+        ori = (C.c_uint8 * n)(*[int(o) for o in orientations]) if orientations is not None else None
+        _check(lib().zj_decode_crops_resized_mixed_device(self._h, (FrameDesc * n)(*descs), n, arr(d_y), arr(d_cb), arr(d_cr), win,
+                                                          out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
+                                                          _flips(flips, n), filt, scale_log2(max_prescale), ori, d_out, stream),
+               "zj_decode_crops_resized_mixed_device", self._h)
 
     def decode_crops_scaled_device(self, desc, d_y, d_cb, d_cr, scale, d_out, windows=None, out_pitch=0, stream=None):
         """Reduced-size decode (zj_decode_crops_scaled_device): the frames at 1/scale (2, 4 or 8), pointers as in
@@ -1044,6 +1069,28 @@ def finish_pixels_batch(decoders, ctx, outs=None, device_ptrs=None):
     if device_ptrs is not None:
         return list(lens), list(rcs)
     return [o[: lens[k]] for k, o in enumerate(outs)], list(rcs)
+
+
+def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
+                                     flips=None, antialias=False, max_prescale=1, apply_orientation=False,
+                                     interpolation="bilinear"):
+    """zj_decoder_finish_pixels_resized_crop_batch_device over Decoder objects that went through prepare() or
+    decode_coefficients(), each with a file of its own size: windows = one (x, y, w, h) per decoder (displayed pixels with
+    apply_orientation), image k left at device pointer d_out + k * resized_out_len.  Returns the list of statuses: image k
+    is Decoder.finish_pixels_resized_crop_device's for decoder k alone, a failed file's slot is untouched."""
+    filt = resize_filter(antialias, interpolation)
+    n = len(decoders)
+    if len(windows) != n:
+        raise ValueError("one window per decoder")
+    dptr = (C.c_void_p * n)(*[d._d for d in decoders])
+    win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
+    rcs = (C.c_int * n)()
+    _check(lib().zj_decoder_finish_pixels_resized_crop_batch_device(dptr, n, ctx.handle, win, out_w, out_h, dtype, out_layout,
+                                                                    _floats(scale), _floats(bias), _flips(flips, n), filt,
+                                                                    scale_log2(max_prescale), 1 if apply_orientation else 0,
+                                                                    d_out, cap, rcs),
+           "zj_decoder_finish_pixels_resized_crop_batch_device", ctx.handle)
+    return list(rcs)
 
 
 class FileBatchDecoder:

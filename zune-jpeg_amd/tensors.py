@@ -195,6 +195,78 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     return out
 
 
+def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
+                                   antialias=False, interpolation="bilinear", max_prescale=1, apply_orientation=False,
+                                   options=None, workers=1, stream=None, decoders=None):
+    """JPEG files of ANY sizes -> ONE dense resized-crop tensor (zj_decoder_finish_pixels_resized_crop_batch_device,
+    DESIGN.md 3.10): blobs = a list of bytes-like JPEG files, windows = one (x, y, w, h) per file (displayed pixels with
+    apply_orientation; None, or None in a file's place: the whole displayed image), size = (out_w, out_h).  Returns
+    [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C] ("NHWC") of `dtype` (default bfloat16); image k is
+    Decoder.finish_pixels_resized_crop_device's for file k alone.  The other keywords as decode_resized_crops_to_tensor.
+    options: ZuneJpegOptions of the decoders (None: the defaults).  workers: threads that prepare the files (headers and
+    the CPU entropy stage; the library calls release the GIL), at most 16.  decoders: a list to keep between calls --
+    Decoder objects are made as needed, appended to it and reused.  A file that fails raises DecodeError naming its index.
+    The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
+    the stream the output is allocated under, synchronised before the call writes it."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from .host import DecodeError, Decoder, finish_pixels_resized_crop_batch, oriented_size, resize_filter, scale_log2
+    scale_log2(max_prescale)
+    resize_filter(antialias, interpolation)
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(blobs)
+    if n == 0 or (windows is not None and len(windows) != n):
+        raise ValueError("one window per file, at least one file")
+    decs = decoders if decoders is not None else []
+    while len(decs) < n:
+        decs.append(Decoder(options, ctx))
+    decs = decs[:n]
+
+    def prep(k):
+        try:
+            return decs[k].prepare(blobs[k])
+        except DecodeError as e:
+            return e
+
+    nw = max(1, min(int(workers), 16, n))
+    if nw > 1:
+        with ThreadPoolExecutor(nw) as ex:
+            prepared = list(ex.map(prep, range(n)))
+    else:
+        prepared = [prep(k) for k in range(n)]
+    for k, r in enumerate(prepared):
+        if isinstance(r, DecodeError):
+            raise DecodeError(r.status, f"file {k}: {r.text}")
+    wins = []
+    for k in range(n):
+        w = windows[k] if windows is not None else None
+        if w is None:
+            info = prepared[k][1]
+            iw, ih = int(info.width), int(info.height)
+            if apply_orientation:
+                iw, ih = oriented_size(decs[k].orientation, iw, ih)
+            w = (0, 0, iw, ih)
+        wins.append(w)
+    channels = ColorSpace(decs[0]._out_cs).num_components()
+    if channels not in (1, 3):
+        raise ValueError("resized outputs have 1 or 3 channels")
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    s.synchronize()  # (the allocator may hand out a block that work queued on `s` still uses: the batch runs on the context's stream)
+    rcs = finish_pixels_resized_crop_batch(decs, ctx, wins, size[0], size[1], code,
+                                           TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(),
+                                           out.numel() * out.element_size(), scale, bias, flips, antialias, max_prescale,
+                                           apply_orientation, interpolation)
+    for k, rc in enumerate(rcs):
+        if rc:
+            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+    return out
+
+
 def decode_scaled_to_tensor(ctx, desc, frames, scale, windows=None, stream=None):
     """Frames decoded at 1/scale (2, 4 or 8) as one dense uint8 tensor (zj_decode_crops_scaled_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output); windows = None (the whole
