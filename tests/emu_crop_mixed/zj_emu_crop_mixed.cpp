@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../zune-jpeg_amd/csrc/zj_mixed.h"
+#include "../../zune-jpeg_amd/csrc/zj_rzgroup.h"
 
 using namespace zj;
 
@@ -151,20 +152,15 @@ static int dispatch_scaled(const MixedLaunch& l, const uint8_t* tab, uint8_t poi
     return ZJ_ERR_UNSUPPORTED;
 }
 
-// the frame checks of zj_decode_crops_resized_mixed_device, all frames before anything runs (orientation: nullptr = none)
+// the frame checks of zj_decode_crops_resized_mixed_device (zj_mixed.h: mixed_check_frames; no planes here to check)
 static int plan_all(const zj_frame_desc* descs, size_t n, const unsigned* windows, unsigned out_w, unsigned out_h, int max_k,
                     const uint8_t* orientation, std::vector<MixedFrame>& fr)
 {
     if (!descs || !windows || n == 0 || max_k < 0 || max_k > 3) return ZJ_ERR_ARG;
-    if (!mixed_descs_agree(descs, n)) return ZJ_ERR_ARG;
     fr.resize(n);
-    for (size_t f = 0; f < n; f++) {
-        int rc = mixed_frame_plan(&descs[f], windows + 4 * f, orientation ? (orientation[f] ? orientation[f] : -1) : 0, fr[f]);
-        if (rc) return rc;
-        if (!resized_len(resize_channels(&descs[f]), out_w, out_h, ZJ_DTYPE_U8)) return ZJ_ERR_ARG;
-        if ((rc = mixed_frame_window(&descs[f], windows + 4 * f, out_w, out_h, max_k, fr[f]))) return rc;
-    }
-    return ZJ_OK;
+    const int out_rc = resized_len(resize_channels(&descs[0]), out_w, out_h, ZJ_DTYPE_U8) ? ZJ_OK : ZJ_ERR_ARG;
+    return mixed_check_frames(descs, n, windows, orientation, out_rc, out_w, out_h, max_k, [](size_t, bool) { return (int)ZJ_OK; },
+                              fr.data());
 }
 
 // The plan alone: status, and per frame info[6f ..] = scale k, the crop-stage window x, y, w, h, the orientation
@@ -203,6 +199,33 @@ extern "C" int zjem_crops(const zj_frame_desc* descs, size_t n, const int16_t* c
         if ((rc = dispatch_scaled(l, tab, (uint8_t)poison))) return rc;
     if (counts) { counts[0] = (int)t.crop.size(); counts[1] = (int)t.scaled.size(); counts[2] = t.zero.n ? 1 : 0; }
     return ZJ_OK;
+}
+
+// The library's group planner (zj_rzgroup.h) over n frames of wh[2f], wh[2f + 1] and orientation o[f] at `cap` (0: the
+// library's RZ_GROUP_CAP).  Returns the scratch bytes of the call; group[f]: the index of frame f's group; place[8f ..]: the
+// crop's offset, w, h, pitch, then the same of the image the resize reads; gbytes[g]: group g's bytes (n entries).
+extern "C" size_t zjem_rz_groups(const unsigned* wh, const uint8_t* o, size_t n, int channels, int chw, size_t cap, int* group,
+                                 unsigned long long* place, unsigned long long* gbytes)
+{
+    if (!cap) cap = RZ_GROUP_CAP;
+    std::vector<RzFrame> fr(n);
+    for (size_t f = 0; f < n; f++) fr[f] = RzFrame{wh[2 * f], wh[2 * f + 1], o[f]};
+    std::vector<RzPlace> pl(n);
+    size_t g = 0;
+    for (size_t g0 = 0, g1; g0 < n; g0 = g1, g++) {
+        size_t bytes = 0;
+        g1 = rz_group_next(fr.data(), n, g0, channels, chw != 0, cap, pl.data(), &bytes);
+        gbytes[g] = bytes;
+        for (size_t f = g0; f < g1; f++) {
+            group[f] = (int)g;
+            const RzImage im[2] = {pl[f].crop, pl[f].in};
+            for (int k = 0; k < 2; k++) {
+                place[8 * f + 4 * k] = im[k].off; place[8 * f + 4 * k + 1] = im[k].w;
+                place[8 * f + 4 * k + 2] = im[k].h; place[8 * f + 4 * k + 3] = im[k].pitch;
+            }
+        }
+    }
+    return rz_scratch_need(fr.data(), n, channels, chw != 0, cap);
 }
 
 extern "C" size_t zjem_record_bytes(int which) { return which == 0 ? sizeof(CropParams) : which == 1 ? sizeof(ScaledParams) : sizeof(MixedZero); }

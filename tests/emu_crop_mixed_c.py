@@ -20,10 +20,11 @@ def lib():
         so = os.path.join(HERE, "emu_crop_mixed", "libzjemucropmixed.so")
         csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
         srcs = [os.path.join(HERE, "emu_crop_mixed", "zj_emu_crop_mixed.cpp")] + \
-            [os.path.join(csrc, h) for h in ("zj_mixed.h", "zj_device.h", "zj_scaled.h", "zj_plan.h", "zj_geom.h")]
+            [os.path.join(csrc, h) for h in ("zj_mixed.h", "zj_rzgroup.h", "zj_device.h", "zj_scaled.h", "zj_plan.h", "zj_geom.h")]
         emu_build.build(so, srcs, "-O1")
         _LIB = C.CDLL(so)
         _LIB.zjem_record_bytes.restype = C.c_size_t
+        _LIB.zjem_rz_groups.restype = C.c_size_t
     return _LIB
 
 
@@ -66,3 +67,19 @@ def crops(descs, frames, windows, out_w, out_h, max_k=0, orientations=None, pois
     for b, ln in zip(bufs, lens):
         assert (b[:guard] == poison).all() and (b[guard + ln:] == poison).all(), "a crop wrote outside its bytes"
     return rc, [b[guard:guard + ln] for b, ln in zip(bufs, lens)], pl, tuple(counts)
+
+
+def rz_groups(sizes, orientations, channels, chw, cap=0):
+    """The library's group planner (zj_rzgroup.h) over crops of sizes[f] = (w, h) and orientations[f] at `cap` bytes (0: the
+    library's RZ_GROUP_CAP).  Returns (need, groups): need = the scratch bytes of the call; groups = a list of (bytes, frames),
+    frames = a list of (f, crop, read) with crop / read = (offset, w, h, pitch) of the crop and of the image the resize reads."""
+    n = len(sizes)
+    wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+    ori = (C.c_uint8 * n)(*[int(o) for o in orientations])
+    group, place, gbytes = (C.c_int * n)(), (C.c_ulonglong * (8 * n))(), (C.c_ulonglong * n)()
+    need = lib().zjem_rz_groups(wh, ori, C.c_size_t(n), C.c_int(channels), C.c_int(1 if chw else 0), C.c_size_t(cap), group, place,
+                                gbytes)
+    groups = [(int(gbytes[g]), []) for g in range(group[n - 1] + 1)] if n else []
+    for f in range(n):
+        groups[group[f]][1].append((f, tuple(place[8 * f:8 * f + 4]), tuple(place[8 * f + 4:8 * f + 8])))
+    return need, groups

@@ -18,6 +18,7 @@
 #include "zj_orient_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
+#include "zj_rzgroup.h"
 #include "zj_scaled_launch.h"
 
 using namespace zj;
@@ -814,43 +815,67 @@ int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy,
 
 /* ---- resize + normalise ---------------------------------------------------------- */
 namespace {
-constexpr size_t RZ_GROUP_CAP = (size_t)256 << 20; // u8 crop bytes per launch group of zj_decode_crops_resized_device
-
 bool finite_f32(float v) { return v - v == 0.f; }
 
-// the output's arguments; s[] / b[]: the per-channel factors of the kernel (s_c = scale_c * 2^-16)
-int resize_out_args(unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
-                    int channels, float s[3], float b[3])
+// The output side of a resized call, as every layer below the entry points takes it: the dense tensor at d_out, image i of
+// the call at d_out + i * img_bytes, flipped if flip[i] (nullptr: none).
+struct ResizeOut {
+    unsigned out_w, out_h;
+    int dtype, layout;          // ZJ_DTYPE_*, ZJ_TENSOR_*
+    const float *scale, *bias;  // the caller's (nullptr: 1, 0)
+    const uint8_t* flip;
+    int filter;
+    uint8_t* d_out;
+    // resize_out_args:
+    int ch;                     // channels of the u8 images
+    float s[3], b[3];           // the per-channel factors of the kernel (s_c = scale_c * 2^-16)
+    size_t img_bytes;           // of one image of the output
+    bool chw;                   // the u8 images are CHW planes (the caller's to set)
+};
+
+ResizeOut resize_out(unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                     const uint8_t* flip, int filter, void* d_out)
 {
-    if (!resized_len(channels, out_w, out_h, dtype)) return ZJ_ERR_ARG; // (the size or the dtype)
-    if (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC) return ZJ_ERR_ARG;
+    ResizeOut o{};
+    o.out_w = out_w; o.out_h = out_h; o.dtype = dtype; o.layout = out_layout;
+    o.scale = scale; o.bias = bias; o.flip = flip; o.filter = filter; o.d_out = (uint8_t*)d_out;
+    return o;
+}
+
+// the check of the output's arguments, for u8 images of `channels`
+int resize_out_args(ResizeOut& o, int channels)
+{
+    o.ch = channels;
+    o.img_bytes = resized_len(channels, o.out_w, o.out_h, o.dtype);
+    if (!o.img_bytes) return ZJ_ERR_ARG; // (the size or the dtype)
+    if (o.layout != ZJ_TENSOR_NCHW && o.layout != ZJ_TENSOR_NHWC) return ZJ_ERR_ARG;
     for (int k = 0; k < 3; k++) {
-        const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
+        const float sc = o.scale && k < channels ? o.scale[k] : 1.f, bi = o.bias && k < channels ? o.bias[k] : 0.f;
         if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
-        s[k] = sc * (1.f / 65536.f); // (exact: a power of two, above float32's smallest normal for every |scale| >= 2^-110)
-        b[k] = bi;
+        o.s[k] = sc * (1.f / 65536.f); // (exact: a power of two, above float32's smallest normal for every |scale| >= 2^-110)
+        o.b[k] = bi;
     }
     return ZJ_OK;
 }
 
-// images [0, n) -> the dense tensor at out, launches of up to RESIZE_BATCH images; wh[2i], wh[2i + 1]: image i's size,
-// pitch[i] (bytes between its rows) already resolved
-int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, int channels,
-                    int in_chw, unsigned out_w, unsigned out_h, int dtype, int nhwc, const float s[3], const float b[3],
-                    const uint8_t* flip, int filter, uint8_t* out, hipStream_t st)
+// images [0, n) -> images [first, first + n) of the output, launches of up to RESIZE_BATCH images; wh[2i], wh[2i + 1]: image
+// i's size, pitch[i] (bytes between its rows) already resolved
+int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const ResizeOut& o,
+                    size_t first, hipStream_t st)
 {
-    const size_t img_bytes = resized_len(channels, out_w, out_h, dtype);
+    const uint8_t* const flip = o.flip ? o.flip + first : nullptr;
+    const int nhwc = o.layout == ZJ_TENSOR_NHWC;
     ResizeParams p{};
-    p.out_w = (int)out_w; p.out_h = (int)out_h;
-    for (int k = 0; k < 3; k++) { p.scale[k] = s[k]; p.bias[k] = b[k]; }
-    p.groups = (int)((out_w + RESIZE_GROUP - 1) / RESIZE_GROUP);
+    p.out_w = (int)o.out_w; p.out_h = (int)o.out_h;
+    for (int k = 0; k < 3; k++) { p.scale[k] = o.s[k]; p.bias[k] = o.b[k]; }
+    p.groups = (int)((o.out_w + RESIZE_GROUP - 1) / RESIZE_GROUP);
     p.rows = RESIZE_ITEMS / p.groups;
     if (p.rows < 1) p.rows = 1;
-    if (p.rows > (int)out_h) p.rows = (int)out_h;
+    if (p.rows > (int)o.out_h) p.rows = (int)o.out_h;
     for (size_t f0 = 0; f0 < n; f0 += RESIZE_BATCH) {
         const int m = (int)(n - f0 < (size_t)RESIZE_BATCH ? n - f0 : (size_t)RESIZE_BATCH);
         p.nimg = m;
-        p.out = (uint64_t)(uintptr_t)(out + f0 * img_bytes);
+        p.out = (uint64_t)(uintptr_t)(o.d_out + (first + f0) * o.img_bytes);
         for (int k = 0; k < RESIZE_BATCH / 32; k++) p.flip[k] = 0;
         for (int i = 0; i < RESIZE_BATCH; i++) {
             const size_t f = f0 + i;
@@ -859,9 +884,9 @@ int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
             p.pitch[i] = i < m ? pitch[f] : 0;
             if (i < m && flip && flip[f]) p.flip[i >> 5] |= 1u << (i & 31);
         }
-        ZJ_HIP(c, filter == ZJ_RESIZE_BICUBIC_AA    ? launch_resize_bicubic(channels, in_chw, dtype, nhwc, p, st)
-                  : filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(channels, in_chw, dtype, nhwc, p, st)
-                                                    : launch_resize(channels, in_chw, dtype, nhwc, p, st));
+        ZJ_HIP(c, o.filter == ZJ_RESIZE_BICUBIC_AA    ? launch_resize_bicubic(o.ch, o.chw, o.dtype, nhwc, p, st)
+                  : o.filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(o.ch, o.chw, o.dtype, nhwc, p, st)
+                                                      : launch_resize(o.ch, o.chw, o.dtype, nhwc, p, st));
     }
     return ZJ_OK;
 }
@@ -891,13 +916,6 @@ int resize_scratch_done(zj_ctx* c, hipStream_t st)
     return ZJ_OK;
 }
 
-size_t crop_bytes(unsigned w, unsigned h, int channels) { return ((size_t)w * h * channels + 15) & ~(size_t)15; }
-
-bool known_filter(int filter)
-{
-    return filter == ZJ_RESIZE_BILINEAR || filter == ZJ_RESIZE_BILINEAR_AA || filter == ZJ_RESIZE_BICUBIC_AA;
-}
-
 // images [0, n) -> their displayed form, launches of up to ORIENT_BATCH images; wh: STORED w, h pairs, the
 // pitches resolved, every o[i] 1..8
 int orient_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int channels,
@@ -919,6 +937,36 @@ int orient_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
         ZJ_HIP(c, launch_orient(channels, in_chw, p, st));
     }
     return ZJ_OK;
+}
+
+// The end of the launch group [g0, g1) of a resized call, its crops written into buf where `place` says (zj_rzgroup.h):
+// the turned frames, gathered: crop -> its displayed form, tight, in the second region; the resize over the images place[f].in
+// names, in order, into images [g0, g1) of the output; the event that orders the buffer's reuse.
+int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g0, size_t g1, uint8_t* buf, const ResizeOut& o,
+                    hipStream_t st)
+{
+    const size_t ng = g1 - g0;
+    std::vector<const uint8_t*> in(ng), oin;
+    std::vector<unsigned> wh(2 * ng), pitch(ng), owh, oip, oop;
+    std::vector<uint8_t*> oout;
+    std::vector<uint8_t> oo;
+    for (size_t f = g0; f < g1; f++) {
+        const RzPlace& p = place[f];
+        in[f - g0] = buf + p.in.off;
+        wh[2 * (f - g0)] = p.in.w; wh[2 * (f - g0) + 1] = p.in.h;
+        pitch[f - g0] = p.in.pitch;
+        if (!p.turned) continue;
+        oin.push_back(buf + p.crop.off); oout.push_back(buf + p.in.off);
+        owh.push_back(p.crop.w); owh.push_back(p.crop.h);
+        oip.push_back(p.crop.pitch); oop.push_back(p.in.pitch);
+        oo.push_back((uint8_t)fr[f].o);
+    }
+    int rc;
+    if (!oin.empty() && (rc = orient_launches(c, oin.size(), oin.data(), owh.data(), oip.data(), o.ch, o.chw, oo.data(), oout.data(),
+                                              oop.data(), st)))
+        return rc;
+    if ((rc = resize_launches(c, ng, in.data(), wh.data(), pitch.data(), o, g0, st))) return rc;
+    return resize_scratch_done(c, st);
 }
 } // namespace
 
@@ -945,14 +993,14 @@ int zj_resize_filtered_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, c
                               const float* scale, const float* bias, const uint8_t* flip, int filter, void* d_out,
                               void* stream)
 {
-    if (!known_filter(filter)) return ZJ_ERR_ARG;
+    if (!resize_filter_valid(filter)) return ZJ_ERR_ARG;
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
     if (channels != 1 && channels != 3) return ZJ_ERR_ARG;
     if (in_layout != ZJ_LAYOUT_HWC && in_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
-    float s[3], b[3];
-    int rc = resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, channels, s, b);
+    ResizeOut ro = resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
+    int rc = resize_out_args(ro, channels);
     if (rc) return rc;
-    const bool chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
+    const bool chw = ro.chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
     std::vector<unsigned> pitch(n);
     for (size_t f = 0; f < n; f++) {
         const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
@@ -964,8 +1012,7 @@ int zj_resize_filtered_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, c
     }
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    return resize_launches(c, n, d_in, in_wh, pitch.data(), channels, chw, out_w, out_h, dtype, out_layout == ZJ_TENSOR_NHWC,
-                           s, b, flip, filter, (uint8_t*)d_out, st);
+    return resize_launches(c, n, d_in, in_wh, pitch.data(), ro, 0, st);
 }
 
 int zj_decode_crops_resized_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
@@ -1021,13 +1068,11 @@ int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, s
 // frames with o != 1 are then turned into a second region of the buffer, behind the group's crops, and the resize reads
 // those.  The scale is picked from the displayed window's sides, the ones the resize sees.
 static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
-                              const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
-                              unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
-                              const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
-                              const uint8_t* orientation, void* d_out, void* stream)
+                              const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows, ResizeOut ro,
+                              int max_prescale_log2, const uint8_t* orientation, void* stream)
 {
-    if (!known_filter(filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
-    if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
+    if (!resize_filter_valid(ro.filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
+    if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
     const unsigned* const shown = windows; // the caller's windows: displayed pixels
     std::vector<unsigned> stored_store;
     if (orientation) {
@@ -1043,8 +1088,7 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
     CropPlan cp;
     int rc = make_crop_plan(d, 1, 1, 0, pl, cp);
     if (rc) return rc;
-    float s[3], b[3];
-    if ((rc = resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, ch, s, b))) return rc;
+    if ((rc = resize_out_args(ro, ch))) return rc;
     const bool chroma = pl.out != OUT_GRAY;
     if ((rc = check_plane_ptrs(d_y, d_cb, d_cr, chroma, nframes))) return rc;
     for (size_t f = 0; f < nframes; f++) {
@@ -1058,8 +1102,7 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
     }
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const bool chw = pl.out == OUT_RGB_CHW;
-    const size_t img_bytes = resized_len(ch, out_w, out_h, dtype);
+    const bool chw = ro.chw = pl.out == OUT_RGB_CHW;
     // per image: its scale and the window the crop stage decodes (scale 1: the window itself)
     std::vector<unsigned> cwin_store;
     std::vector<int> klog;
@@ -1073,37 +1116,22 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
     if (max_prescale_log2 > 0)
         for (size_t f = 0; f < nframes; f++) {
             const unsigned* w = windows + 4 * f;
-            klog[f] = prescale_pick(shown[4 * f + 2], shown[4 * f + 3], out_w, out_h, max_prescale_log2);
+            klog[f] = prescale_pick(shown[4 * f + 2], shown[4 * f + 3], ro.out_w, ro.out_h, max_prescale_log2);
             if (klog[f]) prescale_window(w, klog[f], d->width, d->height, cwin_w + 4 * f);
         }
-    // launch groups: frames whose crops fit RZ_GROUP_CAP together (a larger window alone); the buffer sized for the largest
-    // (a frame that is turned takes its crop's bytes twice: the crop and, in the second region, its displayed form)
-    const auto turned = [&](size_t f) { return orientation && orientation[f] != 1; };
-    size_t need = 0;
-    for (size_t f = 0, g = 0; f < nframes; f++) {
-        const size_t cb = crop_bytes(cwin[4 * f + 2], cwin[4 * f + 3], ch) * (turned(f) ? 2 : 1);
-        g = g && g + cb > RZ_GROUP_CAP ? cb : g + cb;
-        if (g > need) need = g;
-    }
+    // launch groups (zj_rzgroup.h): frames whose crops fit RZ_GROUP_CAP together, the buffer sized for the largest
+    std::vector<RzFrame> rzf(nframes);
+    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{cwin[4 * f + 2], cwin[4 * f + 3], orientation ? orientation[f] : 1};
     uint8_t* buf = nullptr;
-    if ((rc = resize_scratch(c, need, st, &buf))) return rc;
+    if ((rc = resize_scratch(c, rz_scratch_need(rzf.data(), nframes, ch, chw, RZ_GROUP_CAP), st, &buf))) return rc;
+    std::vector<RzPlace> place(nframes);
     std::vector<uint8_t*> crops(nframes);
-    std::vector<unsigned> pitch(nframes), wh(2 * nframes);
     std::vector<const int16_t*> gy, gcb, gcr; // the frames of one scale of a group, gathered
     std::vector<uint8_t*> gout;
     std::vector<unsigned> gwin;
-    for (size_t g0 = 0; g0 < nframes;) {
-        size_t g1 = g0, off = 0, off2 = 0; // off2: bytes of the second region, the displayed forms
-        while (g1 < nframes) {
-            const size_t cb = crop_bytes(cwin[4 * g1 + 2], cwin[4 * g1 + 3], ch);
-            if (g1 > g0 && off + off2 + cb * (turned(g1) ? 2 : 1) > RZ_GROUP_CAP) break;
-            crops[g1] = buf + off;
-            pitch[g1] = cwin[4 * g1 + 2] * (chw ? 1 : ch);
-            wh[2 * g1] = cwin[4 * g1 + 2]; wh[2 * g1 + 1] = cwin[4 * g1 + 3];
-            off += cb;
-            if (turned(g1)) off2 += cb;
-            g1++;
-        }
+    for (size_t g0 = 0, g1, bytes; g0 < nframes; g0 = g1) {
+        g1 = rz_group_next(rzf.data(), nframes, g0, ch, chw, RZ_GROUP_CAP, place.data(), &bytes);
+        for (size_t f = g0; f < g1; f++) crops[f] = buf + place[f].crop.off;
         // the crops of the group, each tight at its own size (CropParams.out_pitch 0); the group before it has been read by
         // then (the same stream)
         for (int k = 0; k <= max_prescale_log2; k++) {
@@ -1129,37 +1157,7 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
                             : decode_crops_impl(c, d, pl, cp, ng, py, pcb, pcr, pwin, 4, pout, st)))
                 return rc;
         }
-        if (off2) {
-            // the turned frames of the group, gathered: crop -> its displayed form, tight, at off + its place in the second
-            // region; the resize then reads that image at its displayed size
-            std::vector<const uint8_t*> oin;
-            std::vector<uint8_t*> oout;
-            std::vector<unsigned> owh, oip, oop;
-            std::vector<uint8_t> oo;
-            size_t at = off;
-            for (size_t f = g0; f < g1; f++) {
-                if (!turned(f)) continue;
-                unsigned dw = 0, dh = 0;
-                orient_size(orientation[f], wh[2 * f], wh[2 * f + 1], &dw, &dh);
-                oin.push_back(crops[f]); oout.push_back(buf + at);
-                owh.push_back(wh[2 * f]); owh.push_back(wh[2 * f + 1]);
-                oip.push_back(pitch[f]); oop.push_back(dw * (chw ? 1 : ch));
-                oo.push_back(orientation[f]);
-                crops[f] = buf + at;
-                wh[2 * f] = dw; wh[2 * f + 1] = dh;
-                pitch[f] = dw * (chw ? 1 : ch);
-                at += crop_bytes(dw, dh, ch);
-            }
-            if ((rc = orient_launches(c, oin.size(), oin.data(), owh.data(), oip.data(), ch, chw, oo.data(), oout.data(),
-                                      oop.data(), st)))
-                return rc;
-        }
-        if ((rc = resize_launches(c, g1 - g0, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h,
-                                  dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
-                                  (uint8_t*)d_out + g0 * img_bytes, st)))
-            return rc;
-        if ((rc = resize_scratch_done(c, st))) return rc;
-        g0 = g1;
+        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st))) return rc;
     }
     return ZJ_OK;
 }
@@ -1170,8 +1168,8 @@ int zj_decode_crops_resized_prescaled_device(zj_ctx* c, const zj_frame_desc* d, 
                                              const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
                                              void* d_out, void* stream)
 {
-    return crops_resized_impl(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter,
-                              max_prescale_log2, nullptr, d_out, stream);
+    return zj_decode_crops_resized_oriented_device(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, scale,
+                                                   bias, flip, filter, max_prescale_log2, nullptr, d_out, stream);
 }
 
 /* ---- EXIF orientation ----------------------------------------------------------- */
@@ -1181,11 +1179,9 @@ int zj_decode_crops_resized_oriented_device(zj_ctx* c, const zj_frame_desc* d, s
                                             const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
                                             const uint8_t* orientation, void* d_out, void* stream)
 {
-    if (!orientation)
-        return zj_decode_crops_resized_prescaled_device(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout,
-                                                        scale, bias, flip, filter, max_prescale_log2, d_out, stream);
-    return crops_resized_impl(c, d, nframes, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter,
-                              max_prescale_log2, orientation, d_out, stream);
+    return crops_resized_impl(c, d, nframes, d_y, d_cb, d_cr, windows,
+                              resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out), max_prescale_log2,
+                              orientation, stream);
 }
 
 /* ---- mixed-geometry resized crops ----------------------------------------------- */
@@ -1216,60 +1212,35 @@ int mixed_tables(zj_ctx* c, size_t bytes)
 // stay as they are until the stream has run: the caller synchronises).  Otherwise they are device planes.
 int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
                              const int16_t* const* d_cb, const int16_t* const* d_cr, bool host_planes, const unsigned* windows,
-                             unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
-                             const uint8_t* flip, int filter, int max_prescale_log2, const uint8_t* orientation, void* d_out,
-                             void* stream)
+                             ResizeOut ro, int max_prescale_log2, const uint8_t* orientation, void* stream)
 {
-    if (!known_filter(filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
-    if (!c || !descs || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
-    if (!mixed_descs_agree(descs, nframes)) return ZJ_ERR_ARG;
+    if (!resize_filter_valid(ro.filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
+    if (!c || !descs || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
     // every frame's checks, in the one-geometry call's order, before anything is launched
     std::vector<MixedFrame> fr(nframes);
-    float s[3], b[3];
     const int ch = resize_channels(&descs[0]);
-    const int out_rc = ch ? resize_out_args(out_w, out_h, dtype, out_layout, scale, bias, ch, s, b) : 0;
-    for (size_t f = 0; f < nframes; f++) {
-        const zj_frame_desc* const d = &descs[f];
-        int rc = mixed_frame_plan(d, windows + 4 * f, orientation ? (orientation[f] ? orientation[f] : -1) : 0, fr[f]);
-        if (rc) return rc;
-        if (out_rc) return out_rc;
-        const bool chroma = fr[f].pl.out != OUT_GRAY;
-        if (chroma && (!d_cb || !d_cr)) return ZJ_ERR_ARG;
-        if ((rc = check_plane_ptrs(d_y + f, chroma ? d_cb + f : nullptr, chroma ? d_cr + f : nullptr, chroma, 1))) return rc;
-        if ((rc = mixed_frame_window(d, windows + 4 * f, out_w, out_h, max_prescale_log2, fr[f]))) return rc;
-    }
+    const auto planes = [&](size_t f, bool chroma) {
+        if (chroma && (!d_cb || !d_cr)) return (int)ZJ_ERR_ARG;
+        return check_plane_ptrs(d_y + f, chroma ? d_cb + f : nullptr, chroma ? d_cr + f : nullptr, chroma, 1);
+    };
+    int rc = mixed_check_frames(descs, nframes, windows, orientation, ch ? resize_out_args(ro, ch) : 0, ro.out_w, ro.out_h,
+                                max_prescale_log2, planes, fr.data());
+    if (rc) return rc;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const bool chw = fr[0].pl.out == OUT_RGB_CHW;
-    const size_t img_bytes = resized_len(ch, out_w, out_h, dtype);
-    // launch groups as crops_resized_impl forms them
-    const auto turned = [&](size_t f) { return fr[f].o != 1; };
-    const auto cbytes = [&](size_t f) { return crop_bytes(fr[f].cwin[2], fr[f].cwin[3], ch); };
-    size_t need = 0;
-    for (size_t f = 0, g = 0; f < nframes; f++) {
-        const size_t cb = cbytes(f) * (turned(f) ? 2 : 1);
-        g = g && g + cb > RZ_GROUP_CAP ? cb : g + cb;
-        if (g > need) need = g;
-    }
+    const bool chw = ro.chw = fr[0].pl.out == OUT_RGB_CHW;
+    // launch groups (zj_rzgroup.h), as the one-geometry call's
+    std::vector<RzFrame> rzf(nframes);
+    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{fr[f].cwin[2], fr[f].cwin[3], fr[f].o};
     uint8_t* buf = nullptr;
-    int rc;
-    if ((rc = resize_scratch(c, need, st, &buf))) return rc;
+    if ((rc = resize_scratch(c, rz_scratch_need(rzf.data(), nframes, ch, chw, RZ_GROUP_CAP), st, &buf))) return rc;
+    std::vector<RzPlace> place(nframes);
     std::vector<uint8_t*> crops(nframes);
-    std::vector<unsigned> pitch(nframes), wh(2 * nframes);
     std::vector<const int16_t*> py(nframes), pcb(nframes), pcr(nframes);
     MixedTables tabs;
-    for (size_t g0 = 0; g0 < nframes;) {
-        size_t g1 = g0, off = 0, off2 = 0;
-        while (g1 < nframes) {
-            const size_t cb = cbytes(g1);
-            if (g1 > g0 && off + off2 + cb * (turned(g1) ? 2 : 1) > RZ_GROUP_CAP) break;
-            crops[g1] = buf + off;
-            pitch[g1] = fr[g1].cwin[2] * (chw ? 1 : ch);
-            wh[2 * g1] = fr[g1].cwin[2]; wh[2 * g1 + 1] = fr[g1].cwin[3];
-            off += cb;
-            if (turned(g1)) off2 += cb;
-            g1++;
-        }
+    for (size_t g0 = 0, g1, bytes; g0 < nframes; g0 = g1) {
+        g1 = rz_group_next(rzf.data(), nframes, g0, ch, chw, RZ_GROUP_CAP, place.data(), &bytes);
+        for (size_t f = g0; f < g1; f++) crops[f] = buf + place[f].crop.off;
         const size_t ng = g1 - g0;
         // (first: it waits until the copies out of the pinned staging, the planes' and the tables', have finished)
         if ((rc = mixed_tables(c, mixed_table_bytes(fr.data() + g0, ng)))) return rc;
@@ -1337,35 +1308,7 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
         // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
         (void)hipEventRecord(c->mx_done, st);
         ZJ_HIP(c, e);
-        if (off2) { // the turned frames: crop -> its displayed form in the second region (crops_resized_impl)
-            std::vector<const uint8_t*> oin;
-            std::vector<uint8_t*> oout;
-            std::vector<unsigned> owh, oip, oop;
-            std::vector<uint8_t> oo;
-            size_t at = off;
-            for (size_t f = g0; f < g1; f++) {
-                if (!turned(f)) continue;
-                unsigned dw = 0, dh = 0;
-                orient_size(fr[f].o, wh[2 * f], wh[2 * f + 1], &dw, &dh);
-                oin.push_back(crops[f]); oout.push_back(buf + at);
-                owh.push_back(wh[2 * f]); owh.push_back(wh[2 * f + 1]);
-                oip.push_back(pitch[f]); oop.push_back(dw * (chw ? 1 : ch));
-                oo.push_back((uint8_t)fr[f].o);
-                crops[f] = buf + at;
-                wh[2 * f] = dw; wh[2 * f + 1] = dh;
-                pitch[f] = dw * (chw ? 1 : ch);
-                at += crop_bytes(dw, dh, ch);
-            }
-            if ((rc = orient_launches(c, oin.size(), oin.data(), owh.data(), oip.data(), ch, chw, oo.data(), oout.data(),
-                                      oop.data(), st)))
-                return rc;
-        }
-        if ((rc = resize_launches(c, ng, crops.data() + g0, wh.data() + 2 * g0, pitch.data() + g0, ch, chw, out_w, out_h, dtype,
-                                  out_layout == ZJ_TENSOR_NHWC, s, b, flip ? flip + g0 : nullptr, filter,
-                                  (uint8_t*)d_out + g0 * img_bytes, st)))
-            return rc;
-        if ((rc = resize_scratch_done(c, st))) return rc;
-        g0 = g1;
+        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st))) return rc;
     }
     return ZJ_OK;
 }
@@ -1377,8 +1320,9 @@ int zj_decode_crops_resized_mixed_device(zj_ctx* c, const zj_frame_desc* descs, 
                                          const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
                                          const uint8_t* orientation, void* d_out, void* stream)
 {
-    return crops_resized_mixed_impl(c, descs, nframes, d_y, d_cb, d_cr, false, windows, out_w, out_h, dtype, out_layout, scale, bias,
-                                    flip, filter, max_prescale_log2, orientation, d_out, stream);
+    return crops_resized_mixed_impl(c, descs, nframes, d_y, d_cb, d_cr, false, windows,
+                                    resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
+                                    max_prescale_log2, orientation, stream);
 }
 
 // Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_resized_crop_batch_device): the same over the CPU walker's planes
@@ -1388,8 +1332,9 @@ int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t
                                    unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
                                    const uint8_t* flip, int filter, int max_prescale_log2, const uint8_t* orientation, void* d_out)
 {
-    const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows, out_w, out_h, dtype, out_layout, scale, bias,
-                                            flip, filter, max_prescale_log2, orientation, d_out, nullptr);
+    const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
+                                            resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
+                                            max_prescale_log2, orientation, nullptr);
     if (c && c->stream) {
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }

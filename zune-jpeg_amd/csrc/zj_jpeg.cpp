@@ -33,6 +33,7 @@
 #include "../../include/zjhip.h"
 #include "zj_crew.h"
 #include "zj_geom.h"
+#include "zj_rzgroup.h"
 #include "zj_huff.h"
 
 namespace {
@@ -2914,7 +2915,7 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
                           int dtype, int filter, size_t out_cap, size_t* out_len, int o, zj_frame_desc& fd, int& ch)
 {
     using namespace zj;
-    if (filter != ZJ_RESIZE_BILINEAR && filter != ZJ_RESIZE_BILINEAR_AA && filter != ZJ_RESIZE_BICUBIC_AA) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
+    if (!resize_filter_valid(filter)) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
     if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     fill_info(d, nullptr, &fd);
@@ -2949,23 +2950,25 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
     const WindowLayout g = window_layout(&fd, win[2], win[3], 0); // (the crop's own check of the window follows)
-    const size_t half = (g.len + 15) & ~(size_t)15;
+    // one image's group (zj_rzgroup.h): the crop at the start of the buffer, turned: its displayed form behind it
+    const RzFrame rf{win[2], win[3], o};
+    RzPlace at;
+    size_t bytes = 0;
+    rz_group_next(&rf, 1, 0, ch, g.nplanes == 3, RZ_GROUP_CAP, &at, &bytes);
     uint8_t* crop = nullptr;
-    rc = zjint_resize_scratch(ctx, o != 1 ? 2 * half : g.len, &crop);
+    rc = zjint_resize_scratch(ctx, bytes, &crop);
     if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     size_t got = 0;
     rc = k ? zj_decoder_finish_pixels_scaled_device(d, ctx, k, win[0], win[1], win[2], win[3], crop, g.len, 0, &got)
            : zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, g.len, 0, &got);
     if (rc) return rc;
     const int layout = g.nplanes == 3 ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
-    if (o != 1) {
-        rc = zjint_orient_one(ctx, crop, win[2], win[3], ch, layout, o, crop + half);
+    if (at.turned) {
+        rc = zjint_orient_one(ctx, crop, win[2], win[3], ch, layout, o, crop + at.in.off);
         if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
-        crop += half;
-        const unsigned sw = win[2], sh = win[3];
-        orient_size(o, sw, sh, &win[2], &win[3]);
     }
-    rc = zjint_resize_one(ctx, crop, win[2], win[3], ch, layout, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
+    rc = zjint_resize_one(ctx, crop + at.in.off, at.in.w, at.in.h, ch, layout, out_w, out_h, dtype, out_layout, scale, bias, flip,
+                          filter, d_out);
     return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 

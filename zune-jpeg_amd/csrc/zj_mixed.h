@@ -84,6 +84,26 @@ inline bool mixed_descs_agree(const zj_frame_desc* descs, size_t n)
     return true;
 }
 
+// Every frame's checks of a mixed call, before anything is launched, in the order that decides a bad call's status: the
+// descriptors agree; then frame by frame mixed_frame_plan, out_rc (the status of the call's output arguments: one output,
+// checked once by the caller), the frame's plane pointers (planes(f, chroma): the caller's check, a status) and
+// mixed_frame_window.  The status is the one the single-frame call gives for the first failing frame.  fr: n of them.
+template <class Planes>
+inline int mixed_check_frames(const zj_frame_desc* descs, size_t n, const unsigned* windows, const uint8_t* orientation,
+                              int out_rc, unsigned out_w, unsigned out_h, int max_k, Planes planes, MixedFrame* fr)
+{
+    if (!mixed_descs_agree(descs, n)) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < n; f++) {
+        const zj_frame_desc* const d = &descs[f];
+        int rc = mixed_frame_plan(d, windows + 4 * f, orientation ? (orientation[f] ? orientation[f] : -1) : 0, fr[f]);
+        if (rc) return rc;
+        if (out_rc) return out_rc;
+        if ((rc = planes(f, fr[f].pl.out != OUT_GRAY))) return rc;
+        if ((rc = mixed_frame_window(d, windows + 4 * f, out_w, out_h, max_k, fr[f]))) return rc;
+    }
+    return ZJ_OK;
+}
+
 // The plane rows frame m's crop stage reads: strips [r0, r1) of yrow / crow i16 elements (scale 1), or MCU rows (k > 0).
 // Whole strips and MCU rows are contiguous ranges of a plane, and no kernel reads across one (zjint_crop_frame,
 // zjint_scaled_frame).
