@@ -20,6 +20,8 @@ pub const ZJ_FLAG_EDGE_REPLICATE: u32 = 4;
 pub const ZJ_FLAG_CORRECTED: u32 = 7;
 /// zj_options.flags only: AC values as the file codes them (the reference cuts some fast-AC values to six bits)
 pub const ZJ_FLAG_FULL_AC_VALUES: u32 = 8;
+/// resized crops only: a one-component frame or file asked for RGB gives R = G = B
+pub const ZJ_FLAG_GRAY_TO_RGB: u32 = 16;
 pub const ZJ_LAYOUT_HWC: u32 = 0;
 pub const ZJ_LAYOUT_CHW: u32 = 1;
 pub const ZJ_DTYPE_F32: c_int = 0;
@@ -249,6 +251,8 @@ extern "C" {
     pub fn zj_oriented_size(orientation: c_int, w: c_uint, h: c_uint, ow: *mut c_uint, oh: *mut c_uint) -> c_int;
     pub fn zj_orient_window(orientation: c_int, frame_w: c_uint, frame_h: c_uint, window: *const c_uint,
                             stored: *mut c_uint) -> c_int;
+    pub fn zj_gray_to_rgb_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                                 out_layout: c_int, d_out: *const *mut u8, out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
     pub fn zj_orient_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
                             channels: c_int, in_layout: c_int, orientation: *const u8, d_out: *const *mut u8,
                             out_pitch: *const c_uint, stream: *mut c_void) -> c_int;

@@ -145,6 +145,24 @@ typedef struct zj_frame_desc {
  * (the reference's own test-images/test-progressive.jpg: 958 coefficients in 649 of 97 200 blocks); with this flag the
  * front-end yields the coded values, which is what libjpeg decodes. */
 #define ZJ_FLAG_FULL_AC_VALUES 8u
+/* Gray to RGB: a one-component JPEG shown as an RGB image with R = G = B, what image viewers and
+ * Pillow's convert("RGB") give.  Off by default, and honoured by the RESIZED-CROP family only:
+ *   zj_frame_desc.flags   zj_decode_crops_resized_device, _filtered_, _prescaled_, _oriented_ and _mixed_, and
+ *                         zj_resized_out_len: a descriptor with in_components == 1 and out_colorspace == ZJ_CS_RGB is decoded
+ *                         as GRAYSCALE and expanded to 3 channels in front of the resize (without the flag such a descriptor
+ *                         is refused: ZJ_ERR_UNSUPPORTED).  Every other entry point returns what it returns for an unknown
+ *                         flag bit (ZJ_ERR_ARG);
+ *   zj_options.flags      a one-component file finished through zj_decoder_finish_pixels_resized_crop*_device or the batch
+ *                         call by a decoder whose out_colorspace is ZJ_CS_RGB gives a 3-channel image: the slot size,
+ *                         *out_len and the capacity check all use 3 channels.  (Without the flag the file is GRAYSCALE
+ *                         whatever the decoder asks for, src/headers.rs:283-290: a 1-channel image.)
+ * DEFINITION: the image equals, byte for byte, zj_resize_filtered_device applied to the 3-channel u8 image E, in the layout
+ * (HWC or CHW) the call's colour crops have, every channel of which is the displayed u8 crop the same call writes for that
+ * frame with out_colorspace = ZJ_CS_GRAYSCALE -- same filter, prescale pick, orientation, flip, scale, bias, dtype and tensor
+ * layout.  Three-component frames and files: the flag does nothing, so a caller can set it everywhere; in a mixed call gray
+ * and colour frames share the launch groups and the resize launches, and the colour frames keep the bytes they have without
+ * the gray ones.  One component with ZJ_CS_YCBCR: ZJ_ERR_UNSUPPORTED. */
+#define ZJ_FLAG_GRAY_TO_RGB 16u
 #define ZJ_LAYOUT_HWC 0u
 #define ZJ_LAYOUT_CHW 1u
 
@@ -372,6 +390,14 @@ ZJ_API int zj_orient_window(int orientation, unsigned frame_w, unsigned frame_h,
 ZJ_API int zj_orient_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
                             int channels, int in_layout, const uint8_t *orientation, uint8_t *const *d_out,
                             const unsigned *out_pitch, void *stream);
+/* n u8 planes in device memory -> 3-channel u8 images with every channel equal to the plane: d_in, in_wh
+ * (width and height, 1..65535) and in_pitch as in zj_orient_device; out_layout ZJ_LAYOUT_HWC (pixels g g g) or ZJ_LAYOUT_CHW
+ * (three planes, out_pitch x height apart); d_out[i] the first byte of image i's output, its rows out_pitch[i] bytes apart
+ * (NULL or 0: tight, 3 x width bytes for HWC and width bytes for CHW; the padding is never written).  Any addresses and
+ * pitches; an image's input and output must not overlap.  One launch per 128 images, whatever their sizes.  Asynchronous on
+ * `stream` (NULL: the context's); nothing is launched after an argument error. */
+ZJ_API int zj_gray_to_rgb_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                                 int out_layout, uint8_t *const *d_out, const unsigned *out_pitch, void *stream);
 /* zj_decode_crops_resized_prescaled_device for frames that are to be shown turned: orientation[f] = 1..8 per frame (NULL: all
  * 1, and the call IS the prescaled one), windows in DISPLAYED pixels of each frame.  The output is zj_resize_filtered_device
  * applied to EXACTLY the displayed form of the u8 crop zj_decode_crops_device writes for the stored window (zj_orient_window)

@@ -1,0 +1,55 @@
+"""ctypes binding of the CPU emulation of the gray-to-RGB kernel (tests/emu_expand).  TEST ONLY."""
+import ctypes as C
+import os
+
+import numpy as np
+
+import emu_build
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+_LIB = None
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        so = os.path.join(HERE, "emu_expand", "libzjemuexpand.so")
+        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
+        srcs = [os.path.join(HERE, "emu_expand", "zj_emu_expand.cpp"), os.path.join(csrc, "zj_expand.h"),
+                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
+        emu_build.build(so, srcs, "-O2")
+        L = C.CDLL(so)
+        L.zjex_expand.restype = C.c_longlong
+        L.zjex_expand.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]
+        _LIB = L
+    return _LIB
+
+
+def run():
+    return lib().zjex_run()
+
+
+def batch():
+    return lib().zjex_batch()
+
+
+def params_bytes():
+    return lib().zjex_params_bytes()
+
+
+def expand(in_addrs, sizes, in_pitches, out_chw, arena, out_offsets, out_pitches):
+    """The launches of one call: in_addrs = addresses of the planes' first bytes, sizes = (w, h), outputs at
+    arena[out_offsets[i]:] at out_pitches[i].  Returns (write map of the arena, stores that fell outside it)."""
+    n = len(in_addrs)
+    ins = (C.c_void_p * n)(*in_addrs)
+    wh = (C.c_uint * (2 * n))(*[v for sz in sizes for v in sz])
+    ip = (C.c_uint * n)(*in_pitches)
+    op = (C.c_uint * n)(*out_pitches)
+    outs = (C.c_void_p * n)(*[arena.ctypes.data + off for off in out_offsets])
+    wmap = np.zeros(arena.size, np.uint8)
+    outside = lib().zjex_expand(n, ins, wh, ip, 1 if out_chw else 0, outs, op, C.c_void_p(arena.ctypes.data), arena.size,
+                                C.c_void_p(wmap.ctypes.data))
+    assert outside >= 0, "the emulation refused its arguments"
+    return wmap, outside

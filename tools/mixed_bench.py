@@ -13,6 +13,11 @@ context's stream before they return).  Per setting: both paths warmed up, then `
 `--inner` calls each, medians and the spread.  The outputs of the two paths are compared for equality first.
 
   python tools/mixed_bench.py [--files 128] [--repeats 15] [--inner 4] [--out profiles/mixed_batch.txt] [--once]
+                              [--gray-share P]
+
+--gray-share P (default 0: the runs above as they are): round(P x files) of the files, picked by a generator of their own, are
+saved as single-component JPEGs of their first channel, and every decoder gets ZJ_FLAG_GRAY_TO_RGB: those
+files come out as RGB with R = G = B, in the same batch call.
 
 --once: one batch call and one loop per setting, no timing table; with --path batch (or loop) only that one: the run to put
 under `rocprofv3 --kernel-trace --stats`, whose per-kernel call counts are the launch counts."""
@@ -32,7 +37,7 @@ sys.path.insert(0, ROOT)
 SETTINGS = [("bilinear", False, "bilinear"), ("antialiased", True, "bilinear"), ("bicubic", True, "bicubic")]
 
 
-def make_files(n, seed):
+def make_files(n, seed, gray=()):
     from PIL import Image
     rng = np.random.default_rng(seed)
     files = []
@@ -42,7 +47,11 @@ def make_files(n, seed):
         base = np.stack([(xx * (1 + i % 5) + yy) % 256, (xx // 3 + yy * (2 + i % 3)) % 256, (xx * yy // (50 + i)) % 256], -1)
         img = (base + rng.normal(0, 12, base.shape)).clip(0, 255).astype(np.uint8)
         buf = io.BytesIO()
-        Image.fromarray(img).save(buf, "JPEG", quality=int(rng.integers(50, 96)), subsampling=["4:2:0", "4:4:4", "4:2:2"][i % 3])
+        quality = int(rng.integers(50, 96))
+        if i in gray:
+            Image.fromarray(img[..., 0]).save(buf, "JPEG", quality=quality)
+        else:
+            Image.fromarray(img).save(buf, "JPEG", quality=quality, subsampling=["4:2:0", "4:4:4", "4:2:2"][i % 3])
         files.append((buf.getvalue(), w, h))
     return files
 
@@ -69,6 +78,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--path", choices=["both", "batch", "loop"], default="both", help="with --once: which of the two to run")
+    ap.add_argument("--gray-share", type=float, default=0.0, help="share of the files that are single-component JPEGs")
     a = ap.parse_args()
 
     import torch  # (first: one HIP runtime in the process)
@@ -80,15 +90,25 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    files = make_files(a.files, a.seed)
+    if not 0.0 <= a.gray_share <= 1.0:
+        ap.error("--gray-share is a share: 0..1")
+    ngray = int(round(a.gray_share * a.files))
+    gray = set(int(i) for i in np.random.default_rng(a.seed + 2).choice(a.files, ngray, replace=False)) if ngray else set()
+    files = make_files(a.files, a.seed, gray)
     rng = np.random.default_rng(a.seed + 1)
     wins = [random_resized_crop(rng, w, h) for _, w, h in files]
     n = len(files)
     ctx = zj.Context(zj.BACKEND_HIP, 0)  # raises without a GPU: there is nothing to measure on a CPU
-    decs = [zj.Decoder(None, ctx) for _ in range(n)]
+    opt = None
+    if gray:
+        opt = zj.ZuneJpegOptions()
+        opt.flags = zj.FLAG_GRAY_TO_RGB
+    decs = [zj.Decoder(opt, ctx) for _ in range(n)]
     say(f"# tools/mixed_bench.py: {n} files, {sum(len(f[0]) for f in files) / 1e6:.2f} MB, sizes "
         f"{min(f[1] for f in files)}..{max(f[1] for f in files)} x {min(f[2] for f in files)}..{max(f[2] for f in files)}, "
         f"{sum(f[1] * f[2] for f in files) / 1e6:.1f} MP; windows {sum(w[2] * w[3] for w in wins) / 1e6:.1f} MP -> 224 x 224 bf16 NCHW")
+    if gray:
+        say(f"# --gray-share {a.gray_share:g}: {ngray} single-component files, decoded to RGB (ZJ_FLAG_GRAY_TO_RGB)")
     say(f"# device: {torch.cuda.get_device_name(0)}")
 
     # entropy stage: prepare() of every file, on one thread (the walker; the same for both paths)

@@ -16,6 +16,7 @@
 #include "zj_launch.h"
 #include "zj_mixed_launch.h"
 #include "zj_orient_launch.h"
+#include "zj_expand_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
 #include "zj_rzgroup.h"
@@ -939,31 +940,70 @@ int orient_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
     return ZJ_OK;
 }
 
+// planes [0, n) -> 3-channel images with every channel the plane, launches of up to EXPAND_BATCH images; wh:
+// w, h pairs, the pitches resolved
+int expand_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int out_chw,
+                    uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
+{
+    ExpandParams p{};
+    for (size_t f0 = 0; f0 < n; f0 += EXPAND_BATCH) {
+        const int m = (int)(n - f0 < (size_t)EXPAND_BATCH ? n - f0 : (size_t)EXPAND_BATCH);
+        p.nimg = m;
+        for (int i = 0; i < EXPAND_BATCH; i++) {
+            const size_t f = f0 + i;
+            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
+            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
+            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
+            p.in_pitch[i] = i < m ? in_pitch[f] : 0;
+            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
+        }
+        ZJ_HIP(c, launch_expand(out_chw, p, st));
+    }
+    return ZJ_OK;
+}
+
 // The end of the launch group [g0, g1) of a resized call, its crops written into buf where `place` says (zj_rzgroup.h):
 // the turned frames, gathered: crop -> its displayed form, tight, in the second region; the resize over the images place[f].in
 // names, in order, into images [g0, g1) of the output; the event that orders the buffer's reuse.
 int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g0, size_t g1, uint8_t* buf, const ResizeOut& o,
                     hipStream_t st)
 {
+    // the images of one stage of the group, gathered
+    struct Stage {
+        std::vector<const uint8_t*> in;
+        std::vector<uint8_t*> out;
+        std::vector<unsigned> wh, ip, op;
+        std::vector<uint8_t> o;
+        void add(uint8_t* buf, const RzImage& from, const RzImage& to, int orientation)
+        {
+            in.push_back(buf + from.off); out.push_back(buf + to.off);
+            wh.push_back(from.w); wh.push_back(from.h);
+            ip.push_back(from.pitch); op.push_back(to.pitch);
+            o.push_back((uint8_t)orientation);
+        }
+    };
     const size_t ng = g1 - g0;
-    std::vector<const uint8_t*> in(ng), oin;
-    std::vector<unsigned> wh(2 * ng), pitch(ng), owh, oip, oop;
-    std::vector<uint8_t*> oout;
-    std::vector<uint8_t> oo;
+    std::vector<const uint8_t*> in(ng);
+    std::vector<unsigned> wh(2 * ng), pitch(ng);
+    Stage turn, turn_gray, expand; // (the gray frames of a 3-channel call are turned as the 1-channel images they still are)
     for (size_t f = g0; f < g1; f++) {
         const RzPlace& p = place[f];
         in[f - g0] = buf + p.in.off;
         wh[2 * (f - g0)] = p.in.w; wh[2 * (f - g0) + 1] = p.in.h;
         pitch[f - g0] = p.in.pitch;
-        if (!p.turned) continue;
-        oin.push_back(buf + p.crop.off); oout.push_back(buf + p.in.off);
-        owh.push_back(p.crop.w); owh.push_back(p.crop.h);
-        oip.push_back(p.crop.pitch); oop.push_back(p.in.pitch);
-        oo.push_back((uint8_t)fr[f].o);
+        if (p.turned) (p.expand ? turn_gray : turn).add(buf, p.crop, p.gray, fr[f].o);
+        if (p.expand) expand.add(buf, p.gray, p.in, 1);
     }
     int rc;
-    if (!oin.empty() && (rc = orient_launches(c, oin.size(), oin.data(), owh.data(), oip.data(), o.ch, o.chw, oo.data(), oout.data(),
-                                              oop.data(), st)))
+    if (!turn.in.empty() && (rc = orient_launches(c, turn.in.size(), turn.in.data(), turn.wh.data(), turn.ip.data(), o.ch, o.chw,
+                                                  turn.o.data(), turn.out.data(), turn.op.data(), st)))
+        return rc;
+    if (!turn_gray.in.empty() && (rc = orient_launches(c, turn_gray.in.size(), turn_gray.in.data(), turn_gray.wh.data(),
+                                                       turn_gray.ip.data(), 1, 0, turn_gray.o.data(), turn_gray.out.data(),
+                                                       turn_gray.op.data(), st)))
+        return rc;
+    if (!expand.in.empty() && (rc = expand_launches(c, expand.in.size(), expand.in.data(), expand.wh.data(), expand.ip.data(),
+                                                    o.chw, expand.out.data(), expand.op.data(), st)))
         return rc;
     if ((rc = resize_launches(c, ng, in.data(), wh.data(), pitch.data(), o, g0, st))) return rc;
     return resize_scratch_done(c, st);
@@ -975,8 +1015,9 @@ size_t zj_resized_out_len(const zj_frame_desc* d, unsigned out_w, unsigned out_h
     Plan pl;
     CropPlan cp;
     const int ch = resize_channels(d);
-    if (!ch) return 0;
-    if (zero_output(d) ? make_zero_crop(d, 1, 1, 0, cp) : make_crop_plan(d, 1, 1, 0, pl, cp)) return 0;
+    if (!ch || gray_to_rgb_refused(d)) return 0;
+    const zj_frame_desc e = resized_stage_desc(d); // (ZJ_FLAG_GRAY_TO_RGB: planned as the GRAYSCALE frame it is decoded as)
+    if (zero_output(&e) ? make_zero_crop(&e, 1, 1, 0, cp) : make_crop_plan(&e, 1, 1, 0, pl, cp)) return 0;
     return resized_len(ch, out_w, out_h, dtype);
 }
 
@@ -1067,12 +1108,17 @@ int zj_decode_crops_resized_filtered_device(zj_ctx* c, const zj_frame_desc* d, s
 // DISPLAYED pixels; each is mapped to its stored window first (orient_window), which is decoded as ever; the crops of the
 // frames with o != 1 are then turned into a second region of the buffer, behind the group's crops, and the resize reads
 // those.  The scale is picked from the displayed window's sides, the ones the resize sees.
-static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* caller_d, size_t nframes, const int16_t* const* d_y,
                               const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows, ResizeOut ro,
                               int max_prescale_log2, const uint8_t* orientation, void* stream)
 {
     if (!resize_filter_valid(ro.filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
-    if (!c || !d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
+    if (!c || !caller_d || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
+    // ZJ_FLAG_GRAY_TO_RGB: the stages in front of the resize run with the frames as GRAYSCALE ones (d), the
+    // output has the caller's 3 channels, and every frame passes the expand stage on the way (rz_finish_group)
+    const bool gray = gray_to_rgb(caller_d);
+    const zj_frame_desc stage_d = resized_stage_desc(caller_d);
+    const zj_frame_desc* const d = &stage_d;
     const unsigned* const shown = windows; // the caller's windows: displayed pixels
     std::vector<unsigned> stored_store;
     if (orientation) {
@@ -1082,8 +1128,8 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
             if (!orient_window(orientation[f], d->width, d->height, shown + 4 * f, stored_store.data() + 4 * f)) return ZJ_ERR_ARG;
         windows = stored_store.data();
     }
-    const int ch = resize_channels(d);
-    if (!ch) return ZJ_ERR_UNSUPPORTED;
+    const int ch = resize_channels(caller_d);
+    if (!ch || gray_to_rgb_refused(caller_d)) return ZJ_ERR_UNSUPPORTED;
     Plan pl;
     CropPlan cp;
     int rc = make_crop_plan(d, 1, 1, 0, pl, cp);
@@ -1102,7 +1148,7 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
     }
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const bool chw = ro.chw = pl.out == OUT_RGB_CHW;
+    const bool chw = ro.chw = ch == 3 && caller_d->out_layout == ZJ_LAYOUT_CHW; // (of RGB: make_plan refuses YCbCr planes)
     // per image: its scale and the window the crop stage decodes (scale 1: the window itself)
     std::vector<unsigned> cwin_store;
     std::vector<int> klog;
@@ -1121,7 +1167,7 @@ static int crops_resized_impl(zj_ctx* c, const zj_frame_desc* d, size_t nframes,
         }
     // launch groups (zj_rzgroup.h): frames whose crops fit RZ_GROUP_CAP together, the buffer sized for the largest
     std::vector<RzFrame> rzf(nframes);
-    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{cwin[4 * f + 2], cwin[4 * f + 3], orientation ? orientation[f] : 1};
+    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{cwin[4 * f + 2], cwin[4 * f + 3], orientation ? orientation[f] : 1, gray};
     uint8_t* buf = nullptr;
     if ((rc = resize_scratch(c, rz_scratch_need(rzf.data(), nframes, ch, chw, RZ_GROUP_CAP), st, &buf))) return rc;
     std::vector<RzPlace> place(nframes);
@@ -1228,10 +1274,10 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
     if (rc) return rc;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const bool chw = ro.chw = fr[0].pl.out == OUT_RGB_CHW;
+    const bool chw = ro.chw = ch == 3 && descs[0].out_layout == ZJ_LAYOUT_CHW; // (of RGB: make_plan refuses YCbCr planes)
     // launch groups (zj_rzgroup.h), as the one-geometry call's
     std::vector<RzFrame> rzf(nframes);
-    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{fr[f].cwin[2], fr[f].cwin[3], fr[f].o};
+    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{fr[f].cwin[2], fr[f].cwin[3], fr[f].o, fr[f].gray};
     uint8_t* buf = nullptr;
     if ((rc = resize_scratch(c, rz_scratch_need(rzf.data(), nframes, ch, chw, RZ_GROUP_CAP), st, &buf))) return rc;
     std::vector<RzPlace> place(nframes);
@@ -1384,6 +1430,40 @@ int zj_orient_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsi
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return orient_launches(c, n, d_in, in_wh, ip.data(), channels, chw, o.data(), d_out, op.data(), st);
+}
+
+/* ---- gray to RGB ---------------------------------------------------------------- */
+int zj_gray_to_rgb_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch,
+                          int out_layout, uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
+    if (out_layout != ZJ_LAYOUT_HWC && out_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    const unsigned bpp = out_layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> ip(n), op(n);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_in[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        ip[f] = in_pitch && in_pitch[f] ? in_pitch[f] : w;
+        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
+        if (ip[f] < w || op[f] < w * bpp || ip[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return expand_launches(c, n, d_in, in_wh, ip.data(), out_layout == ZJ_LAYOUT_CHW, d_out, op.data(), st);
+}
+
+// Library-internal (zj_jpeg.cpp: the single-file resized crop of a gray file shown as RGB): one tight plane expanded on the
+// context stream into a tight image of out_layout; the context's crop buffer counts as read by it; synchronised
+int zjint_gray_to_rgb_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int out_layout, uint8_t* d_out)
+{
+    if (!c) return ZJ_ERR_ARG;
+    const unsigned wh[2] = {w, h};
+    int rc = zj_gray_to_rgb_device(c, 1, &in, wh, nullptr, out_layout, &d_out, nullptr, nullptr);
+    if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
 }
 
 // Library-internal (zj_jpeg.cpp: the decoder's oriented outputs): one image turned on the context stream, tight on both

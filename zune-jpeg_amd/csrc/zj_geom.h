@@ -36,6 +36,26 @@ inline int resize_channels(const zj_frame_desc* d)
     return d->out_colorspace == ZJ_CS_GRAYSCALE ? 1 : 0;
 }
 
+// ZJ_FLAG_GRAY_TO_RGB, which the resized-crop calls alone honour.  gray_to_rgb: d is a one-component frame
+// that the flag turns into an RGB image with R = G = B.  gray_to_rgb_refused: the flag on a one-component frame asked for
+// YCbCr, which has no such form.  resized_stage_desc: the descriptor the stages in front of the resize run with -- the flag
+// stripped (every plan refuses an unknown bit), a gray_to_rgb frame decoded as GRAYSCALE; anything else as it is.
+inline bool gray_to_rgb(const zj_frame_desc* d)
+{
+    return d && (d->flags & ZJ_FLAG_GRAY_TO_RGB) && d->in_components == 1 && d->out_colorspace == ZJ_CS_RGB;
+}
+inline bool gray_to_rgb_refused(const zj_frame_desc* d)
+{
+    return d && (d->flags & ZJ_FLAG_GRAY_TO_RGB) && d->in_components == 1 && d->out_colorspace == ZJ_CS_YCBCR;
+}
+inline zj_frame_desc resized_stage_desc(const zj_frame_desc* d)
+{
+    zj_frame_desc e = *d;
+    e.flags &= ~(uint32_t)ZJ_FLAG_GRAY_TO_RGB;
+    if (gray_to_rgb(d)) e.out_colorspace = ZJ_CS_GRAYSCALE;
+    return e;
+}
+
 // ---- windows --------------------------------------------------------------------------------------------------------
 // A window of w x h pixels of an output of d's format, its rows out_pitch bytes apart (0: tight), laid out by zj_out_len's
 // arithmetic: rows of w x bpp bytes, CHW RGB: w bytes in each of 3 planes.

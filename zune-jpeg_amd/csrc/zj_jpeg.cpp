@@ -2719,6 +2719,8 @@ __attribute__((weak)) int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigne
 __attribute__((weak)) int zjint_scratch_idle(zj_ctx* c, size_t bytes, uint8_t** p);
 __attribute__((weak)) int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, int o,
                                            uint8_t* d_out);
+// ... and one plane expanded to an RGB image with R = G = B
+__attribute__((weak)) int zjint_gray_to_rgb_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int out_layout, uint8_t* d_out);
 
 // ... and the resized crops of several files' planes in host memory, each of its own geometry
 __attribute__((weak)) int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
@@ -2910,7 +2912,8 @@ int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale
 // o: 1, or the orientation the window is given in: x, y, w, h are then DISPLAYED pixels, the stored window
 // they map to is decoded as ever, turned into the second half of the buffer, and the resize reads that
 // finish_resized's checks of its arguments, up to the stored window x, y, w, h (given in displayed pixels when o != 1); fd, ch:
-// the file's descriptor and channel count
+// the file's descriptor and channel count.  A one-component file of a decoder that asks for RGB with ZJ_FLAG_GRAY_TO_RGB
+// (DESIGN.md 3.11): fd is the one-component RGB descriptor with the flag, as the frame calls take it, and ch is 3.
 static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsigned& w, unsigned& h, unsigned out_w, unsigned out_h,
                           int dtype, int filter, size_t out_cap, size_t* out_len, int o, zj_frame_desc& fd, int& ch)
 {
@@ -2919,9 +2922,14 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
     if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     fill_info(d, nullptr, &fd);
+    if (d->ncomp == 1 && (d->flags & ZJ_FLAG_GRAY_TO_RGB)) {
+        if (d->out_colorspace == ZJ_CS_YCBCR) return fail(d, ZJ_ERR_UNSUPPORTED, "ZJ_FLAG_GRAY_TO_RGB gives RGB, not YCbCr");
+        if (d->out_colorspace == ZJ_CS_RGB) { fd.out_colorspace = ZJ_CS_RGB; fd.flags |= ZJ_FLAG_GRAY_TO_RGB; }
+    }
     ch = resize_channels(&fd);
     if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
-    if (k && zero_output(&fd)) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
+    if (gray_to_rgb(&fd) && !zjint_gray_to_rgb_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (k && zero_output(&fd) && !gray_to_rgb(&fd)) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
     const size_t need = resized_len(ch, out_w, out_h, dtype);
     if (out_len) *out_len = need;
     if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
@@ -2949,12 +2957,17 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     const unsigned full[4] = {x, y, w, h};
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
-    const WindowLayout g = window_layout(&fd, win[2], win[3], 0); // (the crop's own check of the window follows)
-    // one image's group (zj_rzgroup.h): the crop at the start of the buffer, turned: its displayed form behind it
-    const RzFrame rf{win[2], win[3], o};
+    // (a gray file shown as RGB: the crop and its displayed form are the 1-channel images of the GRAYSCALE decode)
+    const bool expand = gray_to_rgb(&fd);
+    const zj_frame_desc sd = resized_stage_desc(&fd);
+    const WindowLayout g = window_layout(&sd, win[2], win[3], 0); // (the crop's own check of the window follows)
+    const bool chw = ch == 3 && fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
+    // one image's group (zj_rzgroup.h): the crop at the start of the buffer, turned: its displayed form behind it, a gray
+    // file shown as RGB: its 3-channel image behind both
+    const RzFrame rf{win[2], win[3], o, expand};
     RzPlace at;
     size_t bytes = 0;
-    rz_group_next(&rf, 1, 0, ch, g.nplanes == 3, RZ_GROUP_CAP, &at, &bytes);
+    rz_group_next(&rf, 1, 0, ch, chw, RZ_GROUP_CAP, &at, &bytes);
     uint8_t* crop = nullptr;
     rc = zjint_resize_scratch(ctx, bytes, &crop);
     if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
@@ -2962,10 +2975,14 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     rc = k ? zj_decoder_finish_pixels_scaled_device(d, ctx, k, win[0], win[1], win[2], win[3], crop, g.len, 0, &got)
            : zj_decoder_finish_pixels_crop_device(d, ctx, x, y, w, h, crop, g.len, 0, &got);
     if (rc) return rc;
-    const int layout = g.nplanes == 3 ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
+    const int layout = chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
     if (at.turned) {
-        rc = zjint_orient_one(ctx, crop, win[2], win[3], ch, layout, o, crop + at.in.off);
+        rc = zjint_orient_one(ctx, crop, win[2], win[3], expand ? 1 : ch, layout, o, crop + at.gray.off);
         if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    }
+    if (expand) {
+        rc = zjint_gray_to_rgb_one(ctx, crop + at.gray.off, at.gray.w, at.gray.h, layout, crop + at.in.off);
+        if (rc) return fail(d, rc, std::string("gray to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     }
     rc = zjint_resize_one(ctx, crop + at.in.off, at.in.w, at.in.h, ch, layout, out_w, out_h, dtype, out_layout, scale, bias, flip,
                           filter, d_out);
@@ -3038,7 +3055,8 @@ int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, si
     if (!first) return ZJ_ERR_ARG;
     zj_frame_desc fd0{};
     fd0.out_colorspace = (uint32_t)first->out_colorspace;
-    const size_t img = resized_len(resize_channels(&fd0), out_w, out_h, dtype); // (0: every file's own call says why)
+    const size_t img = resized_len(resize_channels(&fd0), out_w, out_h, dtype); // (0: every file's own call says why; a gray
+                                                                                // file that does not become RGB: 1 channel)
     if (img && out_cap / img < n) return ZJ_ERR_ARG;
     const auto single = [&](size_t k) {
         const unsigned* const w = windows + 4 * k;
@@ -3060,7 +3078,7 @@ int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, si
         const int kk = prescale_pick(w, h, out_w, out_h, max_prescale_log2);
         int ch = 0;
         if ((rcs[k] = resized_checks(d, kk, x, y, w, h, out_w, out_h, dtype, filter, img, nullptr, o, fds[k], ch))) continue;
-        if (d->scan_ready || !d->coef_valid || zero_output(&fds[k])) { rcs[k] = single(k); continue; }
+        if (d->scan_ready || !d->coef_valid || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
         py[k] = d->comps[0].coef;
         pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
         ori[k] = (uint8_t)o;

@@ -35,6 +35,7 @@ struct MixedFrame {
     ScaledPlan sp;                // of scale k (k > 0)
     int k;                        // prescale_pick
     int o;                        // orientation 1..8 (1: none given)
+    bool gray;                    // a one-component frame of an RGB call (ZJ_FLAG_GRAY_TO_RGB): planned as GRAYSCALE, expanded later
     unsigned stored[4];           // the window in stored pixels
     unsigned cwin[4];             // the window the crop stage decodes: `stored` at scale 1, else its reduced cover
 };
@@ -51,8 +52,10 @@ inline int mixed_frame_plan(const zj_frame_desc* d, const unsigned shown[4], int
         if (!orient_window(o, d->width, d->height, shown, m.stored)) return ZJ_ERR_ARG;
         m.o = o;
     }
-    if (!resize_channels(d)) return ZJ_ERR_UNSUPPORTED;
-    return make_crop_plan(d, 1, 1, 0, m.pl, m.cp);
+    if (!resize_channels(d) || gray_to_rgb_refused(d)) return ZJ_ERR_UNSUPPORTED;
+    m.gray = gray_to_rgb(d);
+    const zj_frame_desc e = resized_stage_desc(d); // (what the stages in front of the resize decode: DESIGN.md 3.11)
+    return make_crop_plan(&e, 1, 1, 0, m.pl, m.cp);
 }
 
 // ... second half: the window inside the frame, the reduced plans up to max_k, the frame's scale and crop-stage window
@@ -67,8 +70,9 @@ inline int mixed_frame_window(const zj_frame_desc* d, const unsigned shown[4], u
     m.k = max_k > 0 ? prescale_pick(shown[2], shown[3], out_w, out_h, max_k) : 0;
     Plan spl;
     ScaledPlan sp;
+    const zj_frame_desc e = resized_stage_desc(d);
     for (int k = 1; k <= max_k; k++) {
-        if ((rc = make_scaled_plan(d, k, spl, sp))) return rc;
+        if ((rc = make_scaled_plan(&e, k, spl, sp))) return rc;
         if (k == m.k) m.sp = sp;
     }
     for (int i = 0; i < 4; i++) m.cwin[i] = w[i];
@@ -126,7 +130,9 @@ inline void mixed_plane_rows(const zj_frame_desc* d, const MixedFrame& m, size_t
 struct MixedLaunch { int hs, vs, out, sl; size_t off; int n, gx, gy; };
 
 // The tables of one group's frames: runs of CropParams (scale 1) by sampling mode, runs of ScaledParams by (sampling mode,
-// scale), one run of MixedZero; every run starts on a MIXED_TAB_ALIGN boundary.
+// scale), one run of MixedZero; every run starts on a MIXED_TAB_ALIGN boundary.  A run's frames have one kernel: where a mode
+// holds frames with and without chroma (the gray frames of an RGB call beside its 4:4:4 frames), each kind
+// has a run of its own, the colour frames' first.
 struct MixedTables {
     std::vector<MixedLaunch> crop, scaled;
     MixedLaunch zero{};           // n == 0: none; gx: the tallest window, gy: the most planes
@@ -135,12 +141,12 @@ struct MixedTables {
 
 inline size_t mixed_align(size_t v) { return (v + MIXED_TAB_ALIGN - 1) & ~(MIXED_TAB_ALIGN - 1); }
 
-// bytes the tables of frames fr[0 .. n) take at most (16 runs + the zeros, each starting up to one unit late)
+// bytes the tables of frames fr[0 .. n) take at most (32 runs + the zeros, each starting up to one unit late)
 inline size_t mixed_table_bytes(const MixedFrame* fr, size_t n)
 {
     size_t nc = 0, ns = 0;
     for (size_t f = 0; f < n; f++) (fr[f].k ? ns : nc)++;
-    return nc * (sizeof(CropParams) + sizeof(MixedZero)) + ns * sizeof(ScaledParams) + 17 * MIXED_TAB_ALIGN;
+    return nc * (sizeof(CropParams) + sizeof(MixedZero)) + ns * sizeof(ScaledParams) + 33 * MIXED_TAB_ALIGN;
 }
 
 // Fill `tab` (mixed_table_bytes of it, 16-byte aligned) for frames [0, n) and list the launches.  y / cb / cr / out: the
@@ -153,13 +159,14 @@ inline void mixed_fill_tables(const zj_frame_desc* descs, const MixedFrame* fr, 
     size_t off = 0;
     for (int mode = 0; mode < 4; mode++) {
         const int hs = 1 + (mode & 1), vs = 1 + (mode >> 1);
-        for (int k = 0; k <= 3; k++) {
+        for (int kg = 0; kg < 8; kg++) {
+            const int k = kg >> 1;
+            const bool chroma = !(kg & 1);
             MixedLaunch run{};
             run.hs = hs; run.vs = vs; run.sl = k; run.off = off;
             for (size_t f = 0; f < n; f++) {
                 const MixedFrame& m = fr[f];
-                if (m.pl.hs != hs || m.pl.vs != vs || m.k != k) continue;
-                const bool chroma = m.pl.out != OUT_GRAY;
+                if (m.pl.hs != hs || m.pl.vs != vs || m.k != k || (m.pl.out != OUT_GRAY) != chroma) continue;
                 const int16_t* const py = y[f];
                 const int16_t* const pcb = chroma ? cb[f] : nullptr;
                 const int16_t* const pcr = chroma ? cr[f] : nullptr;

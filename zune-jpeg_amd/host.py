@@ -63,6 +63,7 @@ FLAG_CLAMP_DC = 2     # extension: DC-only shortcut value clamped to 0..255 (Q1 
 FLAG_EDGE_REPLICATE = 4  # extension: horizontal chroma filter per row with replicated edges (Q4 corrected)
 FLAG_CORRECTED = 7
 FLAG_FULL_AC_VALUES = 8  # zj_options.flags only: the front-end yields AC values as coded (the reference cuts some to six bits)
+FLAG_GRAY_TO_RGB = 16    # resized crops only: a one-component frame / file asked for RGB gives R = G = B
 LAYOUT_HWC, LAYOUT_CHW = 0, 1
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8 = 0, 1, 2, 3  # zj_resize_device and the resized crops: the output's dtype
 TENSOR_NCHW, TENSOR_NHWC = 0, 1                          # ... and its layout
@@ -188,6 +189,7 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decoder_orientation", "zj_decoder_finish_pixels_oriented_device",
     "zj_decoder_finish_pixels_resized_crop_oriented_device",
     "zj_decode_crops_resized_mixed_device", "zj_decoder_finish_pixels_resized_crop_batch_device",
+    "zj_gray_to_rgb_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -349,6 +351,7 @@ def lib():
     L.zj_oriented_size.argtypes = [C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zj_orient_window.argtypes = [C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zj_orient_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.zj_gray_to_rgb_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, vp, vp, vp]
     L.zj_decode_crops_resized_oriented_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
                                                           C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.zj_decoder_orientation.argtypes = [vp]
@@ -643,6 +646,19 @@ class Context:
         ori = (C.c_uint8 * n)(*[int(o) for o in orientations]) if orientations is not None else None
         _check(lib().zj_orient_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), channels, in_layout, ori,
                                       (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_orient_device", self._h)
+
+    def gray_to_rgb_device(self, d_in, sizes, out_layout, d_out, in_pitches=None, out_pitches=None, stream=None):
+        """One u8 plane each -> a 3-channel u8 image with R = G = B (zj_gray_to_rgb_device): d_in = device
+        pointers of the planes, sizes = one (w, h) each, out_layout LAYOUT_HWC (pixels g g g) or LAYOUT_CHW (three planes),
+        d_out = one device pointer each; pitches = bytes between rows (None: tight).  Input and output must not overlap.
+        Asynchronous on `stream`."""
+        n = len(d_in)
+        if len(sizes) != n or len(d_out) != n:
+            raise ValueError("one size and output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+        _check(lib().zj_gray_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), out_layout,
+                                           (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_gray_to_rgb_device", self._h)
 
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
                                     bias=None, flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,

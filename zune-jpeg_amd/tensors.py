@@ -166,8 +166,11 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     max_prescale = 2, 4 or 8: every window is decoded at the largest reduced size (1/2, 1/4, 1/8, up to 1/max_prescale)
     that still is at least the output's, and resized from there; 1 (default): none.  Anything else is a
     ValueError.  orientations: one EXIF orientation 1..8 per frame; the windows are then in DISPLAYED pixels of the frames
-    and the crops are turned before the resize; None (default): none.  Stream and allocator rules as
-    decode_to_tensor."""
+    and the crops are turned before the resize; None (default): none.
+    One-component frames: desc.flags | FLAG_GRAY_TO_RGB with ColorSpace.RGB gives the image a viewer shows, R = G = B
+    (DESIGN.md 3.11): the GRAYSCALE crop, turned, copied into three channels, then resized.  Without the flag a
+    one-component descriptor that asks for RGB is refused (ZjError: not supported); ask for GRAYSCALE and get C = 1.  The
+    flag does nothing for three-component frames.  Stream and allocator rules as decode_to_tensor."""
     import torch
     from .host import resize_filter, scale_log2
     scale_log2(max_prescale)
@@ -206,6 +209,11 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     options: ZuneJpegOptions of the decoders (None: the defaults).  workers: threads that prepare the files (headers and
     the CPU entropy stage; the library calls release the GIL), at most 16.  decoders: a list to keep between calls --
     Decoder objects are made as needed, appended to it and reused.  A file that fails raises DecodeError naming its index.
+    Grayscale (one-component) files among colour ones: give options.flags | FLAG_GRAY_TO_RGB with out_colorspace RGB, and
+    their images are R = G = B like torchvision's decode_jpeg(mode=RGB), decoded in the same launch groups
+    as the colour files.  WITHOUT the flag a one-component file is decoded as GRAYSCALE whatever the options ask for: its
+    one channel lands in the first third of its 3-channel slot, the rest of the slot is not written, no error is raised,
+    and the files around it are decoded one by one.  The flag does nothing for three-component files.
     The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
     the stream the output is allocated under, synchronised before the call writes it."""
     import torch
@@ -358,6 +366,27 @@ def orient_to_tensor(ctx, images, orientations, in_layout="HWC", stream=None):
     ctx.orient_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
                       orientations, [o.data_ptr() for o in outs], pitches, None, s.cuda_stream)
     return [o.squeeze(-1) if in_layout != "CHW" and im.dim() == 2 else o for o, im in zip(outs, images)]
+
+
+def gray_to_rgb_tensor(ctx, images, out_layout="HWC", stream=None):
+    """u8 CUDA planes -> 3-channel images with R = G = B (zj_gray_to_rgb_device): images = [H, W] (or
+    [H, W, 1]) uint8 tensors of their own sizes; rows may be strided.  Returns a list of new contiguous tensors, [H, W, 3]
+    ("HWC") or [3, H, W] ("CHW").  Streams as decode_to_tensor."""
+    import torch
+    if out_layout not in ("HWC", "CHW"):
+        raise ValueError("out_layout is 'HWC' or 'CHW'")
+    imgs, sizes, pitches, channels = _u8_images(images, "HWC")
+    if channels != 1:
+        raise ValueError("images are single planes: [H, W] or [H, W, 1]")
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        outs = [torch.empty((3, h, w) if out_layout == "CHW" else (h, w, 3), dtype=torch.uint8, device=dev) for w, h in sizes]
+    _on_stream(s, cur, imgs)
+    ctx.gray_to_rgb_device([im.data_ptr() for im in imgs], sizes, LAYOUT_CHW if out_layout == "CHW" else LAYOUT_HWC,
+                           [o.data_ptr() for o in outs], pitches, None, s.cuda_stream)
+    return outs
 
 
 def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HWC", mean=None, std=None, flips=None,
