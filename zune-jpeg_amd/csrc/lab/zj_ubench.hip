@@ -78,6 +78,11 @@ namespace zj {
 #define I_SATPK_SDWA(r) "v_sat_pk_u8_i16_sdwa " #r ", %9 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n"
 #define I_MIX_DOT(r) "v_dot2c_i32_i16_e32 " #r ", 0x08a914e8, %9\n v_add_u32_e32 " #r ", %9, " #r "\n"
 
+// the byte formulation of the chroma up-sampling filters: four byte averages per instruction, and the byte funnel shift
+#define I_LERP(r) "v_lerp_u8 " #r ", " #r ", %9, %8\n"
+#define I_LERPZ(r) "v_lerp_u8 " #r ", " #r ", %9, 0\n"
+#define I_ALIGNBYTE(r) "v_alignbyte_b32 " #r ", " #r ", %9, 1\n"
+
 UB_KERNEL(ub_add, I_ADD)
 UB_KERNEL(ub_add64, I_ADD64)
 UB_KERNEL(ub_adds, I_ADDS)
@@ -127,6 +132,9 @@ UB_KERNEL(ub_ashr_sdwa, I_ASHR_SDWA)
 UB_KERNEL(ub_ashrs, I_ASHRS)
 UB_KERNEL(ub_satpk_sdwa, I_SATPK_SDWA)
 UB_KERNEL(ub_mix_dot, I_MIX_DOT)
+UB_KERNEL(ub_lerp, I_LERP)
+UB_KERNEL(ub_lerpz, I_LERPZ)
+UB_KERNEL(ub_alignbyte, I_ALIGNBYTE)
 
 #define UB_KERNEL_BODY(NAME, BODY)                                                                     \
     __global__ __launch_bounds__(256) void NAME(int* out, int iters, int seed)                         \
@@ -245,6 +253,7 @@ static const struct { const char* name; ub_fn fn; } UB[] = {
     {"v_dot2_i32_i16 v,v,s,0", ub_dot2z}, {"v_sad_u16 v,v,s,v", ub_sad16},
     {"v_ashrrev_i32_sdwa (word_1, preserve)", ub_ashr_sdwa}, {"v_ashrrev_i32_e32 v,s,v", ub_ashrs},
     {"v_sat_pk_u8_i16_sdwa (word_1, preserve)", ub_satpk_sdwa},
+    {"v_lerp_u8 v,v,v,s", ub_lerp}, {"v_lerp_u8 v,v,v,0", ub_lerpz}, {"v_alignbyte_b32 v,v,v,1", ub_alignbyte},
     {"PAIR dot2c ; add          (2 instr)", ub_mix_dot},
     {"PAIR mul24 ; add          (2 instr)", ub_mix1}, {"TRIPLE mad24 ; add ; ashr (3 instr)", ub_mix2}, {"PAIR add ; ashr            (2 instr)", ub_mix3},
     {"GROUPED 8 mad | 8 add | 8 ashr   (x3 instr)", ub_grp_mad_add_ashr},

@@ -75,7 +75,7 @@ __global__ __launch_bounds__((Cfg<HS, VS, OUT>::NT), (CropOccupancy<HS, VS, OUT>
     }
     __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0), see fused_body
     __syncthreads();
-    const bool redo = NEED_Y16 && __builtin_amdgcn_readfirstlane((int)*lds_flag<C>(lds)) != 0;
+    const bool redo = (NEED_Y16 || C::CBYTE) && __builtin_amdgcn_readfirstlane((int)*lds_flag<C>(lds)) != 0;
     if (redo) { // (the wide code over the same tile, as fused_body's tile_wide)
         __syncthreads();
         const BlockLoc L = locate<C, GEN_WIDE>(p, t, tid, lds);

@@ -76,6 +76,13 @@ typedef uint32_t V4 __attribute__((vector_size(16)));    // the same 16 bytes fo
 #define ZJ_ROUND_ROT 1
 #endif
 
+// 1: the packed generation keeps the chroma of the horizontally sub-sampled modes as BYTES in LDS and runs both triangle
+//    filters four samples per instruction with v_lerp_u8 (Cfg::CBYTE, tri_b); 0: the packed-pair filters of rounds 2-6
+//    (A/B knob: tools/build_variant.sh pairs "-DZJ_CBYTE=0")
+#ifndef ZJ_CBYTE
+#define ZJ_CBYTE 1
+#endif
+
 ZJ_DEV uint32_t as_u32(u16x2 v) { uint32_t r; __builtin_memcpy(&r, &v, 4); return r; }
 ZJ_DEV uint32_t as_u32(s16x2 v) { uint32_t r; __builtin_memcpy(&r, &v, 4); return r; }
 ZJ_DEV u16x2 as_u16x2(uint32_t v) { u16x2 r; __builtin_memcpy(&r, &v, 4); return r; }
@@ -186,6 +193,17 @@ ZJ_DEV uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel)
 }
 // (hi:lo) >> 16, i.e. {lo.hi16, hi.lo16}
 ZJ_DEV uint32_t align16(uint32_t hi, uint32_t lo) { return (lo >> 16) | (hi << 16); }
+// v_lerp_u8: per byte (a + b + (c & 1)) >> 1, four bytes per instruction, nothing carried between them
+ZJ_DEV uint32_t lerp_u8(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(ZJ_EMU)
+    uint32_t r = 0;
+    for (int i = 0; i < 4; i++) r |= ((((a >> (8 * i)) & 0xffu) + ((b >> (8 * i)) & 0xffu) + ((c >> (8 * i)) & 1u)) >> 1) << (8 * i);
+    return r;
+#else
+    return __builtin_amdgcn_lerp(a, b, c);
+#endif
+}
 
 ZJ_DEV s16x2 pk_max(s16x2 a, s16x2 b)
 {
@@ -594,6 +612,12 @@ ZJ_DEV uint32_t tri(uint32_t near_, uint32_t far_)
     return as_u32(sar(splat(3) * as_u16x2(near_) + as_u16x2(far_) + splat(2), 2));
 }
 ZJ_DEV int tri1(int near_, int far_) { return (int)(int16_t)(uint16_t)(3 * near_ + far_ + 2) >> 2; }
+// The same filter on four BYTES per dword: for integers a, b >= 0, with a + b = 2s + r (r = 0 | 1),
+//   (3a + b + 2) >> 2  ==  floor((a + s + 1 + r/2) / 2)  ==  (a + ((a + b) >> 1) + 1) >> 1
+// (the r/2 never carries across the floor), i.e. two byte averages, the second one rounding up: two v_lerp_u8 where the
+// pair form takes three instructions for half as many samples.  The rounding bit is the low bit of every byte of the third
+// operand: -1, an inline constant.
+ZJ_DEV uint32_t tri_b(uint32_t near_, uint32_t far_) { return lerp_u8(near_, lerp_u8(near_, far_, 0u), 0xffffffffu); }
 
 // ------------------------------------------------------------------------------------------------
 // Tile geometry per sampling mode.  A workgroup owns one "tile": the full height of one strip
@@ -663,6 +687,7 @@ enum { GEN_WIDE = 0, GEN_PACKED = 1 };
 // LDS layouts (byte offsets).
 //   GEN_WIDE    Yp[SH][TWY] i16 | Cb[CROWS][CPITCH] i16 | Cr[..] | halo columns, raw + filtered | tables | vertical LUT
 //   GEN_PACKED  Yb[SH][TWY] u8  | Cb[CROWS][CPITCH] i16 | Cr[..] | halo columns, raw + filtered | tables | vertical LUT | flag | store staging
+//               (Cfg::CBYTE: Cb and Cr are u8 as well -- rows of CPITCH bytes; the halo columns stay i16)
 // The packed kernel's allocation covers the wide layout too: a tile whose luma cannot be staged as bytes (an
 // unclamped DC-only value outside 0..255, Q1) is redone by the wide code in the same workgroup.
 template <int HS, int VS, int OUT>
@@ -685,7 +710,7 @@ struct Cfg {
     // conflict on every such read; profiles/r03_lds_conflicts_by_phase.txt).  The halo blocks' single pixel columns live in
     // a side array [comp][side][chroma row], and -- packed generation -- vertically filtered per output row in
     // [comp][side][m] (halo_filter), where the colour phase's edge lanes pick them up.
-    static constexpr int CPITCH = TWC * 8;             // i16 per chroma LDS row
+    static constexpr int CPITCH = TWC * 8;             // samples per chroma LDS row (i16; u8 in the packed generation under CBYTE)
     static constexpr int COFF = 0;                     // LDS column of chroma column 0
     static constexpr int YSZ = SH * TWY;               // luma samples per tile
     static constexpr int CSZ = CROWS * CPITCH;         // chroma samples per tile and component
@@ -706,8 +731,6 @@ struct Cfg {
     static constexpr int LUT_BYTES = ((2 * LUT_N * 2 + 15) / 16) * 16;
     static constexpr int HRAW = (CHROMA && HALO) ? 2 * 2 * CROWS : 0; // i16: halo pixel columns
     static constexpr int HFIL = (CHROMA && HALO) ? 2 * 2 * SH : 0;    // i16: the same per up-sampled row
-    static constexpr int CBYTES = CHROMA ? (2 * CSZ + HRAW + HFIL) * 2 : 0;
-    static_assert(CBYTES % 16 == 0, "tables stay 16-byte aligned");
     // interleaved outputs leave through staged stores: PPI 16-byte pieces per 16-pixel item (3 or 4 bytes per pixel)
     static constexpr bool TSCAP = OUT == OUT_RGB || OUT == OUT_YCBCR || OUT == OUT_RGBA;
     static constexpr int PPI = OUT == OUT_RGBA ? 4 : 3;
@@ -718,11 +741,33 @@ struct Cfg {
     // one lane per block COLUMN instead of one lane per block (halo_pass1 / halo_pass2)
     static constexpr bool HALO_PURE = CHROMA && HALO && (NYB + 2 * CBR * TWC) % 64 == 0 && 2 * CBR * 2 * 8 == 64;
     static constexpr int HALO_T0 = NYB + 2 * CBR * TWC; // first lane of that wave
+    // CBYTE: the packed generation stages the chroma of the horizontally sub-sampled modes as bytes, like luma, and both
+    // triangle filters run on four bytes per instruction (tri_b) -- every sample they touch is a byte: the transforms clamp
+    // to 0..255, and a DC-only shortcut value outside that range (Q1) raises the tile's redo flag exactly as luma's does.
+    // HS == 1 has no horizontal filter to win back the unpacking, gray has no chroma.  The byte code is written for the
+    // shapes the product runs: pure waves (the block waves are all luma or all chroma, the halo columns have their own), and
+    // rows of 16 groups, one DPP row.
+    // (The emulation harnesses that predate the byte path consult the redo flag for the RGB family only; for them the
+    // other outputs keep the pair path.  A harness that honours the flag for every output says so: ZJ_EMU_REDO_ANY.)
+#if defined(ZJ_EMU) && !defined(ZJ_EMU_REDO_ANY)
+    static constexpr bool CBYTE_OUT = OUT == OUT_RGB || OUT == OUT_RGBA || OUT == OUT_RGB_CHW;
+#else
+    static constexpr bool CBYTE_OUT = true;
+#endif
+    static constexpr bool CBYTE = ZJ_CBYTE != 0 && CHROMA && HS == 2 && HALO_PURE && NGRP == 16 && NYB % 64 == 0 && CBYTE_OUT;
     template <int GEN> struct L {
         static constexpr int YPX = GEN == GEN_PACKED ? 1 : 2;        // bytes per staged luma sample
+        static constexpr bool CB = GEN == GEN_PACKED && CBYTE;       // chroma staged as bytes
+        static constexpr int CPX = CB ? 1 : 2;                       // bytes per staged chroma sample
+        static constexpr int CPB = CPITCH * CPX;                     // bytes per chroma LDS row
+        static constexpr int CPLANE = CROWS * CPB;                   // bytes per chroma plane
+        static constexpr int CBYTES = CHROMA ? 2 * CPLANE + (HRAW + HFIL) * 2 : 0; // both planes + the halo side arrays (i16)
+        static_assert(CBYTES % 16 == 0, "tables stay 16-byte aligned");
         // Cb plane, then Cr.  Packed: a wave's round reuses the 16 luma bytes of each of its 64 items as store staging
         // (piece_addr), also for item numbers beyond NITEMS in a partly filled round: the luma area is padded to whole rounds
         static constexpr int C_OFF = GEN == GEN_PACKED ? (NITEMS + 63) / 64 * 64 * 16 : YSZ * 2;
+        static constexpr int HRAW_OFF = C_OFF + 2 * CPLANE;
+        static constexpr int HFIL_OFF = HRAW_OFF + HRAW * 2;
         static constexpr int TAB_OFF = C_OFF + CBYTES;
         static constexpr int LUT_OFF = TAB_OFF + TAB_BYTES;
         static constexpr int FLAG_OFF = LUT_OFF + LUT_BYTES;         // GEN_PACKED: "redo this tile wide"
@@ -889,11 +934,11 @@ ZJ_DEV TileId decode_tile(const Params& p, int bid)
 // side arrays of the halo columns (Cfg::HRAW, Cfg::HFIL): comp 1 | 2, side 0 = left of the tile, 1 = right of it
 template <class C, int GEN> ZJ_DEV int16_t* lds_halo_raw(char* lds, int comp, int side, int row)
 {
-    return reinterpret_cast<int16_t*>(lds + C::template L<GEN>::C_OFF + 2 * C::CSZ * 2) + ((comp - 1) * 2 + side) * C::CROWS + row;
+    return reinterpret_cast<int16_t*>(lds + C::template L<GEN>::HRAW_OFF) + ((comp - 1) * 2 + side) * C::CROWS + row;
 }
 template <class C, int GEN> ZJ_DEV int16_t* lds_halo_fil(char* lds, int comp, int side, int m)
 {
-    return reinterpret_cast<int16_t*>(lds + C::template L<GEN>::C_OFF + (2 * C::CSZ + C::HRAW) * 2) + ((comp - 1) * 2 + side) * C::SH + m;
+    return reinterpret_cast<int16_t*>(lds + C::template L<GEN>::HFIL_OFF) + ((comp - 1) * 2 + side) * C::SH + m;
 }
 
 struct BlockLoc {
@@ -959,8 +1004,8 @@ ZJ_DEV BlockLoc locate(const Params& p, const TileId t, const int b, char* lds)
         L.dst = reinterpret_cast<char*>(lds_halo_raw<C, GEN>(lds, comp, L.halo - 1, brow * 8));
         L.pitch = 2;
     } else {
-        L.dst = lds + LL::C_OFF + ((comp - 1) * C::CSZ + (brow * 8) * C::CPITCH + lcol) * 2;
-        L.pitch = C::CPITCH * 2;
+        L.dst = lds + LL::C_OFF + ((comp - 1) * C::CSZ + (brow * 8) * C::CPITCH + lcol) * LL::CPX;
+        L.pitch = LL::CPB;
     }
     L.comp = comp;
     L.valid = true;
@@ -1034,8 +1079,8 @@ ZJ_DEV void phase_setup(const Params& p, const int tid, char* lds)
         for (int i = tid; i < C::LUT_N; i += C::NT) {
             int ra = 0, rb = 0;
             if (i >= 1 && i <= C::SH) vrows<HS, VS>(i - 1, ra, rb);
-            lds_lut<C, GEN>(lds)[i] = (int16_t)(ra * C::CPITCH * 2);
-            lds_lut<C, GEN>(lds)[C::LUT_N + i] = (int16_t)(rb * C::CPITCH * 2);
+            lds_lut<C, GEN>(lds)[i] = (int16_t)(ra * C::template L<GEN>::CPB);
+            lds_lut<C, GEN>(lds)[C::LUT_N + i] = (int16_t)(rb * C::template L<GEN>::CPB);
         }
     }
     if (GEN == GEN_PACKED && tid == 0) *lds_flag<C>(lds) = 0;
@@ -1132,6 +1177,8 @@ ZJ_DEV void halo_pass2(const HaloLane& H, char* lds, const int clamp_dc)
     if (any == 0) { // DC-only block (scalar.rs:45-74): the shortcut value, not clamped (Q1)
         const uint16_t* q = reinterpret_cast<const uint16_t*>(lds_tab<C, GEN_PACKED>(lds) + TAB_DW * H.comp);
         v = (int32_t)(int16_t)(dc_only_value((uint32_t)sc[72], (int32_t)q[0], clamp_dc) & 0xffffu);
+        // CBYTE: the colour phase takes the halo sample as a byte too; a shortcut value that is none sends the tile to the wide code
+        if (C::template L<GEN_PACKED>::CB && (uint32_t)v > 255u) *lds_flag<C>(lds) = 1; // benign race: every writer stores 1
     } else {
         const U4 a = *reinterpret_cast<const U4*>(sc + 8 * i), b = *reinterpret_cast<const U4*>(sc + 8 * i + 4);
         const int32_t t0 = (int32_t)a.x, t1 = (int32_t)a.y, t2 = (int32_t)a.z, t3 = (int32_t)a.w;
@@ -1160,7 +1207,7 @@ ZJ_DEV int halo_value(char* lds, const int comp, const int side, const int m, co
     if (VS == 2) {
         const int16_t* lut = lds_lut<C, GEN>(lds);
         const int i = m + 1 + (wrap ? (side == 0 ? -1 : 1) : 0);
-        const int ra = lut[i] / (C::CPITCH * 2), rb = lut[C::LUT_N + i] / (C::CPITCH * 2);
+        const int ra = lut[i] / C::template L<GEN>::CPB, rb = lut[C::LUT_N + i] / C::template L<GEN>::CPB;
         return tri1(raw[ra], raw[rb]);
     }
     const int r = side == 0 ? (wrap && m > 0 ? m - 1 : m) : (wrap && m < C::SH - 1 ? m + 1 : m);
@@ -1179,10 +1226,11 @@ ZJ_DEV void halo_filter(const Params& p, const TileId t, const int hl, char* lds
     }
 }
 
-// GEN_WIDE: the round-1 form.  GEN_PACKED: luma leaves as bytes, chroma as i16; NEED_Y16 = the output does
-// arithmetic on luma (RGB family), so an unclamped DC-only luma value outside 0..255 (Q1) cannot be staged as
+// GEN_WIDE: the round-1 form.  GEN_PACKED: luma leaves as bytes, chroma as i16 (as bytes under Cfg::CBYTE); NEED_Y16 = the
+// output does arithmetic on luma (RGB family), so an unclamped DC-only luma value outside 0..255 (Q1) cannot be staged as
 // a byte: the lane raises the tile's flag and the workgroup redoes the tile with the wide code.  (Gray and
-// YCbCr outputs truncate luma to its low byte anyway, Q7.)
+// YCbCr outputs truncate luma to its low byte anyway, Q7.)  Byte chroma raises the flag the same way whatever the output:
+// its samples go through the up-sampling filters before anything truncates them.
 template <class C, int GEN, bool NEED_Y16>
 ZJ_DEV void finish_block(const BlockLoc& L, const U4 raw[8], char* lds, const int debug = 0, const int clamp_dc = 0)
 {
@@ -1206,25 +1254,37 @@ ZJ_DEV void finish_block(const BlockLoc& L, const U4 raw[8], char* lds, const in
     // row of bytes is as long as a chroma row of i16 (the 256-pixel tiles of the horizontally sub-sampled modes) the LDS
     // pitch is ONE compile-time constant: the eight row stores take immediate offsets instead of 64-bit multiply-adds on a
     // per-lane pitch (round 4 ledger: 4 v_mad_u64_u32 + 3 v_lshl_add per block store)
+    // (under CBYTE there are two constants, 256 bytes for a luma row and 128 for a chroma row: each is used on its side of the
+    // `comp` branch, which is there anyway)
     using LLp = typename C::template L<GEN_PACKED>;
-    constexpr bool CONST_PITCH = C::HALO_PURE && C::TWY * LLp::YPX == C::CPITCH * 2;
+    constexpr bool CB = LLp::CB;
+    constexpr bool CONST_PITCH = C::HALO_PURE && (CB || C::TWY * LLp::YPX == LLp::CPB);
     BlockLoc Lc = L;
-    if (CONST_PITCH) { Lc.pitch = C::CPITCH * 2; Lc.halo = 0; }
+    if (CONST_PITCH) { Lc.pitch = LLp::CPB; Lc.halo = 0; }
+    const int ypitch = CONST_PITCH ? C::TWY * LLp::YPX : L.pitch;
     int cls = classify_block(w, tab + 32);
     if (ZJ_ABL(debug, 1)) cls = 0;
     if (cls == 0) {
         const uint32_t v = dc_only_value(w[0], (int32_t)(tab[0] & 0xffffu), clamp_dc);
-        if (L.comp != 0) { store_splat(Lc, v); return; }
-        if (NEED_Y16 && (v & 0xffffu) > 255u) *lds_flag<C>(lds) = 1; // benign race: every writer stores 1
+        if (L.comp != 0 && !CB) { store_splat(Lc, v); return; }
+        if ((L.comp != 0 || NEED_Y16) && (v & 0xffffu) > 255u) *lds_flag<C>(lds) = 1; // benign race: every writer stores 1
         const uint32_t b = (v & 0xffu) * 0x01010101u;
         const U2 row = {b, b};
+        if (L.comp != 0) {
 #pragma unroll
-        for (int r = 0; r < 8; r++) *reinterpret_cast<U2*>(Lc.dst + r * Lc.pitch) = row;
+            for (int r = 0; r < 8; r++) *reinterpret_cast<U2*>(Lc.dst + r * Lc.pitch) = row;
+            return;
+        }
+#pragma unroll
+        for (int r = 0; r < 8; r++) *reinterpret_cast<U2*>(Lc.dst + r * ypitch) = row;
         return;
     }
-    // the block's pixels (16 dwords of bytes) to LDS: luma rows of bytes, chroma rows of i16
+    // the block's pixels (16 dwords of bytes) to LDS: luma rows of bytes, chroma rows of i16 (CBYTE: of bytes)
     auto emit = [&](const uint32_t* b) {
         if (L.comp == 0) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) { const U2 row = {b[2 * r], b[2 * r + 1]}; *reinterpret_cast<U2*>(Lc.dst + r * ypitch) = row; }
+        } else if (CB) {
 #pragma unroll
             for (int r = 0; r < 8; r++) { const U2 row = {b[2 * r], b[2 * r + 1]}; *reinterpret_cast<U2*>(Lc.dst + r * Lc.pitch) = row; }
         } else {
@@ -1431,6 +1491,32 @@ ZJ_DEV void nb_pair(const uint32_t vm[4], const char* cp, const int oa, const in
     }
 }
 
+// The same for byte chroma (Cfg::CBYTE): a lane's eight samples are the dwords a0 = (v1 v2 v3 v4), a1 = (v5 v6 v7 v8); `prev` gets
+// lane g-1's a1 -- v0 in its top byte --, `next` lane g+1's a0 -- v9 in its low byte.  `pl` carries the left halo sample in
+// its top byte, `nr` the right one in its low byte.
+template <class C, int VS>
+ZJ_DEV void nb_bytes(const uint32_t a0, const uint32_t a1, const char* cp, const int oa, const int ob, const int lc, const int g,
+                     uint32_t& prev, uint32_t& next, const uint32_t pl, const uint32_t nr)
+{
+#if !defined(ZJ_EMU)
+    if (C::NGRP == 16) {
+        prev = (uint32_t)__builtin_amdgcn_update_dpp((int)pl, (int)a1, 0x111, 0xf, 0xf, false); // row_shr:1
+        next = (uint32_t)__builtin_amdgcn_update_dpp((int)nr, (int)a0, 0x101, 0xf, 0xf, false); // row_shl:1
+        return;
+    }
+#endif
+    // the emulation (lanes run one after the other): the same bytes from LDS, wherever they exist
+    prev = next = 0;
+    if (g > 0) {
+        prev = *reinterpret_cast<const uint32_t*>(cp + oa + lc - 4);
+        if (VS == 2) prev = tri_b(prev, *reinterpret_cast<const uint32_t*>(cp + ob + lc - 4));
+    }
+    if (g < C::NGRP - 1) {
+        next = *reinterpret_cast<const uint32_t*>(cp + oa + lc + 8);
+        if (VS == 2) next = tri_b(next, *reinterpret_cast<const uint32_t*>(cp + ob + lc + 8));
+    }
+}
+
 template <class C>
 ZJ_DEV void stage_item(const ItemOut& io, const int tid /* logical */, char* lds, const int round, const int hw_wave = -1)
 {
@@ -1539,7 +1625,7 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
             const int16_t* lut = lds_lut<C, GEN>(lds);
             oa = lut[m + 1]; ob = lut[C::LUT_N + m + 1];
         } else {
-            oa = ob = m * C::CPITCH * 2;
+            oa = ob = m * LL::CPB;
         }
         if (edge_tile) {
             ZJ_NO_IF_CONVERT();
@@ -1552,7 +1638,7 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
         const bool no_left = first && m == 0 && !p.edge_rep, no_right = last && m == C::SH - 1 && !p.edge_rep;
 #pragma unroll
         for (int ch = 0; ch < 2; ch++) {
-            const char* cp = lds + LL::C_OFF + ch * C::CSZ * 2;
+            const char* cp = lds + LL::C_OFF + ch * LL::CPLANE;
             uint32_t* dst = ch ? crp : cbp;
             if (ZJ_ABL(ZJ_PDBG(p), 16)) { // ablation: no chroma reads from LDS, no filters (output is wrong)
 #pragma unroll
@@ -1572,6 +1658,59 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
                 }
 #pragma unroll
                 for (int k = 0; k < 8; k++) dst[k] = v[k];
+            } else if (LL::CB) {
+                // Byte chroma: the group's eight samples are two dwords, a0 = (v1 v2 v3 v4), a1 = (v5 v6 v7 v8); every filter
+                // is two v_lerp_u8 per dword (tri_b).  What follows mirrors the pair code below step by step.
+                const int lc = C::COFF + 8 * g;
+                const U2 a = *reinterpret_cast<const U2*>(cp + oa + lc);
+                uint32_t a0 = a.x, a1 = a.y;
+                if (VS == 2) {
+                    const U2 b = *reinterpret_cast<const U2*>(cp + ob + lc);
+                    a0 = tri_b(a0, b.x); a1 = tri_b(a1, b.y);
+                }
+                // the neighbours: lane g-1's a1 (v0 in its top byte), lane g+1's a0 (v9 in its low byte); at the ends of the
+                // row the halo samples in those bytes (the DPP shifts leave `old` in the lanes that have no source)
+                uint32_t prev, next;
+                {
+                    const int hvl = *lds_halo_fil<C, GEN>(lds, ch + 1, 0, m), hvr = *lds_halo_fil<C, GEN>(lds, ch + 1, 1, m);
+                    const uint32_t pl = (uint32_t)hvl << 24, nr = (uint32_t)hvr & 0xffu;
+                    nb_bytes<C, VS>(a0, a1, cp, oa, ob, lc, g, prev, next, pl, nr);
+#if defined(ZJ_EMU)
+                    constexpr bool DPP_ENDS = false;
+#else
+                    constexpr bool DPP_ENDS = C::NGRP == 16;
+#endif
+                    if (!DPP_ENDS) {
+                        if (g == 0) prev = pl;
+                        if (g == nvalid - 1) next = nr;
+                    } else if (nvalid != C::NGRP) { // a row's last, narrower tile (workgroup-uniform): its end is not lane 15
+                        ZJ_NO_IF_CONVERT();
+                        if (g == nvalid - 1) next = nr;
+                    }
+                }
+                if (p.edge_rep) { // uniform branch (kernel argument)
+                    ZJ_NO_IF_CONVERT();
+                    if (rep_first) prev = a0 << 24; // v0 := v1
+                    if (rep_last) next = a1 >> 24;  // v9 := v8
+                }
+                const uint32_t l0 = alignbyte(a0, prev, 3), l1 = alignbyte(a1, a0, 3);   // (v0 v1 v2 v3) (v4 v5 v6 v7)
+                const uint32_t r0 = alignbyte(a1, a0, 1), r1 = alignbyte(next, a1, 1);   // (v2 v3 v4 v5) (v6 v7 v8 v9)
+                uint32_t e0 = tri_b(a0, l0), e1 = tri_b(a1, l1); // even outputs: px 0 2 4 6 | 8 10 12 14
+                uint32_t o0 = tri_b(a0, r0), o1 = tri_b(a1, r1); // odd outputs:  px 1 3 5 7 | 9 11 13 15
+                // the three unfiltered / mis-weighted samples of a strip (upsampler/scalar.rs:13,55,57)
+                if (edge_tile) {
+                    ZJ_NO_IF_CONVERT();
+                    if (no_left) e0 = (e0 & 0xffffff00u) | (a0 & 0xffu);                  // out[0] = in[0]
+                    if (no_right) {
+                        e1 = (e1 & 0x00ffffffu) | ((o1 << 8) & 0xff000000u);                // px 14 <- O(px 13)
+                        o1 = (o1 & 0x00ffffffu) | (a1 & 0xff000000u);                       // px 15 = in[n-1]
+                    }
+                }
+                // bytes -> the pair arrangement the colour math wants: [k] = (px 4k, 4k+2), [4 + k] = (px 4k+1, 4k+3)
+                dst[0] = perm(0, e0, 0x0c010c00u); dst[1] = perm(0, e0, 0x0c030c02u);
+                dst[2] = perm(0, e1, 0x0c010c00u); dst[3] = perm(0, e1, 0x0c030c02u);
+                dst[4] = perm(0, o0, 0x0c010c00u); dst[5] = perm(0, o0, 0x0c030c02u);
+                dst[6] = perm(0, o1, 0x0c010c00u); dst[7] = perm(0, o1, 0x0c030c02u);
             } else {
                 const int lc = (C::COFF + 8 * g) * 2; // LDS byte column of this group's first chroma sample
                 const U4 a = *reinterpret_cast<const U4*>(cp + oa + lc);

@@ -170,8 +170,9 @@ __device__ __forceinline__ void fused_body(const Params& p, char* lds)
     if (ZJ_ABL(ZJ_PDBG(p), 64)) return;   // ... after classification, IDCT, LDS staging (block waves) / the halo wave's work
     __syncthreads();
     // a DC-only luma block of this tile decodes outside 0..255 (Q1: the scalar shortcut does not clamp): the byte
-    // staging cannot carry it, the whole tile is redone by the wide code (never seen on valid 8-bit JPEG data)
-    const bool redo = NEED_Y16 && __builtin_amdgcn_readfirstlane((int)*lds_flag<C>(lds)) != 0;
+    // staging cannot carry it, the whole tile is redone by the wide code (never seen on valid 8-bit JPEG data).  Byte
+    // chroma (Cfg::CBYTE) raises the same flag, from its block wave and from the halo wave, for every output.
+    const bool redo = (NEED_Y16 || C::CBYTE) && __builtin_amdgcn_readfirstlane((int)*lds_flag<C>(lds)) != 0;
     if (redo) {
         __syncthreads(); // everyone has read the flag before the wide layout overwrites it
         tile_wide<C, HS, VS, OUT, FAST, RAG>(p, t, tid, lds);
