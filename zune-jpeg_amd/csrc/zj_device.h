@@ -82,6 +82,12 @@ typedef uint32_t V4 __attribute__((vector_size(16)));    // the same 16 bytes fo
 #ifndef ZJ_CBYTE
 #define ZJ_CBYTE 1
 #endif
+// -- ZJ_INTERIOR: 1 (default): a tile that is neither the first nor the last of its row, in a whole strip, runs its colour
+//    rounds in a form without bounds tests and edge logic (Cfg::INTERIOR, interior_tile); 0: every tile takes the general
+//    rounds (A/B knob: tools/build_variant.sh pairs "-DZJ_INTERIOR=0")
+#ifndef ZJ_INTERIOR
+#define ZJ_INTERIOR 1
+#endif
 
 ZJ_DEV uint32_t as_u32(u16x2 v) { uint32_t r; __builtin_memcpy(&r, &v, 4); return r; }
 ZJ_DEV uint32_t as_u32(s16x2 v) { uint32_t r; __builtin_memcpy(&r, &v, 4); return r; }
@@ -755,6 +761,11 @@ struct Cfg {
     static constexpr bool CBYTE_OUT = true;
 #endif
     static constexpr bool CBYTE = ZJ_CBYTE != 0 && CHROMA && HS == 2 && HALO_PURE && NGRP == 16 && NYB % 64 == 0 && CBYTE_OUT;
+    // INTERIOR: the staged-store kernels of the byte-chroma shapes carry a second form of their colour rounds for the tiles
+    // interior_tile() admits (14 of the 16 tiles of a 4096-pixel row): no per-item bounds test, no first / last / narrow
+    // tile logic, every item an ordinary one.  Only where every round is full -- 4:2:0; the 4:2:2 tile's 256 items on 192
+    // threads leave a partly filled, rotated round (ROUND_ROT), and that shape keeps the general rounds alone.
+    static constexpr bool INTERIOR = ZJ_INTERIOR != 0 && CBYTE && TSCAP && NITEMS % NT == 0 && ROUND_ROT == 0;
     template <int GEN> struct L {
         static constexpr int YPX = GEN == GEN_PACKED ? 1 : 2;        // bytes per staged luma sample
         static constexpr bool CB = GEN == GEN_PACKED && CBYTE;       // chroma staged as bytes
@@ -1517,14 +1528,28 @@ ZJ_DEV void nb_bytes(const uint32_t a0, const uint32_t a1, const char* cp, const
     }
 }
 
+// Is this tile an interior one (Cfg::INTERIOR)?  Workgroup-uniform, from scalars, once per tile.  It is when
+//   - it is neither the first nor the last tile of its row: no wrap to the row's other end, all NGRP groups valid, and the
+//     row's end with its early tail and its unwritten piece (Q5 / Q6: the kind-2 and kind-3 items, `never`) is in another
+//     tile -- both tail groups are in the row's last tile wherever the stores are staged (ts_eligible);
+//   - its strip is whole (rows_left >= SH);
+//   - the launch does not replicate the chroma edges (edge_rep takes a select in every item).
 template <class C>
+ZJ_DEV bool interior_tile(const Params& p, const TileId t)
+{
+    const int cb0 = t.tile * C::TWC;
+    return cb0 != 0 && cb0 + C::TWC < p.mcu_x && p.height - t.strip * C::SH >= C::SH && p.edge_rep == 0;
+}
+
+// INTERIOR (here, in phase_color and in color_copyout): the form of a round for the tiles interior_tile() admits
+template <class C, bool INTERIOR = false>
 ZJ_DEV void stage_item(const ItemOut& io, const int tid /* logical */, char* lds, const int round, const int hw_wave = -1)
 {
-    if (io.kind == 0) return;
+    if (!INTERIOR && io.kind == 0) return;
     const int lwave = tid >> 6, lane = tid & 63;
     const int item0 = 64 * lwave + round * C::NT;
     const int wave = hw_wave < 0 ? lwave : hw_wave; // whose staging bytes
-    if (C::PPI == 3 && io.kind == 3) { // rare: one lane per row of the tile that holds the row's end
+    if (!INTERIOR && C::PPI == 3 && io.kind == 3) { // rare: one lane per row of the tile that holds the row's end
         const U4 z = {0, 0, 0, 0};
         *reinterpret_cast<U4*>(piece_addr<C>(lds, item0, wave, 3 * lane - 1)) = io.s0; // launcher: lane > 0 here
         *reinterpret_cast<U4*>(piece_addr<C>(lds, item0, wave, 3 * lane)) = io.s1;
@@ -1536,7 +1561,7 @@ ZJ_DEV void stage_item(const ItemOut& io, const int tid /* logical */, char* lds
     dst[0] = io.s0;
     dst[1] = io.s1;
     if (C::PPI == 4) { dst[2] = io.s2; dst[3] = io.s3; }
-    else if (io.kind == 1) dst[2] = io.s2;
+    else if (INTERIOR || io.kind == 1) dst[2] = io.s2;
 }
 
 // TS (staged stores, GEN_PACKED, FAST RGB / YCbCr only): processes ONE round (item = tid + round * NT) and, instead
@@ -1547,16 +1572,19 @@ ZJ_DEV void stage_item(const ItemOut& io, const int tid /* logical */, char* lds
 // (worker.rs:143-251).  16-pixel groups below Params::regular_px are ordinary ones (48 bytes at 48 * G, all inside the row):
 // they take the fast stores, from rows that may start at any byte; the few groups beyond take the generic store path, by
 // the lanes that hold them, in the same workgroup.
-template <class C, int HS, int VS, int OUT, int GEN, bool FAST = true, bool TS = false, bool RAG = false>
+// INTERIOR (TS, byte chroma): the tile is an interior one (interior_tile) -- the round's item exists, lies inside the frame
+// and is an ordinary group of kind 1; nothing of the row's ends is here.
+template <class C, int HS, int VS, int OUT, int GEN, bool FAST = true, bool TS = false, bool RAG = false, bool INTERIOR = false>
 ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* lds, const int round = 0, ItemOut* io = nullptr)
 {
     using LL = typename C::template L<GEN>;
+    static_assert(!INTERIOR || (TS && FAST && !RAG && GEN == GEN_PACKED && LL::CB && C::INTERIOR), "the interior form exists for the staged byte-chroma rounds");
     const int P = p.mcu_x * 8 * HS;       // padded row length == luma width_stride (headers.rs:338)
     const int W = p.width;
     const int cbw = p.mcu_x;
     const int cb0 = t.tile * C::TWC;
-    const int nvalid = (cbw - cb0) < C::TWC ? (cbw - cb0) : C::TWC;
-    const bool left_wrap = cb0 == 0, right_wrap = cb0 + C::TWC >= cbw;
+    const int nvalid = INTERIOR ? C::TWC : ((cbw - cb0) < C::TWC ? (cbw - cb0) : C::TWC);
+    const bool left_wrap = !INTERIOR && cb0 == 0, right_wrap = !INTERIOR && cb0 + C::TWC >= cbw;
     const bool edge_tile = HS == 2 && (left_wrap || right_wrap); // workgroup-uniform
     const int x0 = t.tile * C::TWY;
     const long long row_bytes = p.out_pitch; // between rows (tight: W * ncomp; CHW: W, one plane's row); clip ends stay W-based
@@ -1564,11 +1592,12 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
     const int elements = P / 16 - 1; // worker.rs:171 (P >= 32 on this path)
     if (TS) io->kind = 0;
 
+    // (INTERIOR: every round is full, so tid < NT makes this one pass without a test)
     for (int item = TS ? tid + round * C::NT : tid; item < C::NITEMS; item += TS ? C::NITEMS : C::NT) {
         const int m = item / C::NGRP, g = item % C::NGRP;
         const int px0 = x0 + 16 * g;      // first pixel of the group in the padded row
         const int row = t.strip * C::SH + m;
-        if (px0 >= P || row >= p.height) continue;
+        if (!INTERIOR && (px0 >= P || row >= p.height)) continue;
         const bool irregular = RAG && px0 >= p.regular_px; // a group at the row's end: generic stores (RAG only)
         uint8_t* const orow = frame_out + (long long)row * row_bytes;
         // ---- luma: yp[] = packed i16 pairs in the arrangement the chroma code produces -----------------
@@ -1683,12 +1712,12 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
                     if (!DPP_ENDS) {
                         if (g == 0) prev = pl;
                         if (g == nvalid - 1) next = nr;
-                    } else if (nvalid != C::NGRP) { // a row's last, narrower tile (workgroup-uniform): its end is not lane 15
+                    } else if (!INTERIOR && nvalid != C::NGRP) { // a row's last, narrower tile (workgroup-uniform): its end is not lane 15
                         ZJ_NO_IF_CONVERT();
                         if (g == nvalid - 1) next = nr;
                     }
                 }
-                if (p.edge_rep) { // uniform branch (kernel argument)
+                if (!INTERIOR && p.edge_rep) { // uniform branch (kernel argument)
                     ZJ_NO_IF_CONVERT();
                     if (rep_first) prev = a0 << 24; // v0 := v1
                     if (rep_last) next = a1 >> 24;  // v9 := v8
@@ -1841,7 +1870,7 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
             // The early RGB tail (Q5) is a shift by one piece: the last group of a row starts in the third slot of the
             // group before it, and the row's last piece is zero (Q6) or never stored (color_copyout)
             io->s0 = s0; io->s1 = s1; io->s2 = s2;
-            io->kind = (quirk && G == elements) ? 3 : ((quirk && G == elements - 1) ? 2 : 1);
+            io->kind = INTERIOR ? 1 : ((quirk && G == elements) ? 3 : ((quirk && G == elements - 1) ? 2 : 1));
             continue;
         }
         if (!quirk) {
@@ -1869,10 +1898,12 @@ ZJ_DEV void phase_color(const Params& p, const TileId t, const int tid, char* ld
 // Second half of a staged-store round: lane L of a wave stores pieces 64*j + L (j = 0 .. PPI-1) of the 64*PPI pieces
 // its wave staged, i.e. every store instruction writes 1024 contiguous bytes of the tile's rows (row segments of
 // PIECES_PER_ROW pieces), instead of 64 pieces 48 (64) bytes apart.
-template <class C, int OUT, bool RAG = false, bool SEAM = false>
+// INTERIOR: every round of an interior tile (interior_tile) is a plain round; none of the tests that lead there is made.
+template <class C, int OUT, bool RAG = false, bool SEAM = false, bool INTERIOR = false>
 ZJ_DEV void color_copyout(const Params& p, const TileId t, const int tid /* logical */, char* lds, const int round, const int hw_wave = -1)
 {
     using LL = typename C::template L<GEN_PACKED>;
+    static_assert(!INTERIOR || (!RAG && !SEAM && C::INTERIOR), "the interior form exists for the plain staged rounds");
     constexpr int PPI = C::PPI;
     const int P = RAG ? p.regular_px : p.mcu_x * 8 * (C::TWYB / C::TWC); // RAG: only the ordinary groups were staged
     const int x0 = t.tile * C::TWY;
@@ -1883,7 +1914,7 @@ ZJ_DEV void color_copyout(const Params& p, const TileId t, const int tid /* logi
     uint8_t* const tile_out = t.out + (long long)t.strip * C::SH * row_bytes + (long long)(PPI == 4 ? 4 : 3) * x0;
     const int w = uniform(tid >> 6), L = tid & 63;
     const int item0 = 64 * w + round * C::NT;  // first item of this wave's round
-    if (item0 >= C::NITEMS) return;            // (the last round of a tile is partly empty)
+    if (!INTERIOR && item0 >= C::NITEMS) return; // (the last round of a tile is partly empty)
     // the piece the reference never writes: the last one of a row, in the tile that holds the row's end
     const bool row_end_here = !RAG && x0 + 16 * nvg == P;
     const int never = (OUT == OUT_RGB && !p.plain && !p.zero_fill && row_end_here) ? 3 * nvg - 1 : -1;
@@ -1910,7 +1941,7 @@ ZJ_DEV void color_copyout(const Params& p, const TileId t, const int tid /* logi
     }
     // interior tiles (all but the last of a row, all but a clipped last strip), whole rounds: no per-piece test,
     // PPI LDS reads, one wait, PPI stores
-    const bool plain_round = nvg == C::NGRP && rows_left >= C::SH && never < 0 && item0 + 64 <= C::NITEMS;
+    const bool plain_round = INTERIOR || (nvg == C::NGRP && rows_left >= C::SH && never < 0 && item0 + 64 <= C::NITEMS);
     // Rows that are not dword-aligned (ragged widths with width % 4 != 0, or a frame that starts at an odd address): a
     // 16-byte store per lane at an address that is not a multiple of 4 costs the memory pipeline dearly (+22 % kernel time
     // at 4090 pixels, where every second row is off by 2; dword-aligned but not 16-byte-aligned rows cost 3 %).  Such rows

@@ -55,6 +55,25 @@ __device__ __forceinline__ void tile_wide(const Params& p, const TileId t, const
     phase_color<C, HS, VS, OUT, GEN_WIDE, FAST, false, RAG>(p, t, tid, lds);
 }
 
+// The staged colour rounds (fused_body, TS) of an interior tile (zj_device.h: interior_tile), in their INTERIOR form
+template <class C, int HS, int VS, int OUT>
+__device__ __forceinline__ void interior_rounds(const Params& p, const TileId t, const int tid, char* lds)
+{
+    static_assert(C::ROUND_ROT == 0, "full rounds: the logical thread numbering is the hardware's");
+    __builtin_assume(tid >= 0 && tid < C::NT); // every round's item exists: phase_color's `item < NITEMS` folds away
+#pragma unroll
+    for (int round = 0; round * C::NT < C::NITEMS; round++) {
+        ItemOut io;
+        phase_color<C, HS, VS, OUT, GEN_PACKED, true, true, false, true>(p, t, tid, lds, round, &io);
+        if (round == 0 && ZJ_ABL(ZJ_PDBG(p), 128)) { ZJ_USE(io.s0.x ^ io.s0.y ^ io.s0.z ^ io.s0.w ^ io.s1.x ^ io.s1.y ^ io.s1.z ^ io.s1.w ^ io.s2.x ^ io.s2.y ^ io.s2.z ^ io.s2.w); return; } // (the ledger's cut points, as in fused_body)
+        stage_item<C, true>(io, tid, lds, round);
+        ZJ_WAVE_FENCE();
+        color_copyout<C, OUT, false, false, true>(p, t, tid, lds, round);
+        ZJ_WAVE_FENCE();
+        if (round == 0 && ZJ_ABL(ZJ_PDBG(p), 256)) return;
+    }
+}
+
 // The workgroups of a launch's FIRST wave (one per occupancy slot of the chip) all start in the same cycle and would move
 // through load / transform / colour / store in lock step: memory idles while they compute and the SIMDs idle while they
 // load.  In a long launch that synchrony dissolves after a tile or two; a launch of ONE frame (2048 tiles on 1536 slots)
@@ -181,6 +200,11 @@ __device__ __forceinline__ void fused_body(const Params& p, char* lds)
         // of one wave execute in order, so no barrier is needed between the halves or between rounds
         ZJ_SETPRIO(2, 2);
         __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0), free here; see above
+        // one scalar branch per tile: the interior tiles of a row run rounds without bounds tests and edge logic
+        constexpr bool INTERIOR = C::INTERIOR && FAST && !RAG && !SEAM;
+        if constexpr (INTERIOR) {
+            if (interior_tile<C>(p, t)) { interior_rounds<C, HS, VS, OUT>(p, t, tid, lds); return; }
+        }
 #pragma unroll
         for (int round = 0; round * C::NT < C::NITEMS; round++) {
             ItemOut io;
