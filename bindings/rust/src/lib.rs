@@ -22,6 +22,9 @@ pub const ZJ_FLAG_CORRECTED: u32 = 7;
 pub const ZJ_FLAG_FULL_AC_VALUES: u32 = 8;
 /// resized crops only: a one-component frame or file asked for RGB gives R = G = B
 pub const ZJ_FLAG_GRAY_TO_RGB: u32 = 16;
+/// zj_options.flags only: four-component (Adobe CMYK / YCCK) files are accepted and the resized-crop calls show them as RGB
+/// (DESIGN.md 3.12); without it such a file is refused at SOF as in the reference
+pub const ZJ_FLAG_CMYK_TO_RGB: u32 = 32;
 pub const ZJ_LAYOUT_HWC: u32 = 0;
 pub const ZJ_LAYOUT_CHW: u32 = 1;
 pub const ZJ_DTYPE_F32: c_int = 0;
@@ -253,6 +256,9 @@ extern "C" {
                             stored: *mut c_uint) -> c_int;
     pub fn zj_gray_to_rgb_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
                                  out_layout: c_int, d_out: *const *mut u8, out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
+    pub fn zj_cmyk_to_rgb_device(ctx: *mut zj_ctx, n: usize, d_a: *const *const u8, d_k: *const *const u8, in_wh: *const c_uint,
+                                 a_pitch: *const c_uint, k_pitch: *const c_uint, layout: c_int, inverted: *const u8,
+                                 d_out: *const *mut u8, out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
     pub fn zj_orient_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
                             channels: c_int, in_layout: c_int, orientation: *const u8, d_out: *const *mut u8,
                             out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
@@ -275,6 +281,9 @@ extern "C" {
                                                               max_prescale_log2: c_int, apply_orientation: c_int,
                                                               d_out: *mut c_void, out_cap: usize, rcs: *mut c_int) -> c_int;
     pub fn zj_decoder_orientation(d: *const zj_decoder) -> c_int;
+    pub fn zj_decoder_adobe_transform(d: *const zj_decoder) -> c_int;
+    pub fn zj_decoder_plane(d: *const zj_decoder, comp: c_int, plane: *mut *const i16, len: *mut usize, blocks_w: *mut c_uint,
+                            blocks_h: *mut c_uint) -> c_int;
     pub fn zj_decoder_finish_pixels_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, d_out: *mut u8, out_cap: usize,
                                                     out_len: *mut usize, out_w: *mut c_uint, out_h: *mut c_uint) -> c_int;
     pub fn zj_decoder_finish_pixels_resized_crop_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint,

@@ -163,6 +163,33 @@ typedef struct zj_frame_desc {
  * and colour frames share the launch groups and the resize launches, and the colour frames keep the bytes they have without
  * the gray ones.  One component with ZJ_CS_YCBCR: ZJ_ERR_UNSUPPORTED. */
 #define ZJ_FLAG_GRAY_TO_RGB 16u
+/* CMYK to RGB: a four-component JPEG (Adobe CMYK or YCCK) shown as an RGB image, what Pillow's convert("RGB")
+ * and the common tensor loaders' RGB mode give.  zj_options.flags ONLY (on a zj_frame_desc it is an unknown bit, ZJ_ERR_ARG).
+ * Without it a four-component file is refused at its SOF segment as ever (ZJ_ERR_SOF, the reference's text).  With it the
+ * front-end accepts Nf = 4 in SOF0 / SOF2 -- any component ids; components 2 and 3 at (1,1), components 1 and 4 both at the
+ * (h_max, v_max) of one of the four known modes, anything else ZJ_ERR_UNSUPPORTED -- reads the Adobe APP14 segment
+ * (zj_decoder_adobe_transform) and decodes the scans in a serial walk of its own: the coefficients are the values the file
+ * codes (no six-bit cut, none of the reference reader's quirks: the reference has no such path).  The parallel scan, restart
+ * threads, streaming and the device entropy stage leave such a file to that walk, whatever zj_options.entropy says.
+ * Component 4's plane has the layout of a one-component frame of the same size, ceil(w/8) x ceil(h/8) blocks.
+ * The zj_frame_desc that zj_decoder_prepare / zj_decoder_decode_coefficients fill for such a file (in_components = 4) does
+ * NOT describe a frame any frame-level call accepts: callers that want the stages themselves take the planes from
+ * zj_decoder_plane and build descriptors of their own -- three components for planes 0-2, one component for plane 3.
+ * A file whose width is below 57 and no multiple of 8 is ZJ_ERR_PANIC at full resolution, as a one-component frame of that
+ * width is (component 4's GRAYSCALE decode); a reduced-size decode under the resize (max_prescale_log2) decodes it.
+ * Such a file is finished by the RESIZED-CROP family only (zj_decoder_finish_pixels_resized_crop*_device and the batch call),
+ * by a decoder whose out_colorspace is ZJ_CS_RGB; every other finish call, zj_decoder_decode_buffer and the pool, and a decoder
+ * that asks for GRAYSCALE or YCBCR, return ZJ_ERR_UNSUPPORTED.
+ * DEFINITION: the image equals, byte for byte, zj_resize_filtered_device applied to the 3-channel u8 image E with
+ * E[c] = zj_cmyk_to_rgb_device(A[c], K): A the displayed u8 crop the same call writes for a three-component frame made of the
+ * file's components 1-3 (their tables, the file's sampling, the decoder's flags and layout), decoded as ZJ_CS_RGB when the
+ * Adobe transform is 2 (YCCK) and as ZJ_CS_YCBCR -- the stored samples, up-sampled, always HWC -- otherwise; K the displayed
+ * u8 crop of the GRAYSCALE decode of a one-component frame made of component 4; `inverted` set when an Adobe segment was
+ * seen (Adobe files store complemented samples; without the segment the samples are complemented first, Pillow's rule);
+ * same filter, prescale pick, orientation, flip, scale, bias, dtype and tensor layout.  One- and three-component files: the
+ * flag does nothing (their Adobe segment stays ignored), so a loader sets it once.  In the batch call a four-component file
+ * goes through its single-file call; the files around it keep the bytes they have without it. */
+#define ZJ_FLAG_CMYK_TO_RGB 32u
 #define ZJ_LAYOUT_HWC 0u
 #define ZJ_LAYOUT_CHW 1u
 
@@ -398,6 +425,18 @@ ZJ_API int zj_orient_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, c
  * `stream` (NULL: the context's); nothing is launched after an argument error. */
 ZJ_API int zj_gray_to_rgb_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
                                  int out_layout, uint8_t *const *d_out, const unsigned *out_pitch, void *stream);
+/* n 3-channel u8 images a and n u8 planes k of the same sizes, in device memory -> 3-channel u8 images with
+ * out[c] = (a[c] * k + 127) / 255 (integer division): Pillow's CMYK -> RGB on complemented samples.
+ * inverted[i] (NULL: all 0) non-zero: image i's samples are used as stored (an Adobe file, whose samples are complemented
+ * already); 0: a and k are complemented (x ^ 255) first.  in_wh (width and height, 1..65535); `layout` of a and of the output,
+ * ZJ_LAYOUT_HWC or ZJ_LAYOUT_CHW (three planes, pitch x height apart); a_pitch, k_pitch, out_pitch bytes between rows (NULL or
+ * 0: tight; the padding is never read or written).  Any addresses and pitches.  d_out[i] == d_a[i] with equal pitches is
+ * allowed (a lane reads its run before it writes it); any other overlap of an output with an input is the caller's error.
+ * One launch per 96 images (40 bytes of kernel arguments each), whatever their sizes.  Asynchronous on `stream` (NULL: the
+ * context's); nothing is launched after an argument error. */
+ZJ_API int zj_cmyk_to_rgb_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_a, const uint8_t *const *d_k, const unsigned *in_wh,
+                                 const unsigned *a_pitch, const unsigned *k_pitch, int layout, const uint8_t *inverted,
+                                 uint8_t *const *d_out, const unsigned *out_pitch, void *stream);
 /* zj_decode_crops_resized_prescaled_device for frames that are to be shown turned: orientation[f] = 1..8 per frame (NULL: all
  * 1, and the call IS the prescaled one), windows in DISPLAYED pixels of each frame.  The output is zj_resize_filtered_device
  * applied to EXACTLY the displayed form of the u8 crop zj_decode_crops_device writes for the stored window (zj_orient_window)
@@ -495,7 +534,7 @@ typedef struct zj_options {      /* zero = reference default */
                                     decoder keeps its helper threads until zj_decoder_free; 1 = strictly serial */
     int32_t pinned_planes;       /* non-zero: coefficient planes live in pinned host memory (DMA without staging) */
     uint32_t flags;              /* ZJ_FLAG_* for the pixel path (0 = the reference's bytes), see zj_frame_desc;
-                                    + ZJ_FLAG_FULL_AC_VALUES for the front-end itself */
+                                    + ZJ_FLAG_FULL_AC_VALUES and ZJ_FLAG_CMYK_TO_RGB for the front-end itself */
     uint32_t out_layout;         /* ZJ_LAYOUT_HWC (0) or ZJ_LAYOUT_CHW */
     int32_t entropy;             /* where baseline Huffman scans are decoded: ZJ_ENTROPY_CPU (0), ZJ_ENTROPY_GPU (scans of
                                     32 KB and more and 16 bits per block and more on the device, the rest and everything
@@ -573,6 +612,15 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder *d,
  * payload begins "Exif\0\0" decides: TIFF header (II or MM), IFD0, the entry with tag 0x0112, type SHORT, count 1.  Anything
  * else (a bad header, an offset or entry past the segment or the buffer, another type or count, a value outside 1..8) is 1. */
 ZJ_API int zj_decoder_orientation(const zj_decoder *d);
+/* the Adobe APP14 segment of the file whose headers were read last: -1 when none was seen (or before any file), else its
+ * transform byte (0: CMYK / RGB as stored, 1: YCbCr, 2: YCCK).  Read for every file; it decides something for four-component
+ * files only (ZJ_FLAG_CMYK_TO_RGB). */
+ZJ_API int zj_decoder_adobe_transform(const zj_decoder *d);
+/* plane `comp` (0 .. components - 1) of the last file, after a successful CPU decode (zj_decoder_decode_coefficients, or
+ * zj_decoder_prepare that left no scan for the device): the plane, its length in int16 elements and its size in blocks.
+ * Any output pointer may be NULL.  ZJ_ERR_ARG: no such component, or no decoded coefficients. */
+ZJ_API int zj_decoder_plane(const zj_decoder *d, int comp, const int16_t **plane, size_t *len, unsigned *blocks_w,
+                            unsigned *blocks_h);
 /* zj_decoder_finish_pixels_device with the file's orientation applied (what an EXIF-aware image loader returns): the whole
  * DISPLAYED image, tight, in the decoder's colour space and layout; *out_w x *out_h (optional) its size.  Orientation 1
  * decodes straight into d_out; the others decode into a buffer of the context and are turned from there.  RGBA / RGBX are

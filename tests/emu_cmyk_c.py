@@ -1,0 +1,55 @@
+"""ctypes binding of the CPU emulation of the CMYK-to-RGB kernel (tests/emu_cmyk).  TEST ONLY."""
+import ctypes as C
+import os
+
+import numpy as np
+
+import emu_build
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+_LIB = None
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        so = os.path.join(HERE, "emu_cmyk", "libzjemucmyk.so")
+        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
+        srcs = [os.path.join(HERE, "emu_cmyk", "zj_emu_cmyk.cpp"), os.path.join(csrc, "zj_cmyk.h"), os.path.join(csrc, "zj_expand.h"),
+                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
+        emu_build.build(so, srcs, "-O2")
+        L = C.CDLL(so)
+        L.zjck_combine.restype = C.c_longlong
+        L.zjck_combine.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        _LIB = L
+    return _LIB
+
+
+def run():
+    return lib().zjck_run()
+
+
+def batch():
+    return lib().zjck_batch()
+
+
+def params_bytes():
+    return lib().zjck_params_bytes()
+
+
+def combine(a_addrs, k_addrs, sizes, a_pitches, k_pitches, chw, inverted, arena, out_offsets, out_pitches):
+    """The launches of one call: a_addrs / k_addrs = addresses of the images' and the planes' first bytes, sizes = (w, h),
+    outputs at arena[out_offsets[i]:] at out_pitches[i].  Returns (write map of the arena, stores that fell outside it)."""
+    n = len(a_addrs)
+    arr = lambda v: (C.c_uint * n)(*v)
+    wh = (C.c_uint * (2 * n))(*[v for sz in sizes for v in sz])
+    inv = (C.c_uint8 * n)(*[1 if v else 0 for v in inverted])
+    outs = (C.c_void_p * n)(*[arena.ctypes.data + off for off in out_offsets])
+    wmap = np.zeros(arena.size, np.uint8)
+    outside = lib().zjck_combine(n, (C.c_void_p * n)(*a_addrs), (C.c_void_p * n)(*k_addrs), wh, arr(a_pitches), arr(k_pitches),
+                                 1 if chw else 0, inv, outs, arr(out_pitches), C.c_void_p(arena.ctypes.data), arena.size,
+                                 C.c_void_p(wmap.ctypes.data))
+    assert outside >= 0, "the emulation refused its arguments"
+    return wmap, outside

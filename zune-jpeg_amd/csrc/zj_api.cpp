@@ -17,6 +17,7 @@
 #include "zj_mixed_launch.h"
 #include "zj_orient_launch.h"
 #include "zj_expand_launch.h"
+#include "zj_cmyk_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
 #include "zj_rzgroup.h"
@@ -962,6 +963,33 @@ int expand_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
     return ZJ_OK;
 }
 
+// image pairs [0, n) -> out[c] = (a[c] * k + 127) / 255, launches of up to CMYK_BATCH pairs; wh: w, h pairs, the
+// pitches resolved, inverted[i] != 0: the samples are used as stored, else complemented first
+int cmyk_launches(zj_ctx* c, size_t n, const uint8_t* const* a, const uint8_t* const* k, const unsigned* wh, const unsigned* a_pitch,
+                  const unsigned* k_pitch, int chw, const uint8_t* inverted, uint8_t* const* out, const unsigned* out_pitch,
+                  hipStream_t st)
+{
+    CmykParams p{};
+    for (size_t f0 = 0; f0 < n; f0 += CMYK_BATCH) {
+        const int m = (int)(n - f0 < (size_t)CMYK_BATCH ? n - f0 : (size_t)CMYK_BATCH);
+        p.nimg = m;
+        for (int i = 0; i < CMYK_BATCH / 32; i++) p.inverted[i] = 0;
+        for (int i = 0; i < CMYK_BATCH; i++) {
+            const size_t f = f0 + i;
+            p.a[i] = i < m ? (uint64_t)(uintptr_t)a[f] : 0;
+            p.k[i] = i < m ? (uint64_t)(uintptr_t)k[f] : 0;
+            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
+            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
+            p.a_pitch[i] = i < m ? a_pitch[f] : 0;
+            p.k_pitch[i] = i < m ? k_pitch[f] : 0;
+            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
+            if (i < m && inverted[f]) p.inverted[i >> 5] |= 1u << (i & 31);
+        }
+        ZJ_HIP(c, launch_cmyk(chw, p, st));
+    }
+    return ZJ_OK;
+}
+
 // The end of the launch group [g0, g1) of a resized call, its crops written into buf where `place` says (zj_rzgroup.h):
 // the turned frames, gathered: crop -> its displayed form, tight, in the second region; the resize over the images place[f].in
 // names, in order, into images [g0, g1) of the output; the event that orders the buffer's reuse.
@@ -1459,6 +1487,46 @@ int zjint_gray_to_rgb_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, 
     if (!c) return ZJ_ERR_ARG;
     const unsigned wh[2] = {w, h};
     int rc = zj_gray_to_rgb_device(c, 1, &in, wh, nullptr, out_layout, &d_out, nullptr, nullptr);
+    if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+/* ---- CMYK to RGB ---------------------------------------------------------------- */
+int zj_cmyk_to_rgb_device(zj_ctx* c, size_t n, const uint8_t* const* d_a, const uint8_t* const* d_k, const unsigned* in_wh,
+                          const unsigned* a_pitch, const unsigned* k_pitch, int layout, const uint8_t* inverted,
+                          uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_a || !d_k || !in_wh || !d_out) return ZJ_ERR_ARG;
+    if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    const unsigned bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> ap(n), kp(n), op(n);
+    std::vector<uint8_t> inv(n, 0);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_a[f] || !d_k[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        ap[f] = a_pitch && a_pitch[f] ? a_pitch[f] : w * bpp;
+        kp[f] = k_pitch && k_pitch[f] ? k_pitch[f] : w;
+        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
+        if (ap[f] < w * bpp || kp[f] < w || op[f] < w * bpp || ap[f] > (1u << 24) || kp[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
+        if (inverted) inv[f] = inverted[f] ? 1 : 0;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return cmyk_launches(c, n, d_a, d_k, in_wh, ap.data(), kp.data(), layout == ZJ_LAYOUT_CHW, inv.data(), d_out, op.data(), st);
+}
+
+// Library-internal (zj_jpeg.cpp: the single-file resized crop of a four-component file): one tight image combined in place with
+// one tight plane on the context stream; the context's crop buffer counts as read by it; synchronised
+int zjint_cmyk_to_rgb_one(zj_ctx* c, uint8_t* a, const uint8_t* k, unsigned w, unsigned h, int layout, int inverted)
+{
+    if (!c) return ZJ_ERR_ARG;
+    const unsigned wh[2] = {w, h};
+    const uint8_t inv = inverted ? 1 : 0;
+    const uint8_t* ca = a;
+    int rc = zj_cmyk_to_rgb_device(c, 1, &ca, &k, wh, nullptr, nullptr, layout, &inv, &a, nullptr, nullptr);
     if (rc) return rc;
     if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
     if ((rc = resize_scratch_done(c, c->stream))) return rc;

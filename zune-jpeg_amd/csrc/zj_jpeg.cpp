@@ -464,7 +464,7 @@ struct zj_decoder {
     const uint8_t* src = nullptr;        // the caller's file (must stay valid until the pixels are finished): the CPU
     size_t src_len = 0;                  // walker decodes it if the device hands the scan back
     uint32_t flags = 0, out_layout = 0; // extensions of the pixel path, passed through to zj_frame_desc
-    PlaneStore store[3];
+    PlaneStore store[4];   // (the fourth: component 4 of a four-component file, ZJ_FLAG_CMYK_TO_RGB)
     ~zj_decoder() { for (auto& st : store) st.release(); blob_store.release(); }
     // state
     std::string err;
@@ -473,6 +473,8 @@ struct zj_decoder {
     int restart_interval = 0;
     int orientation = 0;     // EXIF Orientation of the last file whose headers were read, 1..8 (1: none said); 0: no file yet
     bool exif_seen = false;  // an APP1 segment with the Exif signature has been met: it decided, later ones are ignored
+    int adobe_transform = -1; // the transform byte of the file's Adobe APP14 segment, -1: none seen
+    bool adobe_short = false; // an APP14 segment with the Adobe signature ended before its transform byte
     int seen_sof = 0, scans = 0;
     bool coef_valid = false; // the planes hold the coefficients of a complete, successful decode_all
     long long hist_retries = 0; // images decoded a second time for it (tests)
@@ -482,9 +484,9 @@ struct zj_decoder {
     uint16_t qt[4][64];
     bool qt_present[4] = {false, false, false, false};
     Huff dc[4], ac[4];
-    Comp comps[3];
+    Comp comps[4];
     // current scan
-    int ns = 0, order[3] = {0, 0, 0}, ss = 0, se = 63, ah = 0, al = 0;
+    int ns = 0, order[4] = {0, 0, 0, 0}, ss = 0, se = 63, ah = 0, al = 0;
     uint32_t eobrun = 0;
     int dri_parallel_segments = 0; // restart segments the last baseline scan decoded concurrently (0 = serial walk)
     long long par_scan_mcus = 0;   // MCUs of the last baseline scan decoded by scan_baseline_parallel (no restart markers; 0: serial)
@@ -591,20 +593,21 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
     if (w == 0 || h == 0) return fail(d, ZJ_ERR_ZERO, "Image width or height is set to zero, cannot continue");
     if (nc == 0) return fail(d, ZJ_ERR_SOF, "Number of components cannot be zero.");
     if (len != 8 + 3 * nc) return fail(d, ZJ_ERR_SOF, "Length of start of frame differs from expected " + std::to_string(8 + 3 * nc) + ",value is " + std::to_string(len));
-    if (nc != 1 && nc != 3) return fail(d, ZJ_ERR_SOF, "Invalid components. Found " + std::to_string(nc) + ", expected either 1 or 3");
+    const bool four = nc == 4 && (d->flags & ZJ_FLAG_CMYK_TO_RGB); // (without the flag: refused as ever)
+    if (nc != 1 && nc != 3 && !four) return fail(d, ZJ_ERR_SOF, "Invalid components. Found " + std::to_string(nc) + ", expected either 1 or 3");
     d->width = w; d->height = h; d->ncomp = nc; d->progressive = progressive;
     d->h_max = d->v_max = 1;
     for (int i = 0; i < nc; i++) {
         int id, hv, tq;
         if (!c.u8(id) || !c.u8(hv) || !c.u8(tq)) return fail(d, ZJ_ERR_FORMAT, "Could not read component data");
-        if (id < 1 || id > 3) return fail(d, ZJ_ERR_FORMAT, "Unknown component id found," + std::to_string(id) + ", expected value between 1 and 3\nNote I and Q components are not supported yet");
+        if (!four && (id < 1 || id > 3)) return fail(d, ZJ_ERR_FORMAT, "Unknown component id found," + std::to_string(id) + ", expected value between 1 and 3\nNote I and Q components are not supported yet");
         Comp& cm = d->comps[i];
         cm = Comp();
         cm.id = id; cm.h = hv >> 4; cm.v = hv & 15; cm.tq = tq;
         if (tq >= 4) return fail(d, ZJ_ERR_FORMAT, "Too large quantization number :" + std::to_string(tq) + ", expected value between 0 and 4");
         auto pow2 = [](int x) { return x > 0 && (x & (x - 1)) == 0; };
-        if (!pow2(cm.h)) return fail(d, ZJ_ERR_FORMAT, "Horizontal sample is not a power of two(" + std::to_string(cm.h) + ") cannot decode");
-        if (!pow2(cm.v)) return fail(d, ZJ_ERR_FORMAT, "Vertical sub-sample is not power of two(" + std::to_string(cm.v) + ") cannot decode");
+        if (!four && !pow2(cm.h)) return fail(d, ZJ_ERR_FORMAT, "Horizontal sample is not a power of two(" + std::to_string(cm.h) + ") cannot decode");
+        if (!four && !pow2(cm.v)) return fail(d, ZJ_ERR_FORMAT, "Vertical sub-sample is not power of two(" + std::to_string(cm.v) + ") cannot decode");
         if (cm.h > d->h_max) d->h_max = cm.h;
         if (cm.v > d->v_max) d->v_max = cm.v;
     }
@@ -614,6 +617,17 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
         d->comps[0].h = d->comps[0].v = 1;
         d->h_max = d->v_max = 1;
     }
+    if (four) {
+        // components 2 and 3 at (1,1), components 1 and 4 both at (h_max, v_max) of one of the four known modes
+        const Comp* const cs = d->comps;
+        if (d->h_max > 2 || d->v_max > 2 || cs[1].h != 1 || cs[1].v != 1 || cs[2].h != 1 || cs[2].v != 1 || cs[0].h != d->h_max ||
+            cs[0].v != d->v_max || cs[3].h != d->h_max || cs[3].v != d->v_max) {
+            std::string t;
+            for (int i = 0; i < 4; i++) t += std::string(i ? " " : "") + "(" + std::to_string(cs[i].h) + "," + std::to_string(cs[i].v) + ")";
+            return fail(d, ZJ_ERR_UNSUPPORTED, "Unsupported sampling of a four-component image: " + t +
+                                                   ", expected (h,v) (1,1) (1,1) (h,v) with h and v 1 or 2");
+        }
+    }
     d->mcu_x = (w + 8 * d->h_max - 1) / (8 * d->h_max);
     d->mcu_y = (h + 8 * d->v_max - 1) / (8 * d->v_max);
     for (int i = 0; i < nc; i++) {
@@ -622,14 +636,17 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
         memcpy(cm.q, d->qt[cm.tq], sizeof cm.q);
         cm.bw = d->mcu_x * cm.h;
         cm.bh = d->mcu_y * cm.v;
+        // (component 4 in the layout of a one-component frame of this size: its blocks in the padding of a 16-pixel MCU are
+        // decoded and dropped, and the pixel stages take the plane as an ordinary GRAYSCALE frame)
+        if (four && i == 3) { cm.bw = (w + 7) / 8; cm.bh = (h + 7) / 8; }
         cm.coef_len = (size_t)cm.bw * cm.bh * 64;
         cm.coef = nullptr; // ensure_planes(): a scan that goes to the device entropy stage never needs host planes
     }
-    if (progressive) { const int rc = ensure_planes(d); if (rc) return rc; }
+    if (progressive || four) { const int rc = ensure_planes(d); if (rc) return rc; }
     // the entropy decoder only writes non-zero coefficients.  Progressive scans accumulate into the planes, so
     // they are cleared up front (in parallel when large); a baseline scan clears each block right before it
     // decodes into it (one pass over memory instead of two) and scan_baseline clears whatever it did not reach
-    for (int i = 0; i < nc && progressive; i++) {
+    for (int i = 0; i < nc && (progressive || four); i++) { // (a four-component file's walk accumulates whatever its scans are)
         Comp& cm = d->comps[i];
         const size_t bytes = cm.coef_len * 2, piece = (size_t)4 << 20;
         const int n = (int)((bytes + piece - 1) / piece);
@@ -655,7 +672,7 @@ int parse_sos(zj_decoder* d, Cursor& c)
     int ls, ns;
     if (!c.u16(ls) || !c.u8(ns)) return fail(d, ZJ_ERR_SOS, "Could not read SOS");
     if (ls != 6 + 2 * ns) return fail(d, ZJ_ERR_SOS, "Bad SOS length,corrupt jpeg");
-    if (ns < 1 || ns > 3) return fail(d, ZJ_ERR_SOS, "Number of components in start of scan should be less than 3 but more than 0. Found " + std::to_string(ns));
+    if (ns < 1 || (ns > 3 && !(ns == 4 && d->seen_sof && d->ncomp == 4))) return fail(d, ZJ_ERR_SOS, "Number of components in start of scan should be less than 3 but more than 0. Found " + std::to_string(ns));
     if (!d->seen_sof || d->ncomp == 0) return fail(d, ZJ_ERR_SOF, "Number of components cannot be zero.");
     if (ns > d->ncomp) return fail(d, ZJ_ERR_FORMAT, "Number of scans " + std::to_string(ns) + " cannot be greater than number of components, " + std::to_string(d->ncomp));
     bool seen[4] = {false, false, false, false};
@@ -748,6 +765,12 @@ int parse_headers(zj_decoder* d, Cursor& c, bool first)
                 if (m == 0xE1 && !d->exif_seen) { // the first Exif segment decides the orientation
                     const int o = exif_orientation(c.p, (size_t)(c.end - c.p < l - 2 ? c.end - c.p : l - 2));
                     if (o > 0) { d->orientation = o; d->exif_seen = true; }
+                }
+                if (m == 0xEE) { // Adobe: 5 signature bytes, version, flags0, flags1 (2 bytes each), transform
+                    const size_t n = (size_t)(c.end - c.p < l - 2 ? c.end - c.p : l - 2);
+                    if (n >= 5 && memcmp(c.p, "Adobe", 5) == 0) {
+                        if (n >= 12) d->adobe_transform = c.p[11]; else d->adobe_short = true;
+                    }
                 }
                 if (c.end - c.p < l - 2) c.p = c.end; else c.p += l - 2;
             }
@@ -2233,6 +2256,129 @@ int scan_progressive(zj_decoder* d, BitReader& br)
     return ZJ_OK;
 }
 
+// ---- four-component files (ZJ_FLAG_CMYK_TO_RGB) ----------------------------------------------------------
+// A plain T.81 walk of its own, serial: the reference has no four-component path, so there is no reader of its to imitate --
+// no six-bit cut of fast-AC values, no short DC reads, no early exit at EOI -- and the walkers above stay what they are for
+// one- and three-component files.  Sequential (SOF0) and progressive (SOF2) scans of 1..4 components, accumulated into planes
+// that parse_sof cleared; a block of component 4 that lies outside its plane (the padding of a 16-pixel MCU) is decoded into
+// a buffer and dropped.
+int four_block(zj_decoder* d, BitReader& br, Comp& cm, int16_t* blk)
+{
+    if (!d->progressive) {
+        const int s = br.decode(d->dc[cm.td & 3]);
+        if (s < 0 || s > 11) return fail(d, ZJ_ERR_HUFFMAN, "Bad Huffman code in DC");
+        const int32_t diff = s ? extend(br.get(s), s) : 0;
+        cm.dc_pred = (int32_t)((uint32_t)cm.dc_pred + (uint32_t)diff);
+        blk[0] = (int16_t)cm.dc_pred;
+        const Huff& ha = d->ac[cm.ta & 3];
+        for (int k = 1; k < 64;) {
+            const int rs = br.decode(ha);
+            if (rs < 0) return fail(d, ZJ_ERR_HUFFMAN, "Bad Huffman code in AC");
+            const int r = rs >> 4, sz = rs & 15;
+            if (sz) {
+                k += r;
+                if (k > 63) return fail(d, ZJ_ERR_HUFFMAN, "AC run past the end of the block");
+                blk[kUnZigzag[k++]] = (int16_t)extend(br.get(sz), sz);
+            } else if (r == 15) k += 16;
+            else break;
+        }
+        return ZJ_OK;
+    }
+    if (d->ss == 0) {
+        if (d->ah) { dc_refine(d, br, blk); return ZJ_OK; }
+        const int s = br.decode(d->dc[cm.td & 3]);
+        if (s < 0 || s > 11) return fail(d, ZJ_ERR_HUFFMAN, "Bad Huffman code in DC");
+        const int32_t diff = s ? extend(br.get(s), s) : 0;
+        cm.dc_pred = (int32_t)((uint32_t)cm.dc_pred + (uint32_t)diff);
+        blk[0] = (int16_t)((uint32_t)cm.dc_pred << d->al);
+        return ZJ_OK;
+    }
+    const Huff& ha = d->ac[cm.ta & 3];
+    if (d->ah) return ac_refine(d, br, ha, blk);
+    if (d->eobrun > 0) { d->eobrun--; return ZJ_OK; }
+    for (int k = d->ss; k <= d->se;) {
+        const int rs = br.decode(ha);
+        if (rs < 0) return fail(d, ZJ_ERR_HUFFMAN, "Bad Huffman code in AC");
+        const int r = rs >> 4, sz = rs & 15;
+        if (sz) {
+            k += r;
+            if (k > d->se) return fail(d, ZJ_ERR_HUFFMAN, "AC run past the end of the band");
+            blk[kUnZigzag[k++]] = (int16_t)(extend(br.get(sz), sz) * (1 << d->al));
+        } else if (r == 15) k += 16;
+        else {
+            d->eobrun = (1u << r) - 1;
+            if (r) d->eobrun += (uint32_t)br.get(r);
+            break;
+        }
+    }
+    return ZJ_OK;
+}
+
+// the restart marker that must follow a restart interval (T.81 E.2.4): found -- the predictions start over; an EOI ends the
+// walk where the caller's loops end; no marker there, or any other, is an error
+int four_restart(zj_decoder* d, BitReader& br, int& todo)
+{
+    todo = d->restart_interval;
+    if (br.nbits < 64) br.fill();
+    if (br.marker >= 0xD0 && br.marker <= 0xD7) {
+        br.reset();
+        for (int i = 0; i < 4; i++) d->comps[i].dc_pred = 0;
+        d->eobrun = 0;
+    } else if (br.marker == 0) {
+        return fail(d, ZJ_ERR_MCU, "Restart marker missing behind a restart interval, corrupt jpeg");
+    } else if (br.marker != 0xD9) {
+        return fail(d, ZJ_ERR_MCU, "Marker found in bitstream, possibly corrupt jpeg");
+    }
+    return ZJ_OK;
+}
+
+int scan_four(zj_decoder* d, BitReader& br)
+{
+    if (!d->progressive) { d->ss = 0; d->se = 63; d->ah = d->al = 0; }
+    else if (d->ss > d->se || (d->ss == 0 && d->se != 0) || (d->ss != 0 && d->ns != 1))
+        return fail(d, ZJ_ERR_HUFFMAN, "Can't merge DC and AC corrupt jpeg");
+    for (int i = 0; i < d->ns; i++) {
+        const Comp& cm = d->comps[d->order[i]];
+        const bool need_dc = d->ss == 0 && d->ah == 0, need_ac = !d->progressive || d->ss != 0;
+        if (need_dc && !d->dc[cm.td & 3].present) return fail(d, ZJ_ERR_FORMAT, "Huffman table at index  " + std::to_string(cm.td) + " not initialized");
+        if (need_ac && !d->ac[cm.ta & 3].present) return fail(d, ZJ_ERR_FORMAT, "Huffman table at index  " + std::to_string(cm.ta) + " not initialized");
+    }
+    for (int i = 0; i < 4; i++) d->comps[i].dc_pred = 0;
+    d->eobrun = 0;
+    int todo = d->restart_interval ? d->restart_interval : 0x7fffffff;
+    alignas(64) int16_t dropped[64];
+    if (d->ns == 1) {
+        // a scan of one component: the blocks that cover the image at that component's sampling (T.81 A.2.2)
+        Comp& cm = d->comps[d->order[0]];
+        const int cw = (d->width * cm.h + d->h_max - 1) / d->h_max, chh = (d->height * cm.v + d->v_max - 1) / d->v_max;
+        const int bw = (cw + 7) / 8, bh = (chh + 7) / 8; // (never more than the plane has)
+        for (int by = 0; by < bh; by++)
+            for (int bx = 0; bx < bw; bx++) {
+                int rc = four_block(d, br, cm, block_at(cm, bx, by));
+                if (rc) return rc;
+                if (--todo == 0 && !(by == bh - 1 && bx == bw - 1) && (rc = four_restart(d, br, todo))) return rc; // (none behind the last)
+            }
+        return ZJ_OK;
+    }
+    for (int my = 0; my < d->mcu_y; my++)
+        for (int mx = 0; mx < d->mcu_x; mx++) {
+            for (int ci = 0; ci < d->ns; ci++) {
+                Comp& cm = d->comps[d->order[ci]];
+                for (int v = 0; v < cm.v; v++)
+                    for (int h = 0; h < cm.h; h++) {
+                        const int bx = mx * cm.h + h, by = my * cm.v + v;
+                        int16_t* blk = dropped;
+                        if (bx < cm.bw && by < cm.bh) blk = block_at(cm, bx, by);
+                        else memset(dropped, 0, sizeof dropped);
+                        const int rc = four_block(d, br, cm, blk);
+                        if (rc) return rc;
+                    }
+            }
+            if (--todo == 0 && !(my == d->mcu_y - 1 && mx == d->mcu_x - 1)) { const int rc = four_restart(d, br, todo); if (rc) return rc; }
+        }
+    return ZJ_OK;
+}
+
 // after a scan: find the next marker (mcu_prog.rs:436-472)
 // ---- the scan as the GPU entropy stage wants it (zj_huff.h) --------------------------------------------------------
 // Two-level decoding table: 2^B first-level entries indexed by the next B bits (B = 9 for DC, 11 for AC tables); codes
@@ -2541,16 +2687,18 @@ int decode_all_once(zj_decoder* d, const uint8_t* buf, size_t len, bool headers_
 {
     d->err.clear(); d->err_code = 0; d->seen_sof = 0; d->scans = 0; d->restart_interval = 0;
     d->coef_valid = false; d->scan_ready = false; d->src = nullptr; d->src_len = 0;
-    d->orientation = 1; d->exif_seen = false;
+    d->orientation = 1; d->exif_seen = false; d->adobe_transform = -1; d->adobe_short = false;
     for (int i = 0; i < 4; i++) { d->qt_present[i] = false; d->dc[i].present = false; d->ac[i].present = false; }
     Cursor c{buf, buf + len};
     int rc = parse_headers(d, c, true);
     if (rc) return rc;
+    if (d->seen_sof && d->ncomp == 4 && d->adobe_short) return fail(d, ZJ_ERR_FORMAT, "Adobe APP14 segment is too short to hold its transform byte");
     if (headers_only) return ZJ_OK;
     if (!d->seen_sof) return fail(d, ZJ_ERR_SOF, "Number of components cannot be zero.");
+    const bool four = d->ncomp == 4;
     BitReader br;
     br.p = c.p; br.end = c.end; br.istart = c.p;
-    if (!d->progressive) {
+    if (!d->progressive && !four) {
         if (for_device && d->entropy && prepare_scan(d, c.p, c.end) == ZJ_OK) {
             d->scans = 1; d->src = buf; d->src_len = len;
             return ZJ_OK;
@@ -2573,7 +2721,7 @@ int decode_all_once(zj_decoder* d, const uint8_t* buf, size_t len, bool headers_
     for (;;) {
         if (++d->scans > d->max_scans) return fail(d, ZJ_ERR_FORMAT, "Too many scans, exceeded limit of " + std::to_string(d->max_scans));
         br.reset();
-        rc = scan_progressive(d, br);
+        rc = four ? scan_four(d, br) : scan_progressive(d, br);
         if (rc) return rc;
         // markers between scans: DHT / SOS / EOI (mcu_prog.rs:90-126)
         for (;;) {
@@ -2626,6 +2774,17 @@ void zj_decoder_free(zj_decoder* d) { delete d; }
 const char* zj_decoder_error(const zj_decoder* d) { return d ? d->err.c_str() : ""; }
 int zj_decoder_parallel_segments(const zj_decoder* d) { return d ? d->dri_parallel_segments : 0; }
 int zj_decoder_orientation(const zj_decoder* d) { return d ? d->orientation : 0; }
+int zj_decoder_adobe_transform(const zj_decoder* d) { return d ? d->adobe_transform : -1; }
+int zj_decoder_plane(const zj_decoder* d, int comp, const int16_t** plane, size_t* len, unsigned* blocks_w, unsigned* blocks_h)
+{
+    if (!d || !d->seen_sof || d->err_code || !d->coef_valid || comp < 0 || comp >= d->ncomp || !d->comps[comp].coef) return ZJ_ERR_ARG;
+    const Comp& cm = d->comps[comp];
+    if (plane) *plane = cm.coef;
+    if (len) *len = cm.coef_len;
+    if (blocks_w) *blocks_w = (unsigned)cm.bw;
+    if (blocks_h) *blocks_h = (unsigned)cm.bh;
+    return ZJ_OK;
+}
 int64_t zj_decoder_parallel_mcus(const zj_decoder* d) { return d ? (int64_t)d->par_scan_mcus : 0; }
 int zj_decoder_set_num_threads(zj_decoder* d, int threads)
 {   // Decoder::set_num_threads (src/decoder.rs:591-603): "Cannot set zero threads to decode image"
@@ -2721,6 +2880,8 @@ __attribute__((weak)) int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigne
                                            uint8_t* d_out);
 // ... and one plane expanded to an RGB image with R = G = B
 __attribute__((weak)) int zjint_gray_to_rgb_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int out_layout, uint8_t* d_out);
+// ... and one image combined in place with one plane, (a * k + 127) / 255
+__attribute__((weak)) int zjint_cmyk_to_rgb_one(zj_ctx* c, uint8_t* a, const uint8_t* k, unsigned w, unsigned h, int layout, int inverted);
 
 // ... and the resized crops of several files' planes in host memory, each of its own geometry
 __attribute__((weak)) int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
@@ -2734,12 +2895,15 @@ __attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, 
                                              int planes_on_device, int scale_log2, unsigned x, unsigned yy, unsigned w, unsigned h,
                                              uint8_t* d_out, unsigned out_pitch);
 
+static const char* const kFourOnlyResized = "four-component files are finished by the resized-crop calls only (ZJ_FLAG_CMYK_TO_RGB)";
+
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
     if (!d || !ctx || !out) return ZJ_ERR_ARG;
     // read_headers alone allocates the planes but decodes nothing into them: only a complete decode_all (or a prepared
     // scan) counts
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
     // grayscale JPEG decoded to RGB: the reference converts nothing and returns zeros (worker.rs:131)
@@ -2848,6 +3012,7 @@ static int finish_window(zj_decoder* d, zj_ctx* ctx, bool reduced, int k, unsign
 {
     using namespace zj;
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
     if (reduced && (k < 1 || k > 3)) return fail(d, ZJ_ERR_ARG, "scale_log2 is 1, 2 or 3");
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
@@ -2922,6 +3087,16 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
     if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     fill_info(d, nullptr, &fd);
+    if (d->ncomp == 4) {
+        // a four-component file shown as RGB: fd is the descriptor of A, the three-component frame made of
+        // the file's components 1-3 -- converted when the file is YCCK, the stored samples otherwise
+        if (d->out_colorspace != ZJ_CS_RGB) return fail(d, ZJ_ERR_UNSUPPORTED, "ZJ_FLAG_CMYK_TO_RGB gives RGB: a four-component file needs a decoder with out_colorspace ZJ_CS_RGB");
+        if (!zjint_cmyk_to_rgb_one || !zjint_crop_frame || !zjint_scaled_frame) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+        if (!d->coef_valid) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+        fd.in_components = 3;
+        fd.out_colorspace = d->adobe_transform == 2 ? ZJ_CS_RGB : ZJ_CS_YCBCR;
+        if (fd.out_colorspace == ZJ_CS_YCBCR) fd.out_layout = ZJ_LAYOUT_HWC; // (stored samples have the interleaved layout only)
+    }
     if (d->ncomp == 1 && (d->flags & ZJ_FLAG_GRAY_TO_RGB)) {
         if (d->out_colorspace == ZJ_CS_YCBCR) return fail(d, ZJ_ERR_UNSUPPORTED, "ZJ_FLAG_GRAY_TO_RGB gives RGB, not YCbCr");
         if (d->out_colorspace == ZJ_CS_RGB) { fd.out_colorspace = ZJ_CS_RGB; fd.flags |= ZJ_FLAG_GRAY_TO_RGB; }
@@ -2945,6 +3120,48 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
     return ZJ_OK;
 }
 
+// finish_resized for a four-component file, its arguments checked: fa the descriptor of A (resized_checks),
+// x, y, w, h the stored window, win the window the crop stage writes (at scale k: of the reduced frame).  In the context's
+// buffer: the crop of A, the crop of K behind it, turned: their displayed forms behind both; A's displayed image combined in
+// place with K's; the resize reads that.
+static int finish_resized_four(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& fa, int k, unsigned x, unsigned y, unsigned w, unsigned h,
+                               const unsigned win[4], int o, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                               const float* scale, const float* bias, int flip, int filter, void* d_out)
+{
+    using namespace zj;
+    zj_frame_desc fk = fa;
+    fk.in_components = 1; fk.out_colorspace = ZJ_CS_GRAYSCALE; fk.h_max = fk.v_max = 1;
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 64; i++) fk.qt[c][i] = d->comps[3].q[i];
+    const bool chw = fa.out_layout == ZJ_LAYOUT_CHW && fa.out_colorspace == ZJ_CS_RGB;
+    const int layout = chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
+    const size_t len_a = window_layout(&fa, win[2], win[3], 0).len, len_k = window_layout(&fk, win[2], win[3], 0).len;
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t off_k = up(len_a), off_a2 = up(off_k + len_k), off_k2 = up(off_a2 + len_a);
+    uint8_t* buf = nullptr;
+    int rc = zjint_resize_scratch(ctx, o != 1 ? off_k2 + len_k : off_k + len_k, &buf);
+    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    const Comp* const cs = d->comps;
+    rc = k ? zjint_scaled_frame(ctx, &fa, cs[0].coef, cs[1].coef, cs[2].coef, 0, k, win[0], win[1], win[2], win[3], buf, 0)
+           : zjint_crop_frame(ctx, &fa, cs[0].coef, cs[1].coef, cs[2].coef, 0, x, y, w, h, buf, 0);
+    if (!rc) rc = k ? zjint_scaled_frame(ctx, &fk, cs[3].coef, nullptr, nullptr, 0, k, win[0], win[1], win[2], win[3], buf + off_k, 0)
+                    : zjint_crop_frame(ctx, &fk, cs[3].coef, nullptr, nullptr, 0, x, y, w, h, buf + off_k, 0);
+    if (rc) return fail(d, rc, std::string(k ? "reduced decode: " : "crop: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    uint8_t *a = buf, *kk = buf + off_k;
+    unsigned dw = win[2], dh = win[3];
+    if (o != 1) {
+        orient_size(o, win[2], win[3], &dw, &dh);
+        rc = zjint_orient_one(ctx, a, win[2], win[3], 3, layout, o, buf + off_a2);
+        if (!rc) rc = zjint_orient_one(ctx, kk, win[2], win[3], 1, ZJ_LAYOUT_HWC, o, buf + off_k2);
+        if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+        a = buf + off_a2; kk = buf + off_k2;
+    }
+    rc = zjint_cmyk_to_rgb_one(ctx, a, kk, dw, dh, layout, d->adobe_transform >= 0);
+    if (rc) return fail(d, rc, std::string("CMYK to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    rc = zjint_resize_one(ctx, a, dw, dh, 3, layout, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
+    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+}
+
 static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
                           unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
                           void* d_out, size_t out_cap, size_t* out_len, int o = 1)
@@ -2957,6 +3174,7 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     const unsigned full[4] = {x, y, w, h};
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
+    if (d->ncomp == 4) return finish_resized_four(d, ctx, fd, k, x, y, w, h, win, o, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
     // (a gray file shown as RGB: the crop and its displayed form are the 1-channel images of the GRAYSCALE decode)
     const bool expand = gray_to_rgb(&fd);
     const zj_frame_desc sd = resized_stage_desc(&fd);
@@ -3035,8 +3253,9 @@ int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder* d, zj_ctx*
 }
 
 // Several prepared files of any sizes into one resized-crop tensor.  The files the CPU walker decoded go
-// through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan left for the device, and one
-// whose output is all zeros, is finished through the single-file call, which gives the same bytes.
+// through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan left for the device, one whose
+// output is all zeros, and a four-component file, is finished through the single-file call, which gives the
+// same bytes.
 int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* windows,
                                                        unsigned out_w, unsigned out_h, int dtype, int out_layout,
                                                        const float* scale, const float* bias, const uint8_t* flip, int filter,
@@ -3078,7 +3297,7 @@ int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, si
         const int kk = prescale_pick(w, h, out_w, out_h, max_prescale_log2);
         int ch = 0;
         if ((rcs[k] = resized_checks(d, kk, x, y, w, h, out_w, out_h, dtype, filter, img, nullptr, o, fds[k], ch))) continue;
-        if (d->scan_ready || !d->coef_valid || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
+        if (d->scan_ready || !d->coef_valid || d->ncomp == 4 || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
         py[k] = d->comps[0].coef;
         pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
         ori[k] = (uint8_t)o;
@@ -3107,6 +3326,7 @@ int zj_decoder_finish_pixels_oriented_device(zj_decoder* d, zj_ctx* ctx, uint8_t
     using namespace zj;
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
     const int ch = resize_channels(&fd);

@@ -64,6 +64,8 @@ FLAG_EDGE_REPLICATE = 4  # extension: horizontal chroma filter per row with repl
 FLAG_CORRECTED = 7
 FLAG_FULL_AC_VALUES = 8  # zj_options.flags only: the front-end yields AC values as coded (the reference cuts some to six bits)
 FLAG_GRAY_TO_RGB = 16    # resized crops only: a one-component frame / file asked for RGB gives R = G = B
+FLAG_CMYK_TO_RGB = 32    # decoder options only: four-component (Adobe CMYK / YCCK) files are accepted and the resized-crop
+                         # calls show them as RGB
 LAYOUT_HWC, LAYOUT_CHW = 0, 1
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8 = 0, 1, 2, 3  # zj_resize_device and the resized crops: the output's dtype
 TENSOR_NCHW, TENSOR_NHWC = 0, 1                          # ... and its layout
@@ -189,7 +191,7 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decoder_orientation", "zj_decoder_finish_pixels_oriented_device",
     "zj_decoder_finish_pixels_resized_crop_oriented_device",
     "zj_decode_crops_resized_mixed_device", "zj_decoder_finish_pixels_resized_crop_batch_device",
-    "zj_gray_to_rgb_device",
+    "zj_gray_to_rgb_device", "zj_cmyk_to_rgb_device", "zj_decoder_adobe_transform", "zj_decoder_plane",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -352,6 +354,9 @@ def lib():
     L.zj_orient_window.argtypes = [C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zj_orient_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.zj_gray_to_rgb_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.zj_cmyk_to_rgb_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.zj_decoder_adobe_transform.argtypes = [vp]
+    L.zj_decoder_plane.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(sz), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zj_decode_crops_resized_oriented_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
                                                           C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.zj_decoder_orientation.argtypes = [vp]
@@ -660,6 +665,23 @@ class Context:
         _check(lib().zj_gray_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), out_layout,
                                            (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_gray_to_rgb_device", self._h)
 
+    def cmyk_to_rgb_device(self, d_a, d_k, sizes, layout, d_out, inverted=None, a_pitches=None, k_pitches=None, out_pitches=None,
+                           stream=None):
+        """One 3-channel u8 image a and one u8 plane k each -> the 3-channel u8 image (a * k + 127) // 255
+        (zj_cmyk_to_rgb_device): d_a, d_k = device pointers, sizes = one (w, h) each, layout LAYOUT_HWC or
+        LAYOUT_CHW of a and of the output, d_out = one device pointer each (d_a[i] itself with the same pitch: in place);
+        inverted = one flag each (None: all 0): non-zero uses the samples as stored, 0 complements a and k first; pitches =
+        bytes between rows (None: tight).  Asynchronous on `stream`."""
+        n = len(d_a)
+        if len(d_k) != n or len(sizes) != n or len(d_out) != n or (inverted is not None and len(inverted) != n):
+            raise ValueError("one plane, size, inverted flag and output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+        inv = (C.c_uint8 * n)(*[1 if v else 0 for v in inverted]) if inverted is not None else None
+        _check(lib().zj_cmyk_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_a), (C.c_void_p * n)(*d_k), wh, pit(a_pitches),
+                                           pit(k_pitches), layout, inv, (C.c_void_p * n)(*d_out), pit(out_pitches), stream),
+               "zj_cmyk_to_rgb_device", self._h)
+
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
                                     bias=None, flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,
                                     interpolation="bilinear"):
@@ -918,7 +940,8 @@ class Decoder:
         rc = lib().zj_decoder_decode_coefficients(self._d, _ptr(b), b.size, C.byref(desc), ptrs, lens, C.byref(info))
         if rc:
             self._raise(rc)
-        planes = [np.ctypeslib.as_array(C.cast(ptrs[c], C.POINTER(C.c_int16)), shape=(lens[c],)) for c in range(info.components)]
+        planes = [np.ctypeslib.as_array(C.cast(ptrs[c], C.POINTER(C.c_int16)), shape=(lens[c],))
+                  for c in range(min(3, info.components))]  # (a four-component file: components 1-3; plane(3) gives the fourth)
         if copy:
             planes = [p.copy() for p in planes]
         self._info = info
@@ -992,6 +1015,21 @@ class Decoder:
     def orientation(self):
         """EXIF Orientation (1..8; 1: the file says nothing usable) of the file whose headers were read last; 0: none yet."""
         return int(lib().zj_decoder_orientation(self._d))
+
+    @property
+    def adobe_transform(self):
+        """The transform byte of the last file's Adobe APP14 segment (0: CMYK / as stored, 1: YCbCr, 2: YCCK); -1: none seen."""
+        return int(lib().zj_decoder_adobe_transform(self._d))
+
+    def plane(self, comp, copy=True):
+        """Coefficient plane `comp` (0 .. components - 1) of the last file after a CPU decode (zj_decoder_plane): an int16
+        array [blocks_h, blocks_w, 64], natural order (copy=False: a view, valid until the decoder's next call or its end)."""
+        p, n, bw, bh = C.c_void_p(), C.c_size_t(0), C.c_uint(0), C.c_uint(0)
+        rc = lib().zj_decoder_plane(self._d, int(comp), C.byref(p), C.byref(n), C.byref(bw), C.byref(bh))
+        if rc:
+            raise DecodeError(rc, "no such plane, or no decoded coefficients")
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(n.value,)).reshape(bh.value, bw.value, 64)
+        return a.copy() if copy else a
 
     def finish_pixels_resized_crop_device(self, x, y, w, h, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
                                           flip=False, antialias=False, max_prescale=1, apply_orientation=False,

@@ -214,6 +214,9 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     as the colour files.  WITHOUT the flag a one-component file is decoded as GRAYSCALE whatever the options ask for: its
     one channel lands in the first third of its 3-channel slot, the rest of the slot is not written, no error is raised,
     and the files around it are decoded one by one.  The flag does nothing for three-component files.
+    Four-component files (Adobe CMYK / YCCK): with options.flags | FLAG_CMYK_TO_RGB and out_colorspace RGB their images are
+    what Pillow's convert("RGB") shows, each finished through its single-file call; WITHOUT the flag such a
+    file is refused when it is prepared (DecodeError naming its index), as the reference refuses it.
     The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
     the stream the output is allocated under, synchronised before the call writes it."""
     import torch
@@ -386,6 +389,30 @@ def gray_to_rgb_tensor(ctx, images, out_layout="HWC", stream=None):
     _on_stream(s, cur, imgs)
     ctx.gray_to_rgb_device([im.data_ptr() for im in imgs], sizes, LAYOUT_CHW if out_layout == "CHW" else LAYOUT_HWC,
                            [o.data_ptr() for o in outs], pitches, None, s.cuda_stream)
+    return outs
+
+
+def cmyk_to_rgb_tensor(ctx, images, planes, layout="HWC", inverted=None, stream=None):
+    """u8 CUDA images a ([H, W, 3] "HWC" or [3, H, W] "CHW") and planes k ([H, W]) of the same sizes -> new contiguous tensors
+    (a * k + 127) // 255 in the same layout (zj_cmyk_to_rgb_device, DESIGN.md 3.12): Pillow's CMYK -> RGB.  inverted = one
+    flag per image (None: all False): True uses the samples as stored (Adobe files), False complements them first.  Rows may
+    be strided.  Streams as decode_to_tensor."""
+    import torch
+    if layout not in ("HWC", "CHW"):
+        raise ValueError("layout is 'HWC' or 'CHW'")
+    imgs, sizes, pitches, channels = _u8_images(images, layout)
+    ks, ksizes, kpitches, kch = _u8_images(planes, "HWC")
+    if channels != 3 or kch != 1 or sizes != ksizes:
+        raise ValueError("one 3-channel image and one plane of the same size per pair")
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        outs = [torch.empty((3, h, w) if layout == "CHW" else (h, w, 3), dtype=torch.uint8, device=dev) for w, h in sizes]
+    _on_stream(s, cur, imgs + ks)
+    ctx.cmyk_to_rgb_device([im.data_ptr() for im in imgs], [k.data_ptr() for k in ks], sizes,
+                           LAYOUT_CHW if layout == "CHW" else LAYOUT_HWC, [o.data_ptr() for o in outs], inverted, pitches,
+                           kpitches, None, s.cuda_stream)
     return outs
 
 
