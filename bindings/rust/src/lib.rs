@@ -25,6 +25,9 @@ pub const ZJ_FLAG_GRAY_TO_RGB: u32 = 16;
 /// zj_options.flags only: four-component (Adobe CMYK / YCCK) files are accepted and the resized-crop calls show them as RGB
 /// (DESIGN.md 3.12); without it such a file is refused at SOF as in the reference
 pub const ZJ_FLAG_CMYK_TO_RGB: u32 = 32;
+/// zj_options.flags only: three-component files of any sampling with factors 1, 2, 4, any ids, and stored-RGB files are accepted
+/// and the resized-crop calls show them as RGB; without it they are refused or shown as ever
+pub const ZJ_FLAG_ANY_SAMPLING: u32 = 64;
 pub const ZJ_LAYOUT_HWC: u32 = 0;
 pub const ZJ_LAYOUT_CHW: u32 = 1;
 pub const ZJ_DTYPE_F32: c_int = 0;
@@ -259,6 +262,9 @@ extern "C" {
     pub fn zj_cmyk_to_rgb_device(ctx: *mut zj_ctx, n: usize, d_a: *const *const u8, d_k: *const *const u8, in_wh: *const c_uint,
                                  a_pitch: *const c_uint, k_pitch: *const c_uint, layout: c_int, inverted: *const u8,
                                  d_out: *const *mut u8, out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
+    pub fn zj_planes_to_rgb_device(ctx: *mut zj_ctx, n: usize, d_p0: *const *const u8, d_p1: *const *const u8, d_p2: *const *const u8,
+                                   in_wh: *const c_uint, ratios: *const u8, pitches: *const c_uint, stored_rgb: c_int, layout: c_int,
+                                   d_out: *const *mut u8, out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
     pub fn zj_orient_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
                             channels: c_int, in_layout: c_int, orientation: *const u8, d_out: *const *mut u8,
                             out_pitch: *const c_uint, stream: *mut c_void) -> c_int;
@@ -282,6 +288,8 @@ extern "C" {
                                                               d_out: *mut c_void, out_cap: usize, rcs: *mut c_int) -> c_int;
     pub fn zj_decoder_orientation(d: *const zj_decoder) -> c_int;
     pub fn zj_decoder_adobe_transform(d: *const zj_decoder) -> c_int;
+    pub fn zj_decoder_stored_rgb(d: *const zj_decoder) -> c_int;
+    pub fn zj_decoder_component_sampling(d: *const zj_decoder, comp: c_int, h: *mut c_uint, v: *mut c_uint) -> c_int;
     pub fn zj_decoder_plane(d: *const zj_decoder, comp: c_int, plane: *mut *const i16, len: *mut usize, blocks_w: *mut c_uint,
                             blocks_h: *mut c_uint) -> c_int;
     pub fn zj_decoder_finish_pixels_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, d_out: *mut u8, out_cap: usize,

@@ -190,6 +190,32 @@ typedef struct zj_frame_desc {
  * flag does nothing (their Adobe segment stays ignored), so a loader sets it once.  In the batch call a four-component file
  * goes through its single-file call; the files around it keep the bytes they have without it. */
 #define ZJ_FLAG_CMYK_TO_RGB 32u
+/* Any sampling: three-component JPEGs the reference refuses -- 4:1:1 and 4:1:0 files, chroma that is not
+ * (1,1), component ids outside 1..3 -- and files whose samples are stored RGB, shown as RGB images.  zj_options.flags ONLY (on
+ * a zj_frame_desc it is an unknown bit, ZJ_ERR_ARG).  Without it every file gives the status and the text it always gave.
+ * With it a three-component SOF0 / SOF2 frame is accepted with any component ids and every h and v in {1, 2, 4} (any other
+ * factor: ZJ_ERR_UNSUPPORTED, the three (h,v) pairs in its text), so that every ratio rx = h_max / h, ry = v_max / v is 1, 2 or 4.
+ * A file is NON-STANDARD when its sampling is outside the four known modes (chroma (1,1) under luma (1,1) / (2,1) / (1,2) /
+ * (2,2)), or an id is outside 1..3, or it is STORED RGB: its Adobe APP14 segment says transform 0 (zj_decoder_stored_rgb;
+ * Pillow's save(keep_rgb=True) writes this).  A standard file goes through exactly the walkers and kernels it goes through
+ * without the flag, byte for byte.  A non-standard one is decoded by the serial T.81 walk of four-component files (the values
+ * the file codes, none of the reference reader's quirks; the parallel scan, restart threads, streaming and the device entropy
+ * stage are never entered, whatever zj_options.entropy says), and EVERY component's plane has the layout of a one-component
+ * frame of the component's own size: ceil(cw/8) x ceil(ch/8) blocks, cw = ceil(W h / h_max), ch = ceil(H v / v_max)
+ * (zj_decoder_plane, zj_decoder_component_sampling).  The zj_frame_desc filled for such a file does NOT describe a frame
+ * any frame-level call accepts.
+ * Such a file is finished by the RESIZED-CROP family only, by a decoder whose out_colorspace is ZJ_CS_RGB; every other finish
+ * call, zj_decoder_decode_buffer and the pool return ZJ_ERR_UNSUPPORTED.
+ * DEFINITION (bit-exact): the image is zj_resize_filtered_device applied to the displayed form of the 3-channel u8 image E over
+ * the stored window (x, y, w, h): E[r][c] = colour(S_0[(y+r) / ry_0][(x+c) / rx_0], S_1[...], S_2[...]), integer divisions
+ * (box replication, libjpeg's rule for every ratio but 2); S_i the clamped 8-point IDCT of component i's blocks with its own
+ * table, the DC-only shortcut clamped too (the GRAYSCALE crop, ZJ_FLAG_CLAMP_DC, of a one-component frame of the plane's padded
+ * size 8 bw x 8 bh); colour the full decode's per-pixel YCbCr -> RGB, the identity for stored RGB.  Same filter, orientation,
+ * flip, scale, bias, dtype and tensor layout as for any file.  max_prescale_log2 is taken as 0 for such a file: the reduced
+ * decode is isotropic and these ratios are not, and the pick s = 1 is "decoded and resized exactly as before".  A component
+ * whose padded plane is wider or higher than 65535 samples is ZJ_ERR_ARG from its crop.  In the batch call such a file goes
+ * through its single-file call; the files around it keep the bytes they have without it. */
+#define ZJ_FLAG_ANY_SAMPLING 64u
 #define ZJ_LAYOUT_HWC 0u
 #define ZJ_LAYOUT_CHW 1u
 
@@ -437,6 +463,18 @@ ZJ_API int zj_gray_to_rgb_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_
 ZJ_API int zj_cmyk_to_rgb_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_a, const uint8_t *const *d_k, const unsigned *in_wh,
                                  const unsigned *a_pitch, const unsigned *k_pitch, int layout, const uint8_t *inverted,
                                  uint8_t *const *d_out, const unsigned *out_pitch, void *stream);
+/* n images from three u8 component planes each, in device memory, every plane at its own resolution:
+ * out[r][c] = colour(p0[r / ry0][c / rx0], p1[r / ry1][c / rx1], p2[r / ry2][c / rx2]), integer divisions (box replication);
+ * colour is the full decode's per-pixel YCbCr -> RGB, or with stored_rgb != 0 the identity (the planes are R, G, B).
+ * in_wh: width and height of each OUTPUT (1..65535); ratios: six bytes per image, rx0 ry0 rx1 ry1 rx2 ry2, each 1, 2 or 4
+ * (anything else: ZJ_ERR_ARG); plane k of an image is ceil(w / rx_k) x ceil(h / ry_k) samples; pitches: three per image, bytes
+ * between a plane's rows (NULL or 0: tight); `layout` of the output, ZJ_LAYOUT_HWC or ZJ_LAYOUT_CHW (three planes, pitch x
+ * height apart); out_pitch (NULL or 0: tight).  Any addresses and pitches; no byte outside a plane's samples is read, no padding
+ * is written.  An output must not overlap a plane.  One launch per 72 images (56 bytes of kernel arguments each), whatever
+ * their sizes.  Asynchronous on `stream` (NULL: the context's); nothing is launched after an argument error. */
+ZJ_API int zj_planes_to_rgb_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_p0, const uint8_t *const *d_p1,
+                                   const uint8_t *const *d_p2, const unsigned *in_wh, const uint8_t *ratios, const unsigned *pitches,
+                                   int stored_rgb, int layout, uint8_t *const *d_out, const unsigned *out_pitch, void *stream);
 /* zj_decode_crops_resized_prescaled_device for frames that are to be shown turned: orientation[f] = 1..8 per frame (NULL: all
  * 1, and the call IS the prescaled one), windows in DISPLAYED pixels of each frame.  The output is zj_resize_filtered_device
  * applied to EXACTLY the displayed form of the u8 crop zj_decode_crops_device writes for the stored window (zj_orient_window)
@@ -534,7 +572,8 @@ typedef struct zj_options {      /* zero = reference default */
                                     decoder keeps its helper threads until zj_decoder_free; 1 = strictly serial */
     int32_t pinned_planes;       /* non-zero: coefficient planes live in pinned host memory (DMA without staging) */
     uint32_t flags;              /* ZJ_FLAG_* for the pixel path (0 = the reference's bytes), see zj_frame_desc;
-                                    + ZJ_FLAG_FULL_AC_VALUES and ZJ_FLAG_CMYK_TO_RGB for the front-end itself */
+                                    + ZJ_FLAG_FULL_AC_VALUES, ZJ_FLAG_CMYK_TO_RGB and ZJ_FLAG_ANY_SAMPLING for the front-end
+                                    itself */
     uint32_t out_layout;         /* ZJ_LAYOUT_HWC (0) or ZJ_LAYOUT_CHW */
     int32_t entropy;             /* where baseline Huffman scans are decoded: ZJ_ENTROPY_CPU (0), ZJ_ENTROPY_GPU (scans of
                                     32 KB and more and 16 bits per block and more on the device, the rest and everything
@@ -616,6 +655,13 @@ ZJ_API int zj_decoder_orientation(const zj_decoder *d);
  * transform byte (0: CMYK / RGB as stored, 1: YCbCr, 2: YCCK).  Read for every file; it decides something for four-component
  * files only (ZJ_FLAG_CMYK_TO_RGB). */
 ZJ_API int zj_decoder_adobe_transform(const zj_decoder *d);
+/* 1 when the last file whose headers were read is STORED RGB: three components and an Adobe APP14 segment with transform 0
+ * (the samples are R, G, B, not Y, Cb, Cr); else 0.  The rule does not look at component ids: 'R','G','B' without the segment
+ * stays YCbCr, as in libjpeg.  It decides something with ZJ_FLAG_ANY_SAMPLING only. */
+ZJ_API int zj_decoder_stored_rgb(const zj_decoder *d);
+/* the sampling factors (h, v) of component `comp` (0 .. components - 1) of the last file whose headers were read, as its
+ * frame header states them (a one-component file: 1, 1).  Either output may be NULL.  ZJ_ERR_ARG: no such component. */
+ZJ_API int zj_decoder_component_sampling(const zj_decoder *d, int comp, unsigned *h, unsigned *v);
 /* plane `comp` (0 .. components - 1) of the last file, after a successful CPU decode (zj_decoder_decode_coefficients, or
  * zj_decoder_prepare that left no scan for the device): the plane, its length in int16 elements and its size in blocks.
  * Any output pointer may be NULL.  ZJ_ERR_ARG: no such component, or no decoded coefficients. */

@@ -18,6 +18,7 @@
 #include "zj_orient_launch.h"
 #include "zj_expand_launch.h"
 #include "zj_cmyk_launch.h"
+#include "zj_planes_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
 #include "zj_rzgroup.h"
@@ -990,6 +991,32 @@ int cmyk_launches(zj_ctx* c, size_t n, const uint8_t* const* a, const uint8_t* c
     return ZJ_OK;
 }
 
+// images [0, n) -> their three component planes box-replicated and converted, launches of up to PLANES_BATCH
+// images; wh: w, h pairs of the outputs, geo: planes_geo of the three components, pitch: three per image, all resolved
+int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t* const* p1, const uint8_t* const* p2,
+                    const unsigned* wh, const uint32_t* geo, const unsigned* pitch, int stored_rgb, int chw, uint8_t* const* out,
+                    const unsigned* out_pitch, hipStream_t st)
+{
+    PlanesParams p{};
+    for (size_t f0 = 0; f0 < n; f0 += PLANES_BATCH) {
+        const int m = (int)(n - f0 < (size_t)PLANES_BATCH ? n - f0 : (size_t)PLANES_BATCH);
+        p.nimg = m;
+        for (int i = 0; i < PLANES_BATCH; i++) {
+            const size_t f = f0 + i;
+            p.p[0][i] = i < m ? (uint64_t)(uintptr_t)p0[f] : 0;
+            p.p[1][i] = i < m ? (uint64_t)(uintptr_t)p1[f] : 0;
+            p.p[2][i] = i < m ? (uint64_t)(uintptr_t)p2[f] : 0;
+            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
+            for (int k = 0; k < 3; k++) p.pitch[k][i] = i < m ? pitch[3 * f + k] : 0;
+            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
+            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
+            p.geo[i] = i < m ? geo[f] : 0;
+        }
+        ZJ_HIP(c, launch_planes(chw, stored_rgb, p, st));
+    }
+    return ZJ_OK;
+}
+
 // The end of the launch group [g0, g1) of a resized call, its crops written into buf where `place` says (zj_rzgroup.h):
 // the turned frames, gathered: crop -> its displayed form, tight, in the second region; the resize over the images place[f].in
 // names, in order, into images [g0, g1) of the output; the event that orders the buffer's reuse.
@@ -1527,6 +1554,64 @@ int zjint_cmyk_to_rgb_one(zj_ctx* c, uint8_t* a, const uint8_t* k, unsigned w, u
     const uint8_t inv = inverted ? 1 : 0;
     const uint8_t* ca = a;
     int rc = zj_cmyk_to_rgb_device(c, 1, &ca, &k, wh, nullptr, nullptr, layout, &inv, &a, nullptr, nullptr);
+    if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+/* ---- component planes to RGB ------------------------------------------------------ */
+// the checks and launches of zj_planes_to_rgb_device; phases: three (x mod rx, y mod ry) pairs per image, NULL: all 0
+static int planes_to_rgb(zj_ctx* c, size_t n, const uint8_t* const* d_p0, const uint8_t* const* d_p1, const uint8_t* const* d_p2,
+                         const unsigned* in_wh, const uint8_t* ratios, const uint8_t* phases, const unsigned* pitches, int stored_rgb,
+                         int layout, uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_p0 || !d_p1 || !d_p2 || !in_wh || !ratios || !d_out) return ZJ_ERR_ARG;
+    if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    const unsigned bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> pp(3 * n), op(n);
+    std::vector<uint32_t> geo(n);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_p0[f] || !d_p1[f] || !d_p2[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        geo[f] = 0;
+        for (int k = 0; k < 3; k++) {
+            const unsigned rx = ratios[6 * f + 2 * k], ry = ratios[6 * f + 2 * k + 1];
+            if ((rx != 1 && rx != 2 && rx != 4) || (ry != 1 && ry != 2 && ry != 4)) return ZJ_ERR_ARG;
+            const unsigned px = phases ? phases[6 * f + 2 * k] : 0, py = phases ? phases[6 * f + 2 * k + 1] : 0;
+            if (px >= rx || py >= ry) return ZJ_ERR_ARG;
+            const unsigned pw = (px + w + rx - 1) / rx; // samples of a row that the image shows
+            pp[3 * f + k] = pitches && pitches[3 * f + k] ? pitches[3 * f + k] : pw;
+            if (pp[3 * f + k] < pw || pp[3 * f + k] > (1u << 24)) return ZJ_ERR_ARG;
+            geo[f] |= planes_geo(rx >> 1, ry >> 1, (int)px, (int)py) << (8 * k); // (log2 of 1, 2, 4: 0, 1, 2)
+        }
+        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
+        if (op[f] < w * bpp || op[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return planes_launches(c, n, d_p0, d_p1, d_p2, in_wh, geo.data(), pp.data(), stored_rgb ? 1 : 0, layout == ZJ_LAYOUT_CHW, d_out,
+                           op.data(), st);
+}
+
+int zj_planes_to_rgb_device(zj_ctx* c, size_t n, const uint8_t* const* d_p0, const uint8_t* const* d_p1, const uint8_t* const* d_p2,
+                            const unsigned* in_wh, const uint8_t* ratios, const unsigned* pitches, int stored_rgb, int layout,
+                            uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    return planes_to_rgb(c, n, d_p0, d_p1, d_p2, in_wh, ratios, nullptr, pitches, stored_rgb, layout, d_out, out_pitch, stream);
+}
+
+// Library-internal (zj_jpeg.cpp: the single-file resized crop of an odd-sampled file): one image from three tight planes that
+// begin at the window's first samples, with the window's phases, on the context stream; the context's crop buffer counts as
+// read by it; synchronised
+int zjint_planes_to_rgb_one(zj_ctx* c, const uint8_t* const planes[3], unsigned w, unsigned h, const uint8_t ratios[6],
+                            const uint8_t phases[6], int stored_rgb, int layout, uint8_t* d_out)
+{
+    if (!c) return ZJ_ERR_ARG;
+    const unsigned wh[2] = {w, h};
+    int rc = planes_to_rgb(c, 1, &planes[0], &planes[1], &planes[2], wh, ratios, phases, nullptr, stored_rgb, layout, &d_out, nullptr,
+                           nullptr);
     if (rc) return rc;
     if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
     if ((rc = resize_scratch_done(c, c->stream))) return rc;

@@ -475,6 +475,8 @@ struct zj_decoder {
     bool exif_seen = false;  // an APP1 segment with the Exif signature has been met: it decided, later ones are ignored
     int adobe_transform = -1; // the transform byte of the file's Adobe APP14 segment, -1: none seen
     bool adobe_short = false; // an APP14 segment with the Adobe signature ended before its transform byte
+    bool odd = false;         // a three-component file outside the four known modes, with ids outside 1..3, or stored RGB
+                              // (ZJ_FLAG_ANY_SAMPLING): every plane laid out as a one-component frame's
     int seen_sof = 0, scans = 0;
     bool coef_valid = false; // the planes hold the coefficients of a complete, successful decode_all
     long long hist_retries = 0; // images decoded a second time for it (tests)
@@ -594,20 +596,21 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
     if (nc == 0) return fail(d, ZJ_ERR_SOF, "Number of components cannot be zero.");
     if (len != 8 + 3 * nc) return fail(d, ZJ_ERR_SOF, "Length of start of frame differs from expected " + std::to_string(8 + 3 * nc) + ",value is " + std::to_string(len));
     const bool four = nc == 4 && (d->flags & ZJ_FLAG_CMYK_TO_RGB); // (without the flag: refused as ever)
+    const bool any3 = nc == 3 && (d->flags & ZJ_FLAG_ANY_SAMPLING); // (without the flag: refused as ever)
     if (nc != 1 && nc != 3 && !four) return fail(d, ZJ_ERR_SOF, "Invalid components. Found " + std::to_string(nc) + ", expected either 1 or 3");
     d->width = w; d->height = h; d->ncomp = nc; d->progressive = progressive;
     d->h_max = d->v_max = 1;
     for (int i = 0; i < nc; i++) {
         int id, hv, tq;
         if (!c.u8(id) || !c.u8(hv) || !c.u8(tq)) return fail(d, ZJ_ERR_FORMAT, "Could not read component data");
-        if (!four && (id < 1 || id > 3)) return fail(d, ZJ_ERR_FORMAT, "Unknown component id found," + std::to_string(id) + ", expected value between 1 and 3\nNote I and Q components are not supported yet");
+        if (!four && !any3 && (id < 1 || id > 3)) return fail(d, ZJ_ERR_FORMAT, "Unknown component id found," + std::to_string(id) + ", expected value between 1 and 3\nNote I and Q components are not supported yet");
         Comp& cm = d->comps[i];
         cm = Comp();
         cm.id = id; cm.h = hv >> 4; cm.v = hv & 15; cm.tq = tq;
         if (tq >= 4) return fail(d, ZJ_ERR_FORMAT, "Too large quantization number :" + std::to_string(tq) + ", expected value between 0 and 4");
         auto pow2 = [](int x) { return x > 0 && (x & (x - 1)) == 0; };
-        if (!four && !pow2(cm.h)) return fail(d, ZJ_ERR_FORMAT, "Horizontal sample is not a power of two(" + std::to_string(cm.h) + ") cannot decode");
-        if (!four && !pow2(cm.v)) return fail(d, ZJ_ERR_FORMAT, "Vertical sub-sample is not power of two(" + std::to_string(cm.v) + ") cannot decode");
+        if (!four && !any3 && !pow2(cm.h)) return fail(d, ZJ_ERR_FORMAT, "Horizontal sample is not a power of two(" + std::to_string(cm.h) + ") cannot decode");
+        if (!four && !any3 && !pow2(cm.v)) return fail(d, ZJ_ERR_FORMAT, "Vertical sub-sample is not power of two(" + std::to_string(cm.v) + ") cannot decode");
         if (cm.h > d->h_max) d->h_max = cm.h;
         if (cm.v > d->v_max) d->v_max = cm.v;
     }
@@ -627,6 +630,17 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
             return fail(d, ZJ_ERR_UNSUPPORTED, "Unsupported sampling of a four-component image: " + t +
                                                    ", expected (h,v) (1,1) (1,1) (h,v) with h and v 1 or 2");
         }
+    }
+    if (any3) {
+        // every factor 1, 2 or 4, so that every ratio h_max / h, v_max / v is 1, 2 or 4
+        const Comp* const cs = d->comps;
+        const auto ok = [](int f) { return f == 1 || f == 2 || f == 4; };
+        for (int i = 0; i < 3; i++)
+            if (!ok(cs[i].h) || !ok(cs[i].v)) {
+                std::string t;
+                for (int k = 0; k < 3; k++) t += std::string(k ? " " : "") + "(" + std::to_string(cs[k].h) + "," + std::to_string(cs[k].v) + ")";
+                return fail(d, ZJ_ERR_UNSUPPORTED, "Unsupported sampling of a three-component image: " + t + ", expected every factor to be 1, 2 or 4");
+            }
     }
     d->mcu_x = (w + 8 * d->h_max - 1) / (8 * d->h_max);
     d->mcu_y = (h + 8 * d->v_max - 1) / (8 * d->v_max);
@@ -656,7 +670,7 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
             memset(base + o, 0, o + piece <= bytes ? piece : bytes - o);
         });
     }
-    if (nc == 3) {
+    if (nc == 3 && !any3) {
         // check_component_dimensions (decoder.rs:609-646): chroma must be (1,1), luma one of the four modes
         for (int i = 1; i < 3; i++)
             if (d->comps[i].h != 1 || d->comps[i].v != 1)
@@ -664,6 +678,25 @@ int parse_sof(zj_decoder* d, Cursor& c, int progressive)
         if (d->h_max > 2 || d->v_max > 2) return fail(d, ZJ_ERR_FORMAT, "Unknown down-sampling method, cannot continue");
     }
     d->seen_sof = 1;
+    return ZJ_OK;
+}
+
+// A three-component file that the serial T.81 walk decodes (zj_decoder::odd): every component's plane gets
+// the layout of a one-component frame of the component's own size, ceil(cw/8) x ceil(ch/8) blocks with cw = ceil(W h / h_max),
+// ch = ceil(H v / v_max), cleared: the walk accumulates whatever the scans are, and the interleaved blocks outside a plane are
+// decoded and dropped.  Called once the headers are read: an Adobe segment may follow the frame header.
+int odd_layout(zj_decoder* d)
+{
+    for (int i = 0; i < 3; i++) {
+        Comp& cm = d->comps[i];
+        const int cw = (d->width * cm.h + d->h_max - 1) / d->h_max, ch = (d->height * cm.v + d->v_max - 1) / d->v_max;
+        cm.bw = (cw + 7) / 8; cm.bh = (ch + 7) / 8;
+        cm.coef_len = (size_t)cm.bw * cm.bh * 64;
+        cm.coef = nullptr;
+    }
+    const int rc = ensure_planes(d);
+    if (rc) return rc;
+    for (int i = 0; i < 3; i++) memset(d->comps[i].coef, 0, d->comps[i].coef_len * 2);
     return ZJ_OK;
 }
 
@@ -2256,12 +2289,13 @@ int scan_progressive(zj_decoder* d, BitReader& br)
     return ZJ_OK;
 }
 
-// ---- four-component files (ZJ_FLAG_CMYK_TO_RGB) ----------------------------------------------------------
+// ---- four-component files (ZJ_FLAG_CMYK_TO_RGB) and odd three-component ones (ZJ_FLAG_ANY_SAMPLING, 3.13) --
 // A plain T.81 walk of its own, serial: the reference has no four-component path, so there is no reader of its to imitate --
 // no six-bit cut of fast-AC values, no short DC reads, no early exit at EOI -- and the walkers above stay what they are for
-// one- and three-component files.  Sequential (SOF0) and progressive (SOF2) scans of 1..4 components, accumulated into planes
-// that parse_sof cleared; a block of component 4 that lies outside its plane (the padding of a 16-pixel MCU) is decoded into
-// a buffer and dropped.
+// standard one- and three-component files.  Sequential (SOF0) and progressive (SOF2) scans of 1..4 components, accumulated
+// into planes that were cleared before the first scan (parse_sof for a four-component file, odd_layout for an odd
+// three-component one); a block that lies outside its component's plane (the MCU padding: component 4 of a four-component
+// file, any component of an odd three-component one) is decoded into a buffer and dropped.
 int four_block(zj_decoder* d, BitReader& br, Comp& cm, int16_t* blk)
 {
     if (!d->progressive) {
@@ -2687,15 +2721,23 @@ int decode_all_once(zj_decoder* d, const uint8_t* buf, size_t len, bool headers_
 {
     d->err.clear(); d->err_code = 0; d->seen_sof = 0; d->scans = 0; d->restart_interval = 0;
     d->coef_valid = false; d->scan_ready = false; d->src = nullptr; d->src_len = 0;
-    d->orientation = 1; d->exif_seen = false; d->adobe_transform = -1; d->adobe_short = false;
+    d->orientation = 1; d->exif_seen = false; d->adobe_transform = -1; d->adobe_short = false; d->odd = false;
     for (int i = 0; i < 4; i++) { d->qt_present[i] = false; d->dc[i].present = false; d->ac[i].present = false; }
     Cursor c{buf, buf + len};
     int rc = parse_headers(d, c, true);
     if (rc) return rc;
     if (d->seen_sof && d->ncomp == 4 && d->adobe_short) return fail(d, ZJ_ERR_FORMAT, "Adobe APP14 segment is too short to hold its transform byte");
+    if (d->seen_sof && d->ncomp == 3 && (d->flags & ZJ_FLAG_ANY_SAMPLING)) {
+        // which walk: today's for a file the front-end takes without the flag, unless its samples are stored RGB
+        const Comp* const cs = d->comps;
+        bool standard = d->h_max <= 2 && d->v_max <= 2 && cs[0].h == d->h_max && cs[0].v == d->v_max;
+        for (int i = 0; i < 3; i++) standard = standard && cs[i].id >= 1 && cs[i].id <= 3 && (i == 0 || (cs[i].h == 1 && cs[i].v == 1));
+        d->odd = !standard || d->adobe_transform == 0;
+    }
     if (headers_only) return ZJ_OK;
     if (!d->seen_sof) return fail(d, ZJ_ERR_SOF, "Number of components cannot be zero.");
-    const bool four = d->ncomp == 4;
+    if (d->odd && (rc = odd_layout(d))) return rc;
+    const bool four = d->ncomp == 4 || d->odd;
     BitReader br;
     br.p = c.p; br.end = c.end; br.istart = c.p;
     if (!d->progressive && !four) {
@@ -2775,6 +2817,14 @@ const char* zj_decoder_error(const zj_decoder* d) { return d ? d->err.c_str() : 
 int zj_decoder_parallel_segments(const zj_decoder* d) { return d ? d->dri_parallel_segments : 0; }
 int zj_decoder_orientation(const zj_decoder* d) { return d ? d->orientation : 0; }
 int zj_decoder_adobe_transform(const zj_decoder* d) { return d ? d->adobe_transform : -1; }
+int zj_decoder_stored_rgb(const zj_decoder* d) { return d && d->seen_sof && d->ncomp == 3 && d->adobe_transform == 0 ? 1 : 0; }
+int zj_decoder_component_sampling(const zj_decoder* d, int comp, unsigned* h, unsigned* v)
+{
+    if (!d || !d->seen_sof || comp < 0 || comp >= d->ncomp) return ZJ_ERR_ARG;
+    if (h) *h = (unsigned)d->comps[comp].h;
+    if (v) *v = (unsigned)d->comps[comp].v;
+    return ZJ_OK;
+}
 int zj_decoder_plane(const zj_decoder* d, int comp, const int16_t** plane, size_t* len, unsigned* blocks_w, unsigned* blocks_h)
 {
     if (!d || !d->seen_sof || d->err_code || !d->coef_valid || comp < 0 || comp >= d->ncomp || !d->comps[comp].coef) return ZJ_ERR_ARG;
@@ -2896,6 +2946,11 @@ __attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, 
                                              uint8_t* d_out, unsigned out_pitch);
 
 static const char* const kFourOnlyResized = "four-component files are finished by the resized-crop calls only (ZJ_FLAG_CMYK_TO_RGB)";
+static const char* const kOddOnlyResized = "files of this sampling or stored RGB are finished by the resized-crop calls only (ZJ_FLAG_ANY_SAMPLING)";
+// ... and three component planes box-replicated and converted into one image
+__attribute__((weak)) int zjint_planes_to_rgb_one(zj_ctx* c, const uint8_t* const planes[3], unsigned w, unsigned h,
+                                                  const uint8_t ratios[6], const uint8_t phases[6], int stored_rgb, int layout,
+                                                  uint8_t* d_out);
 
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
@@ -2904,6 +2959,7 @@ static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap,
     // scan) counts
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
+    if (d->odd) return fail(d, ZJ_ERR_UNSUPPORTED, kOddOnlyResized);
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
     // grayscale JPEG decoded to RGB: the reference converts nothing and returns zeros (worker.rs:131)
@@ -3013,6 +3069,7 @@ static int finish_window(zj_decoder* d, zj_ctx* ctx, bool reduced, int k, unsign
     using namespace zj;
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
+    if (d->odd) return fail(d, ZJ_ERR_UNSUPPORTED, kOddOnlyResized);
     if (reduced && (k < 1 || k > 3)) return fail(d, ZJ_ERR_ARG, "scale_log2 is 1, 2 or 3");
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
@@ -3097,6 +3154,13 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
         fd.out_colorspace = d->adobe_transform == 2 ? ZJ_CS_RGB : ZJ_CS_YCBCR;
         if (fd.out_colorspace == ZJ_CS_YCBCR) fd.out_layout = ZJ_LAYOUT_HWC; // (stored samples have the interleaved layout only)
     }
+    if (d->odd) {
+        //  fd keeps the file's own sampling: no frame-level call takes it, finish_resized_odd builds the
+        // one-component descriptors of the planes
+        if (d->out_colorspace != ZJ_CS_RGB) return fail(d, ZJ_ERR_UNSUPPORTED, "ZJ_FLAG_ANY_SAMPLING gives RGB: such a file needs a decoder with out_colorspace ZJ_CS_RGB");
+        if (!zjint_planes_to_rgb_one || !zjint_crop_frame) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+        if (!d->coef_valid) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    }
     if (d->ncomp == 1 && (d->flags & ZJ_FLAG_GRAY_TO_RGB)) {
         if (d->out_colorspace == ZJ_CS_YCBCR) return fail(d, ZJ_ERR_UNSUPPORTED, "ZJ_FLAG_GRAY_TO_RGB gives RGB, not YCbCr");
         if (d->out_colorspace == ZJ_CS_RGB) { fd.out_colorspace = ZJ_CS_RGB; fd.flags |= ZJ_FLAG_GRAY_TO_RGB; }
@@ -3162,6 +3226,60 @@ static int finish_resized_four(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& 
     return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
 }
 
+// finish_resized for an odd-sampled or stored-RGB file, its arguments checked: x, y, w, h the stored window.
+// In the context's buffer: the three component crops -- component i as the GRAYSCALE crop, DC clamped, of a one-component
+// frame of the plane's padded size, cut to the samples the window shows --, the image E behind them, turned: its displayed
+// form behind that; the resize reads the last.
+static int finish_resized_odd(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& fd, unsigned x, unsigned y, unsigned w, unsigned h, int o,
+                              unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                              int flip, int filter, void* d_out)
+{
+    using namespace zj;
+    const int layout = fd.out_layout == ZJ_LAYOUT_CHW ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    zj_frame_desc fc[3];
+    unsigned cx[3], cy[3], cw[3], chh[3];
+    size_t off[3], at = 0;
+    uint8_t ratios[6], phases[6];
+    for (int i = 0; i < 3; i++) {
+        const Comp& cm = d->comps[i];
+        const unsigned rx = (unsigned)(d->h_max / cm.h), ry = (unsigned)(d->v_max / cm.v);
+        ratios[2 * i] = (uint8_t)rx; ratios[2 * i + 1] = (uint8_t)ry;
+        phases[2 * i] = (uint8_t)(x % rx); phases[2 * i + 1] = (uint8_t)(y % ry);
+        cx[i] = x / rx; cy[i] = y / ry;
+        cw[i] = (x + w - 1) / rx - cx[i] + 1; chh[i] = (y + h - 1) / ry - cy[i] + 1;
+        zj_frame_desc& f = fc[i];
+        memset(&f, 0, sizeof f);
+        f.width = 8u * (unsigned)cm.bw; f.height = 8u * (unsigned)cm.bh;
+        f.h_max = f.v_max = 1; f.in_components = 1;
+        f.out_colorspace = ZJ_CS_GRAYSCALE; f.flags = ZJ_FLAG_CLAMP_DC; f.out_layout = ZJ_LAYOUT_HWC;
+        for (int c = 0; c < 3; c++)
+            for (int q = 0; q < 64; q++) f.qt[c][q] = cm.q[q];
+        off[i] = at;
+        at = up(at + (size_t)cw[i] * chh[i]);
+    }
+    const size_t len_e = (size_t)w * h * 3, off_e = at, off_e2 = up(off_e + len_e);
+    uint8_t* buf = nullptr;
+    int rc = zjint_resize_scratch(ctx, o != 1 ? off_e2 + len_e : off_e + len_e, &buf);
+    if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    for (int i = 0; i < 3 && !rc; i++)
+        rc = zjint_crop_frame(ctx, &fc[i], d->comps[i].coef, nullptr, nullptr, 0, cx[i], cy[i], cw[i], chh[i], buf + off[i], 0);
+    if (rc) return fail(d, rc, std::string("crop: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    const uint8_t* const planes[3] = {buf + off[0], buf + off[1], buf + off[2]};
+    rc = zjint_planes_to_rgb_one(ctx, planes, w, h, ratios, phases, d->adobe_transform == 0, layout, buf + off_e);
+    if (rc) return fail(d, rc, std::string("planes to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+    uint8_t* e = buf + off_e;
+    unsigned dw = w, dh = h;
+    if (o != 1) {
+        orient_size(o, w, h, &dw, &dh);
+        rc = zjint_orient_one(ctx, e, w, h, 3, layout, o, buf + off_e2);
+        if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+        e = buf + off_e2;
+    }
+    rc = zjint_resize_one(ctx, e, dw, dh, 3, layout, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
+    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+}
+
 static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
                           unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
                           void* d_out, size_t out_cap, size_t* out_len, int o = 1)
@@ -3169,8 +3287,10 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     using namespace zj;
     zj_frame_desc fd;
     int ch = 0;
+    if (d->odd) k = 0; // (the reduced decode is isotropic, these ratios are not: such a file is never prescaled)
     int rc = resized_checks(d, k, x, y, w, h, out_w, out_h, dtype, filter, out_cap, out_len, o, fd, ch);
     if (rc) return rc;
+    if (d->odd) return finish_resized_odd(d, ctx, fd, x, y, w, h, o, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
     const unsigned full[4] = {x, y, w, h};
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
@@ -3254,8 +3374,8 @@ int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder* d, zj_ctx*
 
 // Several prepared files of any sizes into one resized-crop tensor.  The files the CPU walker decoded go
 // through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan left for the device, one whose
-// output is all zeros, and a four-component file, is finished through the single-file call, which gives the
-// same bytes.
+// output is all zeros, a four-component file and an odd-sampled or stored-RGB one (3.13), is finished through
+// the single-file call, which gives the same bytes.
 int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* windows,
                                                        unsigned out_w, unsigned out_h, int dtype, int out_layout,
                                                        const float* scale, const float* bias, const uint8_t* flip, int filter,
@@ -3297,7 +3417,7 @@ int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, si
         const int kk = prescale_pick(w, h, out_w, out_h, max_prescale_log2);
         int ch = 0;
         if ((rcs[k] = resized_checks(d, kk, x, y, w, h, out_w, out_h, dtype, filter, img, nullptr, o, fds[k], ch))) continue;
-        if (d->scan_ready || !d->coef_valid || d->ncomp == 4 || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
+        if (d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
         py[k] = d->comps[0].coef;
         pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
         ori[k] = (uint8_t)o;
@@ -3327,6 +3447,7 @@ int zj_decoder_finish_pixels_oriented_device(zj_decoder* d, zj_ctx* ctx, uint8_t
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
+    if (d->odd) return fail(d, ZJ_ERR_UNSUPPORTED, kOddOnlyResized);
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
     const int ch = resize_channels(&fd);

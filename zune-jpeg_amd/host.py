@@ -66,6 +66,9 @@ FLAG_FULL_AC_VALUES = 8  # zj_options.flags only: the front-end yields AC values
 FLAG_GRAY_TO_RGB = 16    # resized crops only: a one-component frame / file asked for RGB gives R = G = B
 FLAG_CMYK_TO_RGB = 32    # decoder options only: four-component (Adobe CMYK / YCCK) files are accepted and the resized-crop
                          # calls show them as RGB
+FLAG_ANY_SAMPLING = 64   # decoder options only: three-component files of any sampling with factors 1, 2, 4 (4:1:1, 4:1:0,
+                         # chroma that is not (1,1)), any ids, and stored-RGB files are accepted and the resized-crop calls
+                         # show them as RGB
 LAYOUT_HWC, LAYOUT_CHW = 0, 1
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8 = 0, 1, 2, 3  # zj_resize_device and the resized crops: the output's dtype
 TENSOR_NCHW, TENSOR_NHWC = 0, 1                          # ... and its layout
@@ -192,6 +195,7 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decoder_finish_pixels_resized_crop_oriented_device",
     "zj_decode_crops_resized_mixed_device", "zj_decoder_finish_pixels_resized_crop_batch_device",
     "zj_gray_to_rgb_device", "zj_cmyk_to_rgb_device", "zj_decoder_adobe_transform", "zj_decoder_plane",
+    "zj_planes_to_rgb_device", "zj_decoder_stored_rgb", "zj_decoder_component_sampling",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -356,6 +360,9 @@ def lib():
     L.zj_gray_to_rgb_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, vp, vp, vp]
     L.zj_cmyk_to_rgb_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.zj_decoder_adobe_transform.argtypes = [vp]
+    L.zj_planes_to_rgb_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.zj_decoder_stored_rgb.argtypes = [vp]
+    L.zj_decoder_component_sampling.argtypes = [vp, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zj_decoder_plane.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(sz), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zj_decode_crops_resized_oriented_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
                                                           C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
@@ -681,6 +688,28 @@ class Context:
         _check(lib().zj_cmyk_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_a), (C.c_void_p * n)(*d_k), wh, pit(a_pitches),
                                            pit(k_pitches), layout, inv, (C.c_void_p * n)(*d_out), pit(out_pitches), stream),
                "zj_cmyk_to_rgb_device", self._h)
+
+    def planes_to_rgb_device(self, d_p0, d_p1, d_p2, sizes, ratios, layout, d_out, stored_rgb=False, pitches=None,
+                             out_pitches=None, stream=None):
+        """Three u8 component planes per image, each at its own resolution -> the 3-channel u8 image whose pixel (r, c) is
+        colour(p0[r // ry0][c // rx0], p1[...], p2[...]) (zj_planes_to_rgb_device, DESIGN.md 3.13): d_p0, d_p1, d_p2 =
+        device pointers, sizes = one (w, h) of the OUTPUT each, ratios = ((rx0, ry0), (rx1, ry1), (rx2, ry2)) each, every
+        ratio 1, 2 or 4 (plane k holds ceil(w / rx_k) x ceil(h / ry_k) samples), layout LAYOUT_HWC or LAYOUT_CHW of the
+        output, d_out = one device pointer each; stored_rgb: the planes are R, G, B as they are, not Y, Cb, Cr; pitches =
+        three per image, out_pitches = one per image, bytes between rows (None: tight).  Asynchronous on `stream`."""
+        n = len(d_p0)
+        if len(d_p1) != n or len(d_p2) != n or len(sizes) != n or len(ratios) != n or len(d_out) != n:
+            raise ValueError("three planes, a size, three ratio pairs and an output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        flat = [int(v) for r in ratios for pair in r for v in pair]
+        if len(flat) != 6 * n or any(v < 0 or v > 255 for v in flat):
+            raise ValueError("ratios: three (rx, ry) pairs per image")
+        rt = (C.c_uint8 * (6 * n))(*flat)
+        pit = (C.c_uint * (3 * n))(*[int(v) for p in pitches for v in p]) if pitches is not None else None
+        opit = (C.c_uint * n)(*[int(x) for x in out_pitches]) if out_pitches is not None else None
+        _check(lib().zj_planes_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_p0), (C.c_void_p * n)(*d_p1), (C.c_void_p * n)(*d_p2),
+                                             wh, rt, pit, 1 if stored_rgb else 0, layout, (C.c_void_p * n)(*d_out), opit, stream),
+               "zj_planes_to_rgb_device", self._h)
 
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
                                     bias=None, flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,
@@ -1020,6 +1049,21 @@ class Decoder:
     def adobe_transform(self):
         """The transform byte of the last file's Adobe APP14 segment (0: CMYK / as stored, 1: YCbCr, 2: YCCK); -1: none seen."""
         return int(lib().zj_decoder_adobe_transform(self._d))
+
+    @property
+    def stored_rgb(self):
+        """True when the last file is stored RGB: three components and an Adobe APP14 segment with transform 0
+        (zj_decoder_stored_rgb; Pillow's save(keep_rgb=True) writes such files)."""
+        return bool(lib().zj_decoder_stored_rgb(self._d))
+
+    def component_sampling(self, comp):
+        """(h, v) of component `comp` (0 .. components - 1) of the last file whose headers were read, as its frame header
+        states them (zj_decoder_component_sampling)."""
+        h, v = C.c_uint(0), C.c_uint(0)
+        rc = lib().zj_decoder_component_sampling(self._d, int(comp), C.byref(h), C.byref(v))
+        if rc:
+            raise DecodeError(rc, "no such component")
+        return h.value, v.value
 
     def plane(self, comp, copy=True):
         """Coefficient plane `comp` (0 .. components - 1) of the last file after a CPU decode (zj_decoder_plane): an int16

@@ -217,6 +217,11 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     Four-component files (Adobe CMYK / YCCK): with options.flags | FLAG_CMYK_TO_RGB and out_colorspace RGB their images are
     what Pillow's convert("RGB") shows, each finished through its single-file call; WITHOUT the flag such a
     file is refused when it is prepared (DecodeError naming its index), as the reference refuses it.
+    Three-component files the reference refuses -- 4:1:1, 4:1:0, chroma that is not (1,1), ids outside 1..3 -- and stored-RGB
+    files (Adobe transform 0, Pillow's keep_rgb=True): with options.flags | FLAG_ANY_SAMPLING and out_colorspace RGB their
+    images are the resize of the box-replicated, colour-converted component planes, never prescaled, each
+    finished through its single-file call; WITHOUT the flag the first kind is refused when it is prepared (DecodeError
+    naming its index) and a stored-RGB file with ids 1..3 is shown through YCbCr -> RGB, with wrong colours.
     The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
     the stream the output is allocated under, synchronised before the call writes it."""
     import torch
@@ -413,6 +418,43 @@ def cmyk_to_rgb_tensor(ctx, images, planes, layout="HWC", inverted=None, stream=
     ctx.cmyk_to_rgb_device([im.data_ptr() for im in imgs], [k.data_ptr() for k in ks], sizes,
                            LAYOUT_CHW if layout == "CHW" else LAYOUT_HWC, [o.data_ptr() for o in outs], inverted, pitches,
                            kpitches, None, s.cuda_stream)
+    return outs
+
+
+def planes_to_rgb_tensor(ctx, planes, sizes, ratios, layout="HWC", stored_rgb=False, stream=None):
+    """Three u8 CUDA planes ([h_k, w_k] each) per image -> new contiguous RGB tensors ([H, W, 3] "HWC" or [3, H, W] "CHW"),
+    pixel (r, c) = colour(p0[r // ry0][c // rx0], p1[...], p2[...]) (zj_planes_to_rgb_device, DESIGN.md 3.13): planes = one
+    (p0, p1, p2) per image, sizes = one (W, H) of the output each, ratios = ((rx0, ry0), (rx1, ry1), (rx2, ry2)) each, every
+    ratio 1, 2 or 4; plane k must hold ceil(W / rx_k) x ceil(H / ry_k) samples.  colour is the full decode's YCbCr -> RGB,
+    with stored_rgb the identity.  Rows may be strided.  Streams as decode_to_tensor."""
+    import torch
+    if layout not in ("HWC", "CHW"):
+        raise ValueError("layout is 'HWC' or 'CHW'")
+    n = len(planes)
+    if n == 0 or len(sizes) != n or len(ratios) != n:
+        raise ValueError("three planes, a size and three ratio pairs per image")
+    ps, pitches = [[], [], []], []
+    for trio, (w, h), rs in zip(planes, sizes, ratios):
+        if len(trio) != 3 or len(rs) != 3:
+            raise ValueError("three planes and three ratio pairs per image")
+        ims, szs, pit, ch = _u8_images(list(trio), "HWC")
+        if ch != 1 or any(r not in (1, 2, 4) for pair in rs for r in pair):
+            raise ValueError("one-channel planes and ratios 1, 2 or 4")
+        for k in range(3):
+            if szs[k] != (-(-int(w) // rs[k][0]), -(-int(h) // rs[k][1])):
+                raise ValueError("plane %d is not ceil(W / rx) x ceil(H / ry)" % k)
+            ps[k].append(ims[k])
+        pitches.append(pit)
+    dev = ps[0][0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        outs = [torch.empty((3, int(h), int(w)) if layout == "CHW" else (int(h), int(w), 3), dtype=torch.uint8, device=dev)
+                for w, h in sizes]
+    _on_stream(s, cur, ps[0] + ps[1] + ps[2])
+    ctx.planes_to_rgb_device([t.data_ptr() for t in ps[0]], [t.data_ptr() for t in ps[1]], [t.data_ptr() for t in ps[2]],
+                             [(int(w), int(h)) for w, h in sizes], ratios, LAYOUT_CHW if layout == "CHW" else LAYOUT_HWC,
+                             [o.data_ptr() for o in outs], stored_rgb, pitches, None, s.cuda_stream)
     return outs
 
 
