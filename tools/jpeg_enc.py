@@ -8,7 +8,9 @@ so that Pillow/libjpeg can decode the same file as an independent cross-check.
 Supports: baseline (SOF0, interleaved scan, optional restart interval) and progressive (SOF2, the
 classic 10-scan script incl. successive approximation), 1 or 3 components, luma sampling (1,1),
 (2,1), (1,2), (2,2).  Huffman tables are fixed-length (every symbol present), which is legal and
-keeps the encoder tiny.  Written from ITU-T T.81 (Annex F, G), pure Python: use small images.
+keeps the encoder tiny; encode_baseline also takes tables of given code lengths, one pair for all
+components (canonical_tables) or a set per component with DHT ids of its own (component_tables).
+Written from ITU-T T.81 (Annex F, G), pure Python: use small images.
 
 Plane layout = the decoder's: per component [block_row][block_col][64] int16, natural order.
 """
@@ -79,7 +81,27 @@ def canonical_tables(dc_lengths, ac_lengths):
     return out
 
 
+def component_tables(dc, ac, sel):
+    """Tables per component for encode_baseline(tables=...).  dc, ac: {DHT id (0..3): {symbol: code length}} -- or, in
+    place of the lengths, a ready table (codes / counts / symbols, as canonical_tables returns per class); sel: per
+    component its (DC id, AC id), which the SOS selectors follow.  Up to three tables per class.  An AC table may carry
+    "zero_skip": r (1..14) -- see encode_baseline."""
+    def one(cls, t):
+        return t if "codes" in t else canonical_tables(t if cls == "dc" else {}, t if cls == "ac" else {})[cls]
+    out = {"dc": {i: one("dc", t) for i, t in dc.items()}, "ac": {i: one("ac", t) for i, t in ac.items()}, "sel": [tuple(x) for x in sel]}
+    assert all(0 <= i <= 3 for cls in ("dc", "ac") for i in out[cls]) and len(out["dc"]) <= 3 and len(out["ac"]) <= 3
+    assert all(td in out["dc"] and ta in out["ac"] for td, ta in out["sel"])
+    return out
+
+
 def _dht_segment(tables=None):
+    if tables is not None and "sel" in tables:
+        seg = bytearray()
+        for cls, name in ((0, "dc"), (1, "ac")):
+            for idx in sorted(tables[name]):
+                t = tables[name][idx]
+                seg += bytes([(cls << 4) | idx]) + bytes(t["counts"]) + bytes(t["symbols"])
+        return b"\xff\xc4" + struct.pack(">H", len(seg) + 2) + bytes(seg)
     if tables is not None:
         seg = bytearray()
         for cls, name in ((0, "dc"), (1, "ac")):
@@ -121,11 +143,13 @@ def _headers(w, h, hs, vs, ncomp, qts, progressive, restart, tables=None):
     return out
 
 
-def _sos(comps, ss, se, ah, al):
+def _sos(comps, ss, se, ah, al, sel=None):
     seg = bytes([len(comps)])
     for c in comps:
-        t = 0 if c == 0 else 1
-        seg += bytes([c + 1, (t << 4) | t])
+        td = ta = 0 if c == 0 else 1
+        if sel is not None:
+            td, ta = sel[c]
+        seg += bytes([c + 1, (td << 4) | ta])
     seg += bytes([ss, se, (ah << 4) | al])
     return b"\xff\xda" + struct.pack(">H", len(seg) + 2) + seg
 
@@ -170,11 +194,20 @@ def _emit_restart(bw, count):
 
 
 def encode_baseline(planes, qts, w, h, hs=1, vs=1, ncomp=3, restart=0, tables=None):
+    """tables: None (the fixed-length pair), one pair for every component (canonical_tables), or tables per component
+    (component_tables).  An AC table of the latter form with "zero_skip": r writes the size-0 symbol (r << 4) in front of
+    a coefficient that follows more than r zeros, for r + 1 of them: not a T.81 symbol -- the reference's fast-AC table
+    reads it that way when its code has at most 9 bits (oracle/ref_walk.py)."""
     P = _Planes(planes, w, h, hs, vs, ncomp)
     out = _headers(w, h, hs, vs, ncomp, qts, False, restart, tables)
-    dc_code = (lambda sym: tables["dc"]["codes"][sym]) if tables else _dc_code
-    ac_code = (lambda sym: tables["ac"]["codes"][sym]) if tables else _ac_code
-    out += _sos(list(range(ncomp)), 0, 63, 0, 0)
+    per_comp = tables is not None and "sel" in tables
+    if per_comp:
+        dc_of = [tables["dc"][td] for td, _ in tables["sel"]]
+        ac_of = [tables["ac"][ta] for _, ta in tables["sel"]]
+    else:
+        one_dc = (lambda sym: tables["dc"]["codes"][sym]) if tables else _dc_code
+        one_ac = (lambda sym: tables["ac"]["codes"][sym]) if tables else _ac_code
+    out += _sos(list(range(ncomp)), 0, 63, 0, 0, tables["sel"] if per_comp else None)
     bw = BitWriter()
     pred = [0] * ncomp
     n_mcu, rst = 0, 0
@@ -184,6 +217,11 @@ def encode_baseline(planes, qts, w, h, hs=1, vs=1, ncomp=3, restart=0, tables=No
             rst += 1
             pred = [0] * ncomp
         for c, by, bx in mcu:
+            skip = 0
+            if per_comp:
+                dc_code, ac_code, skip = dc_of[c]["codes"].__getitem__, ac_of[c]["codes"].__getitem__, ac_of[c].get("zero_skip", 0)
+            else:
+                dc_code, ac_code = one_dc, one_ac
             blk = P.blocks[c][by, bx]
             diff = int(blk[0]) - pred[c]
             pred[c] = int(blk[0])
@@ -197,6 +235,9 @@ def encode_baseline(planes, qts, w, h, hs=1, vs=1, ncomp=3, restart=0, tables=No
                 if v == 0:
                     run += 1
                     continue
+                if skip and run > skip:
+                    bw.put(*ac_code(skip << 4))
+                    run -= skip + 1
                 while run > 15:
                     bw.put(*ac_code(0xF0))
                     run -= 16
