@@ -214,6 +214,25 @@ extern "C" {
                                           d_cb: *const *const i16, d_cr: *const *const i16, windows: *const c_uint,
                                           out_w: c_uint, out_h: c_uint, dtype: c_int, out_layout: c_int, scale: *const f32,
                                           bias: *const f32, flip: *const u8, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_crop_tensor_out_len(d: *const zj_frame_desc, w: c_uint, h: c_uint, dtype: c_int) -> usize;
+    pub fn zj_decode_crops_tensor_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize, d_y: *const *const i16,
+                                         d_cb: *const *const i16, d_cr: *const *const i16, origins: *const c_uint,
+                                         crop_w: c_uint, crop_h: c_uint, dtype: c_int, out_layout: c_int, scale: *const f32,
+                                         bias: *const f32, flip: *const u8, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_tensor_mixed_device(ctx: *mut zj_ctx, descs: *const zj_frame_desc, nframes: usize,
+                                               d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                               origins: *const c_uint, crop_w: c_uint, crop_h: c_uint, dtype: c_int,
+                                               out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                               d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_crop_tensor_batch_device(ds: *const *mut zj_decoder, n: usize, ctx: *mut zj_ctx,
+                                                             origins: *const c_uint, w: c_uint, h: c_uint, dtype: c_int,
+                                                             out_layout: c_int, scale: *const f32, bias: *const f32,
+                                                             flip: *const u8, d_out: *mut c_void, out_cap: usize,
+                                                             rcs: *mut c_int) -> c_int;
+    pub fn zj_decoder_finish_pixels_crop_tensor_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint, w: c_uint,
+                                                       h: c_uint, dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                       bias: *const f32, flip: c_int, d_out: *mut c_void, out_cap: usize,
+                                                       out_len: *mut usize) -> c_int;
     pub fn zj_decoder_finish_pixels_resized_crop_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint, w: c_uint,
                                                         h: c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
                                                         out_layout: c_int, scale: *const f32, bias: *const f32, flip: c_int,

@@ -353,6 +353,37 @@ ZJ_API int zj_decode_crops_resized_device(zj_ctx *ctx, const zj_frame_desc *d, s
                                           const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *windows,
                                           unsigned out_w, unsigned out_h, int dtype, int out_layout, const float *scale,
                                           const float *bias, const uint8_t *flip, void *d_out, void *stream);
+/* Crop windows straight into a normalised tensor, NOT resized: a RandomCrop / CenterCrop at native
+ * resolution, a segmentation or detection crop, a whole frame.  d: out_colorspace RGB / YCbCr (C = 3) or GRAYSCALE (C = 1),
+ * out_layout ZJ_LAYOUT_HWC and out_pitch 0 (the tensor's layout is the call's; anything else, RGBA / RGBX included, is
+ * ZJ_ERR_UNSUPPORTED).  Frame f's window is crop_w x crop_h at origins[2f], origins[2f + 1], checked as in
+ * zj_decode_crops_device.  With p[r][i][c] the byte zj_decode_crops_device writes for that window (its zeros included), the
+ * element of image f, channel c, row r, column (flip[f] ? crop_w - 1 - i : i) is the conversion above of v = p << 16:
+ * ZJ_DTYPE_F32 fl32(fl32(v * (scale[c] / 65536)) + bias[c]), F16 / BF16 its nearest-even rounding, U8 the byte itself.  A
+ * zero byte therefore becomes bias[c].  For crop_w, crop_h <= 8192 this is, byte for byte, zj_decode_crops_resized_device
+ * with out_w = crop_w, out_h = crop_h -- written once by one launch, with no buffer of the context in between, no ordering
+ * events and no 8192 limit.  dtype, out_layout, scale, bias, flip as zj_resize_device; image f lies at d_out + f *
+ * zj_crop_tensor_out_len() bytes, d_out aligned to the element.  Batches larger than ZJ_SCATTER_MAX are split into several
+ * launches.  Asynchronous on `stream`; nothing is launched after an error.
+ * Frames of several geometries: zj_decode_crops_tensor_mixed_device below.  A decoder's file, several decoders' files:
+ * zj_decoder_finish_pixels_crop_tensor_device, zj_decoder_finish_pixels_crop_tensor_batch_device.  d->flags takes what
+ * zj_decode_crops_device takes: ZJ_FLAG_GRAY_TO_RGB, an orientation or a prescale are the resized-crop calls'.  The launch's
+ * arguments pass through a small table of the context (a few KB per 32 frames), whose reuse is ordered on the caller's stream.
+ * zj_crop_tensor_out_len: C * w * h * the element's bytes; 0: not a valid window / dtype for d, or d has no tensor. */
+ZJ_API size_t zj_crop_tensor_out_len(const zj_frame_desc *d, unsigned w, unsigned h, int dtype);
+ZJ_API int zj_decode_crops_tensor_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
+                                         const int16_t *const *d_cb, const int16_t *const *d_cr, const unsigned *origins,
+                                         unsigned crop_w, unsigned crop_h, int dtype, int out_layout, const float *scale,
+                                         const float *bias, const uint8_t *flip, void *d_out, void *stream);
+/* ... of frames of MIXED geometry: descs[f] is frame f's own descriptor (size, sampling, tables, flags, in_components);
+ * out_colorspace and out_layout must be the same in all (ZJ_ERR_ARG otherwise); every window crop_w x crop_h.  Image f is
+ * byte for byte zj_decode_crops_tensor_device's for frame f alone.  Every frame is checked before anything is launched: the
+ * status is that call's for the first failing frame, and then nothing is written.  One launch per sampling mode. */
+ZJ_API int zj_decode_crops_tensor_mixed_device(zj_ctx *ctx, const zj_frame_desc *descs, size_t nframes,
+                                               const int16_t *const *d_y, const int16_t *const *d_cb,
+                                               const int16_t *const *d_cr, const unsigned *origins, unsigned crop_w,
+                                               unsigned crop_h, int dtype, int out_layout, const float *scale,
+                                               const float *bias, const uint8_t *flip, void *d_out, void *stream);
 /* Resize filters of the *_filtered_device entry points:
  *   ZJ_RESIZE_BILINEAR     the bilinear definition above: the entry points without a filter, byte for byte
  *   ZJ_RESIZE_BILINEAR_AA  antialiased: the triangle filter of Pillow's bilinear / F.interpolate(antialias=True), in exact
@@ -624,6 +655,29 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_device(zj_decoder *d, zj_ctx *c
                                                         unsigned h, unsigned out_w, unsigned out_h, int dtype, int out_layout,
                                                         const float *scale, const float *bias, int flip, void *d_out,
                                                         size_t out_cap, size_t *out_len);
+/* the decoder's last prepared file: the w x h window at (x, y) converted into one image of a normalised tensor, NOT resized
+ * (zj_decode_crops_tensor_device's contract; flip: non-zero mirrors the columns), left in HBM; the file path, its uploads
+ * and the stream ordering are zj_decoder_finish_pixels_crop_device's.  It takes the files that call takes, with an
+ * out_colorspace of RGB / YCBCR / GRAYSCALE, out_layout ZJ_LAYOUT_HWC and no out_pitch.  ZJ_ERR_UNSUPPORTED, with a
+ * zj_decoder_error text that says so: a one-component file of a decoder that asks for a colour output (ZJ_FLAG_GRAY_TO_RGB;
+ * with out_colorspace GRAYSCALE it has its one-channel tensor), four-component
+ * files (ZJ_FLAG_CMYK_TO_RGB) and files of another sampling or stored RGB (ZJ_FLAG_ANY_SAMPLING) -- those, an orientation
+ * and a prescale are the resized-crop calls'.  *out_len = zj_crop_tensor_out_len(); out_cap below it is ZJ_ERR_ARG. */
+ZJ_API int zj_decoder_finish_pixels_crop_tensor_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y, unsigned w,
+                                                       unsigned h, int dtype, int out_layout, const float *scale,
+                                                       const float *bias, int flip, void *d_out, size_t out_cap,
+                                                       size_t *out_len);
+/* n decoders' last prepared files, of any sizes, into ONE crop tensor: file k's window is w x h at origins[2k],
+ * origins[2k + 1], its image at d_out + k * zj_crop_tensor_out_len's bytes, image k what the single-file call above writes
+ * for file k.  The decoders must agree in out_colorspace and out_layout (ZJ_ERR_ARG).  Consecutive files the CPU walker
+ * decoded go through one mixed-geometry launch group; files prepared for device entropy, and every file the single-file
+ * call refuses (a one-component file among colour ones, four components, another sampling, a damaged file, a window that
+ * leaves the image), go through that call, which sets the decoder's error text.  rcs[k]: file k's status; a failed file
+ * leaves its image untouched and stops no other.  out_cap below n images is ZJ_ERR_ARG.  Synchronous. */
+ZJ_API int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx,
+                                                             const unsigned *origins, unsigned w, unsigned h, int dtype,
+                                                             int out_layout, const float *scale, const float *bias,
+                                                             const uint8_t *flip, void *d_out, size_t out_cap, int *rcs);
 /* ... with a resize filter (ZJ_RESIZE_*; any other is ZJ_ERR_ARG) */
 ZJ_API int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y,
                                                                  unsigned w, unsigned h, unsigned out_w, unsigned out_h,

@@ -11,8 +11,8 @@ from .host import (  # noqa: F401
     BACKEND_AVX2, BACKEND_HIP, BACKEND_SCALAR, FLAG_CLAMP_DC, FLAG_CORRECTED, FLAG_EDGE_REPLICATE, FLAG_ANY_SAMPLING, FLAG_CMYK_TO_RGB, FLAG_FULL_AC_VALUES, FLAG_GRAY_TO_RGB, FLAG_PLAIN_TAIL, LAYOUT_CHW, LAYOUT_HWC, ColorSpace, Component, Context, DecodeError, Decoder, FrameDesc,
     ENTROPY_CPU, ENTROPY_GPU, ENTROPY_GPU_ALWAYS, HUFF_ST, RETRY_CPU, FileBatchDecoder, ImageInfo, Pool, ZjError,
     ZuneJpegOptions, abi_symbols, choose_idct_func, choose_upsample_func,
-    choose_ycbcr_to_rgb_convert_func, device_count, finish_pixels_batch, finish_pixels_resized_crop_batch, lib, lib_path, num_components,
+    choose_ycbcr_to_rgb_convert_func, device_count, finish_pixels_batch, finish_pixels_resized_crop_batch, finish_pixels_crop_tensor_batch, lib, lib_path, num_components,
     SCATTER_MAX, Multi, pointer_device, shard_range, device_numa_node, bind_thread_near_device, thread_numa_node, variants_available,
-    crop_out_len, resized_out_len, scaled_size, scaled_crop_out_len, oriented_size, orient_window, DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8, TENSOR_NCHW, TENSOR_NHWC,
+    crop_out_len, resized_out_len, crop_tensor_out_len, scaled_size, scaled_crop_out_len, oriented_size, orient_window, DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8, TENSOR_NCHW, TENSOR_NHWC,
     RESIZE_BILINEAR, RESIZE_BILINEAR_AA, RESIZE_BICUBIC_AA, resize_filter,
 )

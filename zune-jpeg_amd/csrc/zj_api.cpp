@@ -14,6 +14,7 @@
 
 #include "../../include/zjhip.h"
 #include "zj_launch.h"
+#include "zj_crop_tensor_launch.h"
 #include "zj_mixed_launch.h"
 #include "zj_orient_launch.h"
 #include "zj_expand_launch.h"
@@ -1441,6 +1442,279 @@ int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t
         if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
     }
     return rc;
+}
+
+/* ---- crop windows into a normalised tensor, no resize ------------------------------ */
+size_t zj_crop_tensor_out_len(const zj_frame_desc* d, unsigned w, unsigned h, int dtype)
+{
+    Plan pl;
+    CropPlan cp;
+    if (!d || !crop_tensor_desc_ok(d) || make_crop_plan(d, w, h, 0, pl, cp) != ZJ_OK) return 0;
+    return crop_tensor_len(resize_channels(d), w, h, dtype);
+}
+
+namespace {
+// The checks of a tensor call in the order that decides a bad call's status: the pointers, the descriptor's kind, the
+// output's arguments, the crop plan and the windows (zj_decode_crops_device's).  s, b: the kernel's factors.
+int crop_tensor_args(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const unsigned* origins, unsigned w, unsigned h, int dtype,
+                     int out_layout, const float* scale, const float* bias, const void* d_out, Plan& pl, CropPlan& cp, float s[3],
+                     float b[3], size_t& img_bytes)
+{
+    if (!c || !d || !origins || !d_out || nframes == 0 || nframes > (size_t)1 << 20) return ZJ_ERR_ARG;
+    if (!crop_tensor_desc_ok(d)) return ZJ_ERR_UNSUPPORTED;
+    const int ch = resize_channels(d);
+    if (!resize_elem_bytes(dtype) || (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC)) return ZJ_ERR_ARG;
+    if ((uintptr_t)d_out % (uintptr_t)resize_elem_bytes(dtype)) return ZJ_ERR_ARG;
+    for (int k = 0; k < 3; k++) {
+        const float sc = scale && k < ch ? scale[k] : 1.f, bi = bias && k < ch ? bias[k] : 0.f;
+        if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
+        s[k] = sc * (1.f / 65536.f); // (resize_out_args: exact)
+        b[k] = bi;
+    }
+    int rc = make_crop_plan(d, w, h, 0, pl, cp);
+    if (rc) return rc;
+    if (!(img_bytes = crop_tensor_len(ch, w, h, dtype))) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < nframes; f++) {
+        int s0, s1, k0, k1;
+        if ((rc = crop_window(d, pl, cp, origins[2 * f], origins[2 * f + 1], s0, s1, k0, k1))) return rc;
+    }
+    return ZJ_OK;
+}
+
+// One launch of the tensor kernels: the n records from record `first` of the table, each of up to 2^shift frames of the
+// kernel (hs, vs, out); gx x gy: the widest tile-column / strip ranges over them
+struct CropTensorRun { int hs, vs, out, shift, gx, gy; size_t first; int n; };
+
+// The records into the context's pinned staging, one copy into its device table, then the zero launch and one launch per
+// run, all on st.  The staging and the table are the mixed-geometry calls' (mixed_tables): the host waits for the last
+// copy out of the staging before it writes it, st waits for the last launch that read the table before the copy.
+int crop_tensor_submit(zj_ctx* c, const std::vector<CropTensorParams>& recs, const std::vector<CropTensorZero>& zeros,
+                       const std::vector<CropTensorRun>& runs, hipStream_t st)
+{
+    const size_t rb = recs.size() * sizeof(CropTensorParams), zb = zeros.size() * sizeof(CropTensorZero);
+    int rc = mixed_tables(c, rb + zb);
+    if (rc) return rc;
+    memcpy(c->mx_host, recs.data(), rb);
+    if (zb) memcpy((uint8_t*)c->mx_host + rb, zeros.data(), zb);
+    if (c->mx_used) ZJ_HIP(c, hipStreamWaitEvent(st, c->mx_done, 0));
+    ZJ_HIP(c, hipMemcpyAsync(c->mx_dev, c->mx_host, rb + zb, hipMemcpyHostToDevice, st));
+    ZJ_HIP(c, hipEventRecord(c->mx_up, st));
+    c->mx_used = true;
+    const uint8_t* const tab = (const uint8_t*)c->mx_dev;
+    hipError_t e = hipSuccess;
+    if (!zeros.empty()) {
+        int rows = 0, frames = 0;
+        for (const CropTensorZero& z : zeros) {
+            if (z.h - z.rmin > rows) rows = z.h - z.rmin;
+            if (z.nframes > frames) frames = z.nframes;
+        }
+        e = launch_crop_tensor_zero((const CropTensorZero*)(tab + rb), (int)zeros.size(), rows, frames, st);
+    }
+    for (size_t i = 0; e == hipSuccess && i < runs.size(); i++) {
+        const CropTensorRun& r = runs[i];
+        e = launch_crop_tensor(r.hs, r.vs, r.out, (const CropTensorParams*)tab + r.first, r.n, r.shift, r.gx, r.gy, st);
+    }
+    // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
+    (void)hipEventRecord(c->mx_done, st);
+    ZJ_HIP(c, e);
+    return ZJ_OK;
+}
+
+// frames [0, nframes) of ONE geometry, checked: one record per SCATTER_MAX frames, all of them one launch, with the
+// converted zero for the windows' rows at or below rows_covered, if any has such rows
+int crop_tensor_launches(zj_ctx* c, const zj_frame_desc* d, const Plan& pl, const CropPlan& cp, size_t nframes,
+                         const int16_t* const* y, const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins,
+                         int dtype, int out_layout, const float* s, const float* b, const uint8_t* flip, uint8_t* d_out,
+                         size_t img_bytes, hipStream_t st)
+{
+    const size_t nrec = (nframes + SCATTER_MAX - 1) / SCATTER_MAX;
+    std::vector<CropTensorParams> recs(nrec);
+    std::vector<CropTensorZero> zeros;
+    CropTensorRun run{pl.hs, pl.vs, pl.out, CROP_TENSOR_SHIFT, 0, 0, 0, (int)nrec};
+    for (size_t r = 0; r < nrec; r++) {
+        const size_t f0 = r * SCATTER_MAX;
+        const int n = (int)(nframes - f0 < (size_t)SCATTER_MAX ? nframes - f0 : (size_t)SCATTER_MAX);
+        CropTensorZero z;
+        if (crop_tensor_fill(d, pl, cp, y, cb, cr, d_out, img_bytes, origins, dtype, out_layout == ZJ_TENSOR_NHWC, s, b, flip, f0, n,
+                             recs[r], z))
+            zeros.push_back(z);
+        if (recs[r].cp.ncols > run.gx) run.gx = recs[r].cp.ncols;
+        if (recs[r].cp.nstrips > run.gy) run.gy = recs[r].cp.nstrips;
+    }
+    return crop_tensor_submit(c, recs, zeros, std::vector<CropTensorRun>(1, run), st);
+}
+
+// The call behind both mixed entry points: frames that each bring their own descriptor, one window size, one tensor.
+// host_planes: y / cb / cr are the CPU walker's planes in host memory; the strips each window needs go into the context's
+// arena in one copy (crops_resized_mixed_impl's way; the planes must stay as they are until the stream has run: the caller
+// synchronises).  Every frame is checked before anything is launched; the status is the single-frame call's for the first
+// failing frame.
+int crops_tensor_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                            const int16_t* const* cb, const int16_t* const* cr, bool host_planes, const unsigned* origins,
+                            unsigned w, unsigned h, int dtype, int out_layout, const float* scale, const float* bias,
+                            const uint8_t* flip, void* d_out, void* stream)
+{
+    if (!c || !descs || !origins || !d_out || !y || nframes == 0 || nframes > (size_t)1 << 20) return ZJ_ERR_ARG;
+    if (!mixed_descs_agree(descs, nframes)) return ZJ_ERR_ARG;
+    std::vector<Plan> pls(nframes);
+    std::vector<CropPlan> cps(nframes);
+    float s[3], b[3];
+    size_t img = 0;
+    for (size_t f = 0; f < nframes; f++) {
+        int rc = crop_tensor_args(c, &descs[f], 1, origins + 2 * f, w, h, dtype, out_layout, scale, bias, d_out, pls[f], cps[f], s, b, img);
+        if (rc) return rc;
+        const bool chroma = pls[f].out != OUT_GRAY;
+        if (chroma && (!cb || !cr)) return ZJ_ERR_ARG;
+        if (host_planes) { if (!y[f] || (chroma && (!cb[f] || !cr[f]))) return ZJ_ERR_ARG; }
+        else if ((rc = check_plane_ptrs(y + f, chroma ? cb + f : nullptr, chroma ? cr + f : nullptr, chroma, 1))) return rc;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    // (first: it waits until the copies out of the pinned stagings, the planes' and the tables', have finished)
+    int rc = mixed_tables(c, nframes * (sizeof(CropTensorParams) + sizeof(CropTensorZero)));
+    if (rc) return rc;
+    std::vector<const int16_t*> py(nframes), pcb(nframes), pcr(nframes);
+    if (host_planes) {
+        std::vector<size_t> r0(nframes), r1(nframes), yrow(nframes), crow(nframes);
+        size_t total = 0;
+        for (size_t f = 0; f < nframes; f++) {
+            const Plan& pl = pls[f];
+            int s0, s1, k0, k1;
+            crop_window(&descs[f], pl, cps[f], origins[2 * f], origins[2 * f + 1], s0, s1, k0, k1);
+            r0[f] = (size_t)s0; r1[f] = (size_t)s1;
+            yrow[f] = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8); crow[f] = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+            total += (r1[f] - r0[f]) * (yrow[f] + (pl.out != OUT_GRAY ? 2 * crow[f] : 0)) * 2;
+        }
+        if (total > c->mx_arena_cap) {
+            ZJ_HIP(c, hipStreamSynchronize(st));
+            if (c->mx_arena) { ZJ_HIP(c, hipFree(c->mx_arena)); c->mx_arena = nullptr; }
+            if (c->mx_stage) { ZJ_HIP(c, hipHostFree(c->mx_stage)); c->mx_stage = nullptr; }
+            c->mx_arena_cap = 0;
+            const size_t cap = total + total / 4 + 4096;
+            ZJ_HIP(c, hipHostMalloc(&c->mx_stage, cap, hipHostMallocDefault));
+            ZJ_HIP(c, hipMalloc(&c->mx_arena, cap));
+            c->mx_arena_cap = cap;
+        }
+        size_t at = 0; // i16 elements into staging and arena alike
+        for (size_t f = 0; f < nframes; f++) {
+            const bool chroma = pls[f].out != OUT_GRAY;
+            const int16_t* const src[3] = {y[f], chroma ? cb[f] : nullptr, chroma ? cr[f] : nullptr};
+            const int16_t** const dst[3] = {&py[f], &pcb[f], &pcr[f]};
+            for (int k = 0; k < 3; k++) {
+                const size_t row = k ? crow[f] : yrow[f], n = (r1[f] - r0[f]) * row;
+                *dst[k] = nullptr;
+                if (!src[k]) continue;
+                // (the address the plane's row 0 would have: every address a lane forms lies in a strip of its window)
+                *dst[k] = (const int16_t*)((uintptr_t)c->mx_arena + 2 * at - 2 * r0[f] * row);
+                if (n) memcpy((int16_t*)c->mx_stage + at, src[k] + r0[f] * row, n * 2);
+                at += n;
+            }
+        }
+        if (at) ZJ_HIP(c, hipMemcpyAsync(c->mx_arena, c->mx_stage, at * 2, hipMemcpyHostToDevice, st));
+    } else {
+        for (size_t f = 0; f < nframes; f++) {
+            const bool chroma = pls[f].out != OUT_GRAY;
+            py[f] = y[f]; pcb[f] = chroma ? cb[f] : nullptr; pcr[f] = chroma ? cr[f] : nullptr;
+        }
+    }
+    // one record per frame, the frames of one kernel in one run
+    std::vector<CropTensorParams> recs(nframes);
+    std::vector<CropTensorZero> zeros;
+    std::vector<CropTensorRun> runs;
+    size_t at = 0;
+    for (int mode = 0; mode < 4; mode++)
+        for (int gray = 0; gray < 2; gray++) {
+            const int hs = 1 + (mode & 1), vs = 1 + (mode >> 1);
+            CropTensorRun run{hs, vs, 0, 0, 0, 0, at, 0};
+            for (size_t f = 0; f < nframes; f++) {
+                const Plan& pl = pls[f];
+                if (pl.hs != hs || pl.vs != vs || (pl.out == OUT_GRAY) != (gray != 0)) continue;
+                CropTensorZero z;
+                if (crop_tensor_fill(&descs[f], pl, cps[f], py.data(), pcb.data(), pcr.data(), (uint8_t*)d_out, img, origins, dtype,
+                                     out_layout == ZJ_TENSOR_NHWC, s, b, flip, f, 1, recs[at], z))
+                    zeros.push_back(z);
+                run.out = pl.out;
+                if (recs[at].cp.ncols > run.gx) run.gx = recs[at].cp.ncols;
+                if (recs[at].cp.nstrips > run.gy) run.gy = recs[at].cp.nstrips;
+                run.n++; at++;
+            }
+            if (run.n) runs.push_back(run);
+        }
+    return crop_tensor_submit(c, recs, zeros, runs, st);
+}
+} // namespace
+
+int zj_decode_crops_tensor_mixed_device(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
+                                        const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* origins,
+                                        unsigned crop_w, unsigned crop_h, int dtype, int out_layout, const float* scale,
+                                        const float* bias, const uint8_t* flip, void* d_out, void* stream)
+{
+    return crops_tensor_mixed_impl(c, descs, nframes, d_y, d_cb, d_cr, false, origins, crop_w, crop_h, dtype, out_layout, scale, bias,
+                                   flip, d_out, stream);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_crop_tensor_batch_device): the same over the CPU walker's planes in
+// host memory, on the context stream, synchronised (the planes are free again when it returns)
+int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                  const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins, unsigned w, unsigned h,
+                                  int dtype, int out_layout, const float* scale, const float* bias, const uint8_t* flip, void* d_out)
+{
+    const int rc = crops_tensor_mixed_impl(c, descs, nframes, y, cb, cr, true, origins, w, h, dtype, out_layout, scale, bias, flip,
+                                           d_out, nullptr);
+    if (c && c->stream) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
+    }
+    return rc;
+}
+
+int zj_decode_crops_tensor_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
+                                  const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* origins,
+                                  unsigned crop_w, unsigned crop_h, int dtype, int out_layout, const float* scale,
+                                  const float* bias, const uint8_t* flip, void* d_out, void* stream)
+{
+    Plan pl;
+    CropPlan cp;
+    float s[3], b[3];
+    size_t img_bytes = 0;
+    int rc = crop_tensor_args(c, d, nframes, origins, crop_w, crop_h, dtype, out_layout, scale, bias, d_out, pl, cp, s, b, img_bytes);
+    if (rc) return rc;
+    if ((rc = check_plane_ptrs(d_y, d_cb, d_cr, pl.out != OUT_GRAY, nframes))) return rc;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return crop_tensor_launches(c, d, pl, cp, nframes, d_y, d_cb, d_cr, origins, dtype, out_layout, s, b, flip, (uint8_t*)d_out,
+                                img_bytes, st);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_crop_tensor_device): one frame's window on the context stream,
+// synchronised, from planes in host memory (only the strips the window needs are uploaded, as zjint_crop_frame) or in HBM
+int zjint_crop_tensor_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                            int planes_on_device, unsigned x, unsigned yy, unsigned w, unsigned h, int dtype, int out_layout,
+                            const float* scale, const float* bias, int flip, void* d_out)
+{
+    Plan pl;
+    CropPlan cp;
+    float s[3], b[3];
+    size_t img_bytes = 0;
+    const unsigned origin[2] = {x, yy};
+    int rc = crop_tensor_args(c, d, 1, origin, w, h, dtype, out_layout, scale, bias, d_out, pl, cp, s, b, img_bytes);
+    if (rc) return rc;
+    const bool chroma = pl.out != OUT_GRAY;
+    if (!y || (chroma && (!cb || !cr))) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    const int16_t* p[3] = {y, cb, cr};
+    if (!planes_on_device) {
+        int s0, s1, k0, k1;
+        crop_window(d, pl, cp, x, yy, s0, s1, k0, k1);
+        const size_t yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8), crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+        if ((rc = upload_plane_rows(c, pl, chroma, y, cb, cr, (size_t)s0, (size_t)s1, yrow, crow, p))) return rc;
+    }
+    const uint8_t fl = flip ? 1 : 0;
+    if ((rc = crop_tensor_launches(c, d, pl, cp, 1, &p[0], &p[1], &p[2], origin, dtype, out_layout, s, b, &fl, (uint8_t*)d_out,
+                                   img_bytes, c->stream)))
+        return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
 }
 
 int zj_oriented_size(int orientation, unsigned w, unsigned h, unsigned* ow, unsigned* oh)

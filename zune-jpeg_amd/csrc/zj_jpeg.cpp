@@ -3118,6 +3118,124 @@ int zj_decoder_finish_pixels_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x,
     return finish_window(d, ctx, false, 0, x, y, w, h, d_out, out_cap, out_pitch, out_len);
 }
 
+// ... and one frame's window converted straight into a tensor image
+__attribute__((weak)) int zjint_crop_tensor_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
+                                                  int planes_on_device, unsigned x, unsigned yy, unsigned w, unsigned h, int dtype,
+                                                  int out_layout, const float* scale, const float* bias, int flip, void* d_out);
+
+// The window x, y, w, h of the decoder's last file converted into one image of a normalised tensor, not resized:
+// zj_decode_crops_tensor_device's contract over the crop file path (finish_window: with a scan prepared for the device the
+// planes in HBM, otherwise the CPU walker's planes uploaded by the strips the window needs).
+int zj_decoder_finish_pixels_crop_tensor_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                                int dtype, int out_layout, const float* scale, const float* bias, int flip,
+                                                void* d_out, size_t out_cap, size_t* out_len)
+{
+    using namespace zj;
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    if (!zjint_crop_tensor_frame || !zjint_scan_to_planes) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
+    if (d->odd) return fail(d, ZJ_ERR_UNSUPPORTED, kOddOnlyResized);
+    // (a one-component file is always decoded as GRAYSCALE, fill_info: for a decoder that asks for three channels that is not
+    // the tensor the caller sized)
+    if (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE)
+        return fail(d, ZJ_ERR_UNSUPPORTED, "a one-component file has a GRAYSCALE crop tensor only (ZJ_FLAG_GRAY_TO_RGB is the resized-crop calls')");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int ch = resize_channels(&fd);
+    if (!ch || fd.out_layout != ZJ_LAYOUT_HWC || fd.out_pitch != 0)
+        return fail(d, ZJ_ERR_UNSUPPORTED, "crop tensors have 1 or 3 channels, from a decoder with out_layout HWC and no out_pitch");
+    const size_t need = (size_t)ch * w * h * (size_t)resize_elem_bytes(dtype);
+    if (out_len) *out_len = need;
+    const WindowLayout g = window_layout(&fd, w, h, 0);
+    if (!need || !window_inside(g, x, y, w, h, fd.width, fd.height)) return fail(d, ZJ_ERR_ARG, "not a valid crop window or dtype");
+    if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
+    const auto window = [&](const int16_t* yp, const int16_t* cb, const int16_t* cr, int on_device) {
+        const int rc = zjint_crop_tensor_frame(ctx, &fd, yp, cb, cr, on_device, x, y, w, h, dtype, out_layout, scale, bias, flip, d_out);
+        return rc ? fail(d, rc, std::string("crop tensor: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : (int)ZJ_OK;
+    };
+    if (d->scan_ready) {
+        const int16_t* planes[3] = {nullptr, nullptr, nullptr};
+        unsigned status = 0;
+        const int rc = zjint_scan_to_planes(ctx, &fd, d->blob_store.p, d->blob_len, planes, &status);
+        d->gpu_status = status;
+        if (rc == ZJ_OK) return window(planes[0], planes[1], planes[2], 1);
+        if (rc != ZJ_RETRY_CPU) return fail(d, rc, std::string("GPU entropy stage: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
+        const uint8_t* src = d->src;
+        const size_t src_len = d->src_len;
+        const int rc2 = decode_all(d, src, src_len, false, false);
+        if (rc2) return rc2;
+    }
+    return window(d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr, d->ncomp == 3 ? d->comps[2].coef : nullptr, 0);
+}
+
+// ... and the crop tensors of several files' planes in host memory, each of its own geometry
+__attribute__((weak)) int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                                        const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins,
+                                                        unsigned w, unsigned h, int dtype, int out_layout, const float* scale,
+                                                        const float* bias, const uint8_t* flip, void* d_out);
+
+// Several prepared files of any sizes into one crop tensor, every window w x h (after 3.10's batch call).  The
+// files the CPU walker decoded go through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan
+// left for the device, and every file the single-file call refuses, is finished (or refused, with its text) by that call.
+// rcs[k]: file k's status; a failed file leaves its image untouched and stops no other.
+int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* origins,
+                                                      unsigned w, unsigned h, int dtype, int out_layout, const float* scale,
+                                                      const float* bias, const uint8_t* flip, void* d_out, size_t out_cap, int* rcs)
+{
+    using namespace zj;
+    if (!ds || !n || !ctx || !origins || !d_out || !rcs) return ZJ_ERR_ARG;
+    if (!zjint_crops_tensor_mixed_host || !zjint_crop_tensor_frame) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    const zj_decoder* first = nullptr;
+    for (size_t k = 0; k < n; k++) {
+        if (!ds[k]) continue;
+        if (!first) first = ds[k];
+        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
+    }
+    if (!first) return ZJ_ERR_ARG;
+    zj_frame_desc fd0{};
+    fd0.out_colorspace = (uint32_t)first->out_colorspace;
+    // (0: every file's own call says why)
+    const size_t img = (size_t)resize_channels(&fd0) * w * h * (size_t)resize_elem_bytes(dtype);
+    if (img && out_cap / img < n) return ZJ_ERR_ARG;
+    const auto single = [&](size_t k) {
+        return zj_decoder_finish_pixels_crop_tensor_device(ds[k], ctx, origins[2 * k], origins[2 * k + 1], w, h, dtype, out_layout, scale,
+                                                           bias, flip ? flip[k] : 0, (uint8_t*)d_out + k * img, img, nullptr);
+    };
+    std::vector<zj_frame_desc> fds(n);
+    std::vector<const int16_t*> py(n), pcb(n), pcr(n);
+    std::vector<char> mixed(n, 0);
+    for (size_t k = 0; k < n; k++) {
+        zj_decoder* const d = ds[k];
+        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
+        // what the mixed call does not take, or the single-file call refuses with a text of its own: that call
+        if (!img || !d->seen_sof || d->err_code || d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd ||
+            (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE)) { rcs[k] = single(k); continue; }
+        fill_info(d, nullptr, &fds[k]);
+        const WindowLayout g = window_layout(&fds[k], w, h, 0);
+        if (fds[k].out_layout != ZJ_LAYOUT_HWC || !window_inside(g, origins[2 * k], origins[2 * k + 1], w, h, fds[k].width, fds[k].height)) {
+            rcs[k] = single(k);
+            continue;
+        }
+        py[k] = d->comps[0].coef;
+        pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
+        rcs[k] = ZJ_OK;
+        mixed[k] = 1;
+    }
+    for (size_t k0 = 0; k0 < n;) {
+        if (!mixed[k0]) { k0++; continue; }
+        size_t k1 = k0;
+        while (k1 < n && mixed[k1]) k1++;
+        const int rc = zjint_crops_tensor_mixed_host(ctx, fds.data() + k0, k1 - k0, py.data() + k0, pcb.data() + k0, pcr.data() + k0,
+                                                     origins + 2 * k0, w, h, dtype, out_layout, scale, bias, flip ? flip + k0 : nullptr,
+                                                     (uint8_t*)d_out + k0 * img);
+        // a run that is refused has launched nothing: each of its files through its own call, which names the failing one
+        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(k) : (int)ZJ_OK;
+        k0 = k1;
+    }
+    return ZJ_OK;
+}
+
 // The decoder's last prepared file at 1 / 2^scale_log2, cut to the window x, y, w, h of the REDUCED frame (all four 0: the
 // whole reduced frame): zj_decode_crops_scaled_device's contract.  With the CPU walker only the MCU rows the window's blocks
 // lie in are uploaded; with device entropy the planes in HBM are used.

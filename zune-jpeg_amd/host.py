@@ -196,6 +196,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decode_crops_resized_mixed_device", "zj_decoder_finish_pixels_resized_crop_batch_device",
     "zj_gray_to_rgb_device", "zj_cmyk_to_rgb_device", "zj_decoder_adobe_transform", "zj_decoder_plane",
     "zj_planes_to_rgb_device", "zj_decoder_stored_rgb", "zj_decoder_component_sampling",
+    "zj_crop_tensor_out_len", "zj_decode_crops_tensor_device", "zj_decoder_finish_pixels_crop_tensor_device",
+    "zj_decode_crops_tensor_mixed_device", "zj_decoder_finish_pixels_crop_tensor_batch_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -336,6 +338,16 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                                                C.c_uint, C.c_int, C.c_int, vp, vp, C.c_int, vp, sz,
                                                                C.POINTER(sz)]
+    L.zj_crop_tensor_out_len.restype = sz
+    L.zj_crop_tensor_out_len.argtypes = [C.POINTER(FrameDesc), C.c_uint, C.c_uint, C.c_int]
+    L.zj_decode_crops_tensor_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_int,
+                                                C.c_int, vp, vp, vp, vp, vp]
+    L.zj_decoder_finish_pixels_crop_tensor_device.argtypes = [vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                              vp, vp, C.c_int, vp, sz, C.POINTER(sz)]
+    L.zj_decode_crops_tensor_mixed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, vp,
+                                                      vp, vp]
+    L.zj_decoder_finish_pixels_crop_tensor_batch_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp,
+                                                                    vp, vp, sz, vp]
     L.zj_resize_filtered_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp,
                                             vp, C.c_int, vp, vp]
     L.zj_decode_crops_resized_filtered_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
@@ -419,6 +431,11 @@ def crop_out_len(desc, w, h, out_pitch=0):
 def resized_out_len(desc, out_w, out_h, dtype):
     """bytes of one out_w x out_h resized output of frames of `desc` (zj_resized_out_len); 0: not supported"""
     return lib().zj_resized_out_len(C.byref(desc), out_w, out_h, dtype)
+
+
+def crop_tensor_out_len(desc, w, h, dtype):
+    """bytes of one image of the tensor of w x h crops of frames of `desc` (zj_crop_tensor_out_len); 0: not supported"""
+    return lib().zj_crop_tensor_out_len(C.byref(desc), w, h, dtype)
 
 
 def scale_log2(scale):
@@ -745,6 +762,36 @@ class Context:
         else:
             _check(lib().zj_decode_crops_resized_device(*args, d_out, stream), "zj_decode_crops_resized_device", self._h)
 
+    def decode_crops_tensor_device(self, desc, d_y, d_cb, d_cr, origins, w, h, dtype, out_layout, d_out, scale=None, bias=None,
+                                   flips=None, stream=None):
+        """Crop windows straight into a normalised tensor, not resized (zj_decode_crops_tensor_device): pointers and
+        origins as in decode_crops_device, every window w x h; the dense output at d_out, image f of crop_tensor_out_len
+        bytes.  dtype, out_layout, scale, bias, flips as decode_crops_resized_device.  Asynchronous on `stream`."""
+        n = len(d_y)
+        if len(origins) != n:
+            raise ValueError("one origin per frame")
+        arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
+        org = (C.c_uint * (2 * n))(*[int(v) for xy in origins for v in xy])
+        _check(lib().zj_decode_crops_tensor_device(self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), org, w, h, dtype,
+                                                   out_layout, _floats(scale), _floats(bias), _flips(flips, n), d_out, stream),
+               "zj_decode_crops_tensor_device", self._h)
+
+    def decode_crops_tensor_mixed_device(self, descs, d_y, d_cb, d_cr, origins, w, h, dtype, out_layout, d_out, scale=None,
+                                         bias=None, flips=None, stream=None):
+        """Crop windows of frames of MIXED geometry straight into a normalised tensor (zj_decode_crops_tensor_mixed_device):
+        descs = one FrameDesc per frame (out_colorspace and out_layout the same in all), every window w x h; the other
+        arguments as decode_crops_tensor_device.  Image f equals that call's for frame f alone.  Asynchronous on `stream`."""
+        n = len(d_y)
+        if len(descs) != n or len(origins) != n:
+            raise ValueError("one descriptor and origin per frame")
+        arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
+        org = (C.c_uint * (2 * n))(*[int(v) for xy in origins for v in xy])
+        darr = (FrameDesc * n)(*descs)
+        _check(lib().zj_decode_crops_tensor_mixed_device(self._h, darr, n, arr(d_y), arr(d_cb), arr(d_cr), org, w, h, dtype,
+                                                         out_layout, _floats(scale), _floats(bias), _flips(flips, n), d_out,
+                                                         stream),
+               "zj_decode_crops_tensor_mixed_device", self._h)
+
     def decode_crops_resized_mixed_device(self, descs, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out,
                                           scale=None, bias=None, flips=None, stream=None, antialias=False, max_prescale=1,
                                           orientations=None, interpolation="bilinear"):
@@ -1023,6 +1070,20 @@ class Decoder:
             self._raise(rc)
         return n.value
 
+    def finish_pixels_crop_tensor_device(self, x, y, w, h, dtype, out_layout, d_out, cap, scale=None, bias=None, flip=False):
+        """Stage 2 cut to the w x h window at (x, y) and converted into one image of a normalised tensor, not resized (the
+        contract of zj_decode_crops_tensor_device), left in HBM at device pointer d_out; returns the image's length in
+        bytes."""
+        if self._ctx is None:
+            self._ctx = Context()
+        n = C.c_size_t(0)
+        rc = lib().zj_decoder_finish_pixels_crop_tensor_device(self._d, self._ctx.handle, x, y, w, h, dtype, out_layout,
+                                                               _floats(scale), _floats(bias), 1 if flip else 0, d_out, cap,
+                                                               C.byref(n))
+        if rc:
+            self._raise(rc)
+        return n.value
+
     def finish_pixels_scaled_device(self, scale, d_out, cap, window=None, out_pitch=0):
         """Stage 2 at 1/scale (2, 4 or 8), cut to window = (x, y, w, h) of the reduced frame (None: all of it), pixels left
         in HBM at device pointer d_out (the contract of zj_decode_crops_scaled_device); returns the length in bytes."""
@@ -1188,6 +1249,25 @@ def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype
                                                                     scale_log2(max_prescale), 1 if apply_orientation else 0,
                                                                     d_out, cap, rcs),
            "zj_decoder_finish_pixels_resized_crop_batch_device", ctx.handle)
+    return list(rcs)
+
+
+def finish_pixels_crop_tensor_batch(decoders, ctx, origins, w, h, dtype, out_layout, d_out, cap, scale=None, bias=None,
+                                    flips=None):
+    """zj_decoder_finish_pixels_crop_tensor_batch_device over Decoder objects that went through prepare() or
+    decode_coefficients(), each with a file of its own size: origins = one (x, y) per decoder, every window w x h, image k
+    left at device pointer d_out + k * crop_tensor_out_len.  Returns the list of statuses: image k is
+    Decoder.finish_pixels_crop_tensor_device's for decoder k alone, a failed file's slot is untouched."""
+    n = len(decoders)
+    if len(origins) != n:
+        raise ValueError("one origin per decoder")
+    dptr = (C.c_void_p * n)(*[d._d for d in decoders])
+    org = (C.c_uint * (2 * n))(*[int(v) for xy in origins for v in xy])
+    rcs = (C.c_int * n)()
+    _check(lib().zj_decoder_finish_pixels_crop_tensor_batch_device(dptr, n, ctx.handle, org, w, h, dtype, out_layout,
+                                                                   _floats(scale), _floats(bias), _flips(flips, n), d_out, cap,
+                                                                   rcs),
+           "zj_decoder_finish_pixels_crop_tensor_batch_device", ctx.handle)
     return list(rcs)
 
 

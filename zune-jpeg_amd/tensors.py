@@ -198,6 +198,38 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     return out
 
 
+def decode_crops_to_normalized_tensor(ctx, desc, frames, origins, size, dtype=None, layout="NCHW", mean=None, std=None,
+                                      flips=None, stream=None):
+    """Crop windows converted and normalised into ONE dense tensor WITHOUT a resize (zj_decode_crops_tensor_device,
+    DESIGN.md 3.14): frames = a list of (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE
+    output), origins = one (x, y) per frame, size = (w, h) of every window (any size inside the frame: no 8192 limit).
+    Returns [N, C, h, w] ("NCHW") or [N, h, w, C] ("NHWC") of `dtype` (default bfloat16), element for element what
+    decode_resized_crops_to_tensor gives for windows of exactly `size`, written once by one launch per 32 frames.  dtype,
+    mean / std and flips as there.  Stream and allocator rules as decode_to_tensor."""
+    import torch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(frames)
+    if n == 0 or len(origins) != n:
+        raise ValueError("one origin per frame, at least one frame")
+    w, h = size
+    if lib().zj_crop_tensor_out_len(C.byref(desc), w, h, code) == 0:
+        raise ValueError(f"{w}x{h} {dtype} is not a supported crop tensor of this frame descriptor")
+    channels = ColorSpace(desc.out_colorspace).num_components()
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = frames[0][0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    _on_stream(s, cur, [p for fr in frames for p in fr])
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ctx.decode_crops_tensor_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
+                                   [ptr(fr[2]) for fr in frames], origins, w, h, code,
+                                   TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
+                                   s.cuda_stream)
+    return out
+
+
 def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
                                    antialias=False, interpolation="bilinear", max_prescale=1, apply_orientation=False,
                                    options=None, workers=1, stream=None, decoders=None):
@@ -277,6 +309,68 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
                                            TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(),
                                            out.numel() * out.element_size(), scale, bias, flips, antialias, max_prescale,
                                            apply_orientation, interpolation)
+    for k, rc in enumerate(rcs):
+        if rc:
+            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+    return out
+
+
+def decode_files_cropped_to_tensor(ctx, blobs, origins, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
+                                   options=None, workers=1, stream=None, decoders=None):
+    """JPEG files -> ONE dense tensor of their size = (w, h) windows, converted and normalised but NOT resized
+    (zj_decoder_finish_pixels_crop_tensor_batch_device): blobs = a list of bytes-like JPEG files, origins = one
+    (x, y) per file, or None: the whole image, and then every file must measure exactly `size` (ValueError naming the
+    first that does not).  Returns [N, C, h, w] ("NCHW") or [N, h, w, C] ("NHWC") of `dtype` (default bfloat16); image k
+    is Decoder.finish_pixels_crop_tensor_device's for file k.  dtype, mean / std, flips, options, workers, decoders and
+    stream as decode_files_resized_to_tensor.  The batch call runs on the context's stream and has finished when it
+    returns; a file that fails raises DecodeError naming its index (its image is untouched, the others are decoded).  Files that need FLAG_GRAY_TO_RGB,
+    FLAG_CMYK_TO_RGB or FLAG_ANY_SAMPLING, an orientation or a prescale are decode_files_resized_to_tensor's."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from .host import DecodeError, Decoder, finish_pixels_crop_tensor_batch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(blobs)
+    if n == 0 or (origins is not None and len(origins) != n) or (flips is not None and len(flips) != n):
+        raise ValueError("one origin (and flip) per file, at least one file")
+    decs = decoders if decoders is not None else []
+    while len(decs) < n:
+        decs.append(Decoder(options, ctx))
+    decs = decs[:n]
+
+    def prep(k):
+        try:
+            return decs[k].prepare(blobs[k])
+        except DecodeError as e:
+            return e
+
+    nw = max(1, min(int(workers), 16, n))
+    if nw > 1:
+        with ThreadPoolExecutor(nw) as ex:
+            prepared = list(ex.map(prep, range(n)))
+    else:
+        prepared = [prep(k) for k in range(n)]
+    for k, r in enumerate(prepared):
+        if isinstance(r, DecodeError):
+            raise DecodeError(r.status, f"file {k}: {r.text}")
+    w, h = size
+    if origins is None:
+        for k in range(n):
+            info = prepared[k][1]
+            if (int(info.width), int(info.height)) != (w, h):
+                raise ValueError(f"file {k} is {info.width}x{info.height}, not {w}x{h}: give origins")
+        origins = [(0, 0)] * n
+    channels = ColorSpace(decs[0]._out_cs).num_components()
+    if channels not in (1, 3):
+        raise ValueError("crop tensors have 1 or 3 channels")
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    s.synchronize()  # (the allocator may hand out a block that work queued on `s` still uses: the files run on the context's stream)
+    rcs = finish_pixels_crop_tensor_batch(decs, ctx, origins, w, h, code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC,
+                                          out.data_ptr(), out.numel() * out.element_size(), scale, bias, flips)
     for k, rc in enumerate(rcs):
         if rc:
             raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
