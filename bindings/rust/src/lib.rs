@@ -233,6 +233,18 @@ extern "C" {
                                                        h: c_uint, dtype: c_int, out_layout: c_int, scale: *const f32,
                                                        bias: *const f32, flip: c_int, d_out: *mut c_void, out_cap: usize,
                                                        out_len: *mut usize) -> c_int;
+    pub fn zj_decoder_finish_pixels_crop_tensor_oriented_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint,
+                                                                w: c_uint, h: c_uint, dtype: c_int, out_layout: c_int,
+                                                                scale: *const f32, bias: *const f32, flip: c_int,
+                                                                d_out: *mut c_void, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn zj_decoder_finish_pixels_crop_tensor_batch_oriented_device(ds: *const *mut zj_decoder, n: usize, ctx: *mut zj_ctx,
+                                                                      origins: *const c_uint, w: c_uint, h: c_uint,
+                                                                      dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                                      bias: *const f32, flip: *const u8, d_out: *mut c_void,
+                                                                      out_cap: usize, rcs: *mut c_int) -> c_int;
+    pub fn zj_to_tensor_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, w: c_uint, h: c_uint, in_pitch: *const c_uint,
+                               in_channels: c_int, channels: c_int, dtype: c_int, out_layout: c_int, scale: *const f32,
+                               bias: *const f32, flip: *const u8, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn zj_decoder_finish_pixels_resized_crop_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint, w: c_uint,
                                                         h: c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
                                                         out_layout: c_int, scale: *const f32, bias: *const f32, flip: c_int,

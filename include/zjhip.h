@@ -146,14 +146,16 @@ typedef struct zj_frame_desc {
  * front-end yields the coded values, which is what libjpeg decodes. */
 #define ZJ_FLAG_FULL_AC_VALUES 8u
 /* Gray to RGB: a one-component JPEG shown as an RGB image with R = G = B, what image viewers and
- * Pillow's convert("RGB") give.  Off by default, and honoured by the RESIZED-CROP family only:
+ * Pillow's convert("RGB") give.  Off by default, and honoured by the RESIZED-CROP family and, for files, by the crop-tensor
+ * file calls (zj_decoder_finish_pixels_crop_tensor*_device: the GRAYSCALE u8 crop through zj_to_tensor_device, 1 -> 3
+ * channels) only:
  *   zj_frame_desc.flags   zj_decode_crops_resized_device, _filtered_, _prescaled_, _oriented_ and _mixed_, and
  *                         zj_resized_out_len: a descriptor with in_components == 1 and out_colorspace == ZJ_CS_RGB is decoded
  *                         as GRAYSCALE and expanded to 3 channels in front of the resize (without the flag such a descriptor
  *                         is refused: ZJ_ERR_UNSUPPORTED).  Every other entry point returns what it returns for an unknown
  *                         flag bit (ZJ_ERR_ARG);
- *   zj_options.flags      a one-component file finished through zj_decoder_finish_pixels_resized_crop*_device or the batch
- *                         call by a decoder whose out_colorspace is ZJ_CS_RGB gives a 3-channel image: the slot size,
+ *   zj_options.flags      a one-component file finished through zj_decoder_finish_pixels_resized_crop*_device, the batch
+ *                         call or the crop-tensor file calls by a decoder whose out_colorspace is ZJ_CS_RGB gives a 3-channel image: the slot size,
  *                         *out_len and the capacity check all use 3 channels.  (Without the flag the file is GRAYSCALE
  *                         whatever the decoder asks for, src/headers.rs:283-290: a 1-channel image.)
  * DEFINITION: the image equals, byte for byte, zj_resize_filtered_device applied to the 3-channel u8 image E, in the layout
@@ -177,8 +179,9 @@ typedef struct zj_frame_desc {
  * zj_decoder_plane and build descriptors of their own -- three components for planes 0-2, one component for plane 3.
  * A file whose width is below 57 and no multiple of 8 is ZJ_ERR_PANIC at full resolution, as a one-component frame of that
  * width is (component 4's GRAYSCALE decode); a reduced-size decode under the resize (max_prescale_log2) decodes it.
- * Such a file is finished by the RESIZED-CROP family only (zj_decoder_finish_pixels_resized_crop*_device and the batch call),
- * by a decoder whose out_colorspace is ZJ_CS_RGB; every other finish call, zj_decoder_decode_buffer and the pool, and a decoder
+ * Such a file is finished by the RESIZED-CROP family (zj_decoder_finish_pixels_resized_crop*_device and the batch call) and
+ * by the crop-tensor file calls (zj_decoder_finish_pixels_crop_tensor*_device: E below through zj_to_tensor_device, DESIGN.md
+ * 3.15) only, by a decoder whose out_colorspace is ZJ_CS_RGB; every other finish call, zj_decoder_decode_buffer and the pool, and a decoder
  * that asks for GRAYSCALE or YCBCR, return ZJ_ERR_UNSUPPORTED.
  * DEFINITION: the image equals, byte for byte, zj_resize_filtered_device applied to the 3-channel u8 image E with
  * E[c] = zj_cmyk_to_rgb_device(A[c], K): A the displayed u8 crop the same call writes for a three-component frame made of the
@@ -204,7 +207,8 @@ typedef struct zj_frame_desc {
  * frame of the component's own size: ceil(cw/8) x ceil(ch/8) blocks, cw = ceil(W h / h_max), ch = ceil(H v / v_max)
  * (zj_decoder_plane, zj_decoder_component_sampling).  The zj_frame_desc filled for such a file does NOT describe a frame
  * any frame-level call accepts.
- * Such a file is finished by the RESIZED-CROP family only, by a decoder whose out_colorspace is ZJ_CS_RGB; every other finish
+ * Such a file is finished by the RESIZED-CROP family and the crop-tensor file calls (E below through zj_to_tensor_device,
+ * DESIGN.md 3.15) only, by a decoder whose out_colorspace is ZJ_CS_RGB; every other finish
  * call, zj_decoder_decode_buffer and the pool return ZJ_ERR_UNSUPPORTED.
  * DEFINITION (bit-exact): the image is zj_resize_filtered_device applied to the displayed form of the 3-channel u8 image E over
  * the stored window (x, y, w, h): E[r][c] = colour(S_0[(y+r) / ry_0][(x+c) / rx_0], S_1[...], S_2[...]), integer divisions
@@ -367,7 +371,8 @@ ZJ_API int zj_decode_crops_resized_device(zj_ctx *ctx, const zj_frame_desc *d, s
  * launches.  Asynchronous on `stream`; nothing is launched after an error.
  * Frames of several geometries: zj_decode_crops_tensor_mixed_device below.  A decoder's file, several decoders' files:
  * zj_decoder_finish_pixels_crop_tensor_device, zj_decoder_finish_pixels_crop_tensor_batch_device.  d->flags takes what
- * zj_decode_crops_device takes: ZJ_FLAG_GRAY_TO_RGB, an orientation or a prescale are the resized-crop calls'.  The launch's
+ * zj_decode_crops_device takes: a one-component frame shown as RGB or a turned one is made of the u8 crop and
+ * zj_to_tensor_device below (the decoder's file calls do that); a prescale is the resized-crop calls'.  The launch's
  * arguments pass through a small table of the context (a few KB per 32 frames), whose reuse is ordered on the caller's stream.
  * zj_crop_tensor_out_len: C * w * h * the element's bytes; 0: not a valid window / dtype for d, or d has no tensor. */
 ZJ_API size_t zj_crop_tensor_out_len(const zj_frame_desc *d, unsigned w, unsigned h, int dtype);
@@ -384,6 +389,21 @@ ZJ_API int zj_decode_crops_tensor_mixed_device(zj_ctx *ctx, const zj_frame_desc 
                                                const int16_t *const *d_cr, const unsigned *origins, unsigned crop_w,
                                                unsigned crop_h, int dtype, int out_layout, const float *scale,
                                                const float *bias, const uint8_t *flip, void *d_out, void *stream);
+/* u8 images in device memory into one normalised tensor, NOT resized: the last stage of the crop-tensor file
+ * calls for the files whose u8 image is made by stages of its own (gray shown as RGB, CMYK, another sampling, a turned
+ * file), and a call of its own.  n images of ONE size w x h (1..65535 each; no 8192 limit), interleaved, in_channels 1 or
+ * 3; image f starts at d_in[f], in_pitch[f] bytes between its rows (NULL or 0: tight; below w * in_channels: ZJ_ERR_ARG).
+ * channels: of the tensor, 1 or 3; in_channels 1 with channels 3 replicates the byte into the three channels, each with its
+ * own scale[c], bias[c]; in_channels 3 with channels 1 is ZJ_ERR_ARG.  With p the byte of image f, row r, column i, channel
+ * c, the element (c, r, flip[f] ? w - 1 - i : i) of image f is the conversion of v = p << 16 defined at zj_resize_device: for
+ * w, h <= 8192 and in_channels == channels the output is byte for byte zj_resize_device's with out_w = w, out_h = h and
+ * ZJ_LAYOUT_HWC input.  Image f lies at d_out + f * channels * w * h * the element's bytes; d_out aligned to the element.
+ * dtype, out_layout, scale, bias, flip and their checks as zj_resize_device; n == 0 or a NULL pointer is ZJ_ERR_ARG.  ONE
+ * kernel, up to 128 images per launch; no byte outside an image's own h rows of w * in_channels bytes is read.
+ * Asynchronous on `stream` (NULL: the context's); nothing is launched after an error. */
+ZJ_API int zj_to_tensor_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, unsigned w, unsigned h,
+                               const unsigned *in_pitch, int in_channels, int channels, int dtype, int out_layout,
+                               const float *scale, const float *bias, const uint8_t *flip, void *d_out, void *stream);
 /* Resize filters of the *_filtered_device entry points:
  *   ZJ_RESIZE_BILINEAR     the bilinear definition above: the entry points without a filter, byte for byte
  *   ZJ_RESIZE_BILINEAR_AA  antialiased: the triangle filter of Pillow's bilinear / F.interpolate(antialias=True), in exact
@@ -658,26 +678,46 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_device(zj_decoder *d, zj_ctx *c
 /* the decoder's last prepared file: the w x h window at (x, y) converted into one image of a normalised tensor, NOT resized
  * (zj_decode_crops_tensor_device's contract; flip: non-zero mirrors the columns), left in HBM; the file path, its uploads
  * and the stream ordering are zj_decoder_finish_pixels_crop_device's.  It takes the files that call takes, with an
- * out_colorspace of RGB / YCBCR / GRAYSCALE, out_layout ZJ_LAYOUT_HWC and no out_pitch.  ZJ_ERR_UNSUPPORTED, with a
- * zj_decoder_error text that says so: a one-component file of a decoder that asks for a colour output (ZJ_FLAG_GRAY_TO_RGB;
- * with out_colorspace GRAYSCALE it has its one-channel tensor), four-component
- * files (ZJ_FLAG_CMYK_TO_RGB) and files of another sampling or stored RGB (ZJ_FLAG_ANY_SAMPLING) -- those, an orientation
- * and a prescale are the resized-crop calls'.  *out_len = zj_crop_tensor_out_len(); out_cap below it is ZJ_ERR_ARG. */
+ * out_colorspace of RGB / YCBCR / GRAYSCALE, out_layout ZJ_LAYOUT_HWC and no out_pitch.  With the decoder's flags set it
+ * also takes a one-component file shown as RGB (ZJ_FLAG_GRAY_TO_RGB, out_colorspace RGB: the GRAYSCALE u8
+ * crop, every channel that byte's conversion), a four-component file (ZJ_FLAG_CMYK_TO_RGB) and a file of another sampling or
+ * stored RGB (ZJ_FLAG_ANY_SAMPLING): the u8 image the resized-crop call makes of the window in the context's buffer, then
+ * zj_to_tensor_device -- byte for byte that call at out_w = w, out_h = h, bilinear.  ZJ_ERR_UNSUPPORTED, with a
+ * zj_decoder_error text that says so: a one-component file of a decoder that asks for a colour output without
+ * ZJ_FLAG_GRAY_TO_RGB, or for YCbCr with it (with out_colorspace GRAYSCALE it has its one-channel tensor).  A prescale is
+ * the resized-crop calls'.  *out_len = C * w * h * the element's bytes; out_cap below it is ZJ_ERR_ARG. */
 ZJ_API int zj_decoder_finish_pixels_crop_tensor_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y, unsigned w,
                                                        unsigned h, int dtype, int out_layout, const float *scale,
                                                        const float *bias, int flip, void *d_out, size_t out_cap,
                                                        size_t *out_len);
+/* ... with x, y, w, h in DISPLAYED pixels of the file's own orientation (zj_decoder_orientation): the stored window is
+ * zj_orient_window's (orientations 5..8: h x w), the tensor always w x h, flip mirrors the displayed image's columns.  A file
+ * with orientation 1, or with no or an invalid tag, takes the call above as it is.  A turned file: the u8 crop of the stored
+ * window, the orient stage (CMYK and other samplings: in finish order of the resized oriented call), zj_to_tensor_device --
+ * byte for byte zj_decoder_finish_pixels_resized_crop_oriented_device at out_w = w, out_h = h, bilinear, no prescale. */
+ZJ_API int zj_decoder_finish_pixels_crop_tensor_oriented_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y, unsigned w,
+                                                                unsigned h, int dtype, int out_layout, const float *scale,
+                                                                const float *bias, int flip, void *d_out, size_t out_cap,
+                                                                size_t *out_len);
 /* n decoders' last prepared files, of any sizes, into ONE crop tensor: file k's window is w x h at origins[2k],
  * origins[2k + 1], its image at d_out + k * zj_crop_tensor_out_len's bytes, image k what the single-file call above writes
  * for file k.  The decoders must agree in out_colorspace and out_layout (ZJ_ERR_ARG).  Consecutive files the CPU walker
- * decoded go through one mixed-geometry launch group; files prepared for device entropy, and every file the single-file
- * call refuses (a one-component file among colour ones, four components, another sampling, a damaged file, a window that
- * leaves the image), go through that call, which sets the decoder's error text.  rcs[k]: file k's status; a failed file
- * leaves its image untouched and stops no other.  out_cap below n images is ZJ_ERR_ARG.  Synchronous. */
+ * decoded go through one mixed-geometry launch group; files prepared for device entropy, the files that call finishes
+ * through zj_to_tensor_device (a one-component file shown as RGB, four components, another sampling) and every file it
+ * refuses (a one-component file among colour ones without ZJ_FLAG_GRAY_TO_RGB, a damaged file, a window that leaves the
+ * image) go through that call, which sets the decoder's error text.  rcs[k]: file k's status; a failed file leaves its
+ * image untouched and stops no other.  out_cap below n images is ZJ_ERR_ARG.  Synchronous. */
 ZJ_API int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx,
                                                              const unsigned *origins, unsigned w, unsigned h, int dtype,
                                                              int out_layout, const float *scale, const float *bias,
                                                              const uint8_t *flip, void *d_out, size_t out_cap, int *rcs);
+/* ... with the origins in DISPLAYED pixels of each file's own orientation: image k and rcs[k] are
+ * zj_decoder_finish_pixels_crop_tensor_oriented_device's for file k; the turned files go through that call */
+ZJ_API int zj_decoder_finish_pixels_crop_tensor_batch_oriented_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx,
+                                                                      const unsigned *origins, unsigned w, unsigned h,
+                                                                      int dtype, int out_layout, const float *scale,
+                                                                      const float *bias, const uint8_t *flip, void *d_out,
+                                                                      size_t out_cap, int *rcs);
 /* ... with a resize filter (ZJ_RESIZE_*; any other is ZJ_ERR_ARG) */
 ZJ_API int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y,
                                                                  unsigned w, unsigned h, unsigned out_w, unsigned out_h,

@@ -24,6 +24,7 @@
 #include "zj_resize_launch.h"
 #include "zj_rzgroup.h"
 #include "zj_scaled_launch.h"
+#include "zj_to_tensor_launch.h"
 
 using namespace zj;
 static_assert(SCATTER_MAX == ZJ_SCATTER_MAX, "include/zjhip.h and zj_device.h disagree");
@@ -1993,6 +1994,64 @@ int zjint_scratch_idle(zj_ctx* c, size_t bytes, uint8_t** p)
 {
     const int rc = zjint_resize_scratch(c, bytes, p);
     if (rc) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+/* ---- u8 images to a normalised tensor, not resized --------------------------------- */
+int zj_to_tensor_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, unsigned w, unsigned h, const unsigned* in_pitch,
+                        int in_channels, int channels, int dtype, int out_layout, const float* scale, const float* bias,
+                        const uint8_t* flip, void* d_out, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !d_out) return ZJ_ERR_ARG;
+    if (!((in_channels == 1 && (channels == 1 || channels == 3)) || (in_channels == 3 && channels == 3))) return ZJ_ERR_ARG;
+    if (w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+    const int E = resize_elem_bytes(dtype);
+    if (!E || (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC)) return ZJ_ERR_ARG;
+    if ((uintptr_t)d_out % (uintptr_t)E) return ZJ_ERR_ARG; // (the kernel's blocks are counted from element boundaries)
+    ToTensorParams p{};
+    for (int k = 0; k < 3; k++) {
+        const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
+        if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
+        p.scale[k] = sc * (1.f / 65536.f); // (resize_out_args: exact)
+        p.bias[k] = bi;
+    }
+    const unsigned row = w * (unsigned)in_channels;
+    std::vector<unsigned> pitch(n);
+    for (size_t f = 0; f < n; f++) {
+        if (!d_in[f]) return ZJ_ERR_ARG;
+        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : row;
+        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    p.w = (int)w; p.h = (int)h; p.cin = in_channels; p.cout = channels; p.dtype = dtype; p.nhwc = out_layout == ZJ_TENSOR_NHWC;
+    const size_t img_bytes = (size_t)channels * w * h * (size_t)E;
+    for (size_t f0 = 0; f0 < n; f0 += TT_BATCH) {
+        const int m = (int)(n - f0 < (size_t)TT_BATCH ? n - f0 : (size_t)TT_BATCH);
+        p.nimg = m;
+        p.out = (uint64_t)(uintptr_t)((uint8_t*)d_out + f0 * img_bytes);
+        for (int k = 0; k < TT_BATCH / 32; k++) p.flip[k] = 0;
+        for (int i = 0; i < TT_BATCH; i++) {
+            p.in[i] = i < m ? (uint64_t)(uintptr_t)d_in[f0 + i] : 0;
+            p.pitch[i] = i < m ? pitch[f0 + i] : 0;
+            if (i < m && flip && flip[f0 + i]) p.flip[i >> 5] |= 1u << (i & 31);
+        }
+        ZJ_HIP(c, launch_to_tensor(p, st));
+    }
+    return ZJ_OK;
+}
+
+// Library-internal (zj_jpeg.cpp: the crop-tensor file calls of the files that pass through u8 stages): one tight image of the
+// context's crop buffer converted on the context stream into d_out; the buffer counts as read by it; synchronised
+int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int in_channels, int channels, int dtype,
+                        int out_layout, const float* scale, const float* bias, int flip, void* d_out)
+{
+    const uint8_t fl = flip ? 1 : 0;
+    int rc = zj_to_tensor_device(c, 1, &in, w, h, nullptr, in_channels, channels, dtype, out_layout, scale, bias, &fl, d_out, nullptr);
+    if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));
     return ZJ_OK;
 }

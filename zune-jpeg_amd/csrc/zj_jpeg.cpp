@@ -2945,6 +2945,25 @@ __attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, 
                                              int planes_on_device, int scale_log2, unsigned x, unsigned yy, unsigned w, unsigned h,
                                              uint8_t* d_out, unsigned out_pitch);
 
+// ... and one u8 image converted into a tensor image at its own size
+__attribute__((weak)) int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int in_channels, int channels,
+                                              int dtype, int out_layout, const float* scale, const float* bias, int flip, void* d_out);
+
+// The last stage of a single-file call that passes its u8 image through the context's buffer: the resize to out_w x out_h
+// (the resized-crop calls), or the conversion at the image's own size (to_tensor: the crop-tensor calls, DESIGN.md 3.15;
+// out_w x out_h is then the displayed window itself and filter is not used).  Everything in front of it -- the buffer's
+// layout, the component descriptors, the ratios and phases, the turn -- is the one copy in finish_resized* below.
+struct LastStage {
+    bool to_tensor;
+    unsigned out_w, out_h;
+    int dtype, out_layout;
+    const float *scale, *bias;
+    int flip, filter;
+    void* d_out;
+};
+static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, const LastStage& ls,
+                          size_t out_cap, size_t* out_len, int o = 1);
+
 static const char* const kFourOnlyResized = "four-component files are finished by the resized-crop calls only (ZJ_FLAG_CMYK_TO_RGB)";
 static const char* const kOddOnlyResized = "files of this sampling or stored RGB are finished by the resized-crop calls only (ZJ_FLAG_ANY_SAMPLING)";
 // ... and three component planes box-replicated and converted into one image
@@ -3126,22 +3145,29 @@ __attribute__((weak)) int zjint_crop_tensor_frame(zj_ctx* c, const zj_frame_desc
 // The window x, y, w, h of the decoder's last file converted into one image of a normalised tensor, not resized:
 // zj_decode_crops_tensor_device's contract over the crop file path (finish_window: with a scan prepared for the device the
 // planes in HBM, otherwise the CPU walker's planes uploaded by the strips the window needs).
-int zj_decoder_finish_pixels_crop_tensor_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
-                                                int dtype, int out_layout, const float* scale, const float* bias, int flip,
-                                                void* d_out, size_t out_cap, size_t* out_len)
+// o: 1, or the orientation the window is given in.  The files whose u8 image is made by stages of
+// their own -- a one-component file shown as RGB (ZJ_FLAG_GRAY_TO_RGB), four components (ZJ_FLAG_CMYK_TO_RGB), another
+// sampling or stored RGB (ZJ_FLAG_ANY_SAMPLING), a turned file -- take finish_resized's composition with the conversion at
+// the image's own size as its last stage; every other file the fused crop-tensor kernel, as ever.
+static int finish_crop_tensor(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h, int dtype, int out_layout,
+                              const float* scale, const float* bias, int flip, void* d_out, size_t out_cap, size_t* out_len, int o)
 {
     using namespace zj;
-    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
     if (!zjint_crop_tensor_frame || !zjint_scan_to_planes) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
-    if (d->ncomp == 4) return fail(d, ZJ_ERR_UNSUPPORTED, kFourOnlyResized);
-    if (d->odd) return fail(d, ZJ_ERR_UNSUPPORTED, kOddOnlyResized);
-    // (a one-component file is always decoded as GRAYSCALE, fill_info: for a decoder that asks for three channels that is not
-    // the tensor the caller sized)
-    if (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE)
-        return fail(d, ZJ_ERR_UNSUPPORTED, "a one-component file has a GRAYSCALE crop tensor only (ZJ_FLAG_GRAY_TO_RGB is the resized-crop calls')");
     zj_frame_desc fd;
     fill_info(d, nullptr, &fd);
+    const bool gray_rgb = d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE && (d->flags & ZJ_FLAG_GRAY_TO_RGB);
+    // (a one-component file is always decoded as GRAYSCALE, fill_info: for a decoder that asks for three channels without
+    // the flag that is not the tensor the caller sized)
+    if (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE && !gray_rgb)
+        return fail(d, ZJ_ERR_UNSUPPORTED, "a one-component file has a GRAYSCALE crop tensor only (a decoder with ZJ_FLAG_GRAY_TO_RGB shows it as RGB)");
+    if (d->ncomp == 4 || d->odd || gray_rgb || o != 1) {
+        if (fd.out_layout != ZJ_LAYOUT_HWC || fd.out_pitch != 0)
+            return fail(d, ZJ_ERR_UNSUPPORTED, "crop tensors have 1 or 3 channels, from a decoder with out_layout HWC and no out_pitch");
+        return finish_resized(d, ctx, 0, x, y, w, h, LastStage{true, w, h, dtype, out_layout, scale, bias, flip, ZJ_RESIZE_BILINEAR, d_out},
+                              out_cap, out_len, o);
+    }
     const int ch = resize_channels(&fd);
     if (!ch || fd.out_layout != ZJ_LAYOUT_HWC || fd.out_pitch != 0)
         return fail(d, ZJ_ERR_UNSUPPORTED, "crop tensors have 1 or 3 channels, from a decoder with out_layout HWC and no out_pitch");
@@ -3169,6 +3195,25 @@ int zj_decoder_finish_pixels_crop_tensor_device(zj_decoder* d, zj_ctx* ctx, unsi
     return window(d->comps[0].coef, d->ncomp == 3 ? d->comps[1].coef : nullptr, d->ncomp == 3 ? d->comps[2].coef : nullptr, 0);
 }
 
+int zj_decoder_finish_pixels_crop_tensor_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                                int dtype, int out_layout, const float* scale, const float* bias, int flip,
+                                                void* d_out, size_t out_cap, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    return finish_crop_tensor(d, ctx, x, y, w, h, dtype, out_layout, scale, bias, flip, d_out, out_cap, out_len, 1);
+}
+
+// ... with the window in DISPLAYED pixels of the file's own orientation; a file with orientation 1 takes the call above as
+// it is
+int zj_decoder_finish_pixels_crop_tensor_oriented_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
+                                                         int dtype, int out_layout, const float* scale, const float* bias, int flip,
+                                                         void* d_out, size_t out_cap, size_t* out_len)
+{
+    if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
+    return finish_crop_tensor(d, ctx, x, y, w, h, dtype, out_layout, scale, bias, flip, d_out, out_cap, out_len,
+                              d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
+}
+
 // ... and the crop tensors of several files' planes in host memory, each of its own geometry
 __attribute__((weak)) int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
                                                         const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins,
@@ -3177,11 +3222,13 @@ __attribute__((weak)) int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_fram
 
 // Several prepared files of any sizes into one crop tensor, every window w x h (after 3.10's batch call).  The
 // files the CPU walker decoded go through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan
-// left for the device, and every file the single-file call refuses, is finished (or refused, with its text) by that call.
+// left for the device, a file whose u8 image is made by stages of its own (gray shown as RGB, four components, another
+// sampling) and every file the single-file call refuses is finished (or refused, with its text) by that call.
 // rcs[k]: file k's status; a failed file leaves its image untouched and stops no other.
-int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* origins,
-                                                      unsigned w, unsigned h, int dtype, int out_layout, const float* scale,
-                                                      const float* bias, const uint8_t* flip, void* d_out, size_t out_cap, int* rcs)
+// oriented: the origins are in DISPLAYED pixels of each file's own orientation; a turned file is the single-file call's too.
+static int crop_tensor_batch(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* origins, unsigned w, unsigned h, int dtype,
+                             int out_layout, const float* scale, const float* bias, const uint8_t* flip, void* d_out, size_t out_cap,
+                             int* rcs, bool oriented)
 {
     using namespace zj;
     if (!ds || !n || !ctx || !origins || !d_out || !rcs) return ZJ_ERR_ARG;
@@ -3199,8 +3246,9 @@ int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, siz
     const size_t img = (size_t)resize_channels(&fd0) * w * h * (size_t)resize_elem_bytes(dtype);
     if (img && out_cap / img < n) return ZJ_ERR_ARG;
     const auto single = [&](size_t k) {
-        return zj_decoder_finish_pixels_crop_tensor_device(ds[k], ctx, origins[2 * k], origins[2 * k + 1], w, h, dtype, out_layout, scale,
-                                                           bias, flip ? flip[k] : 0, (uint8_t*)d_out + k * img, img, nullptr);
+        return (oriented ? zj_decoder_finish_pixels_crop_tensor_oriented_device : zj_decoder_finish_pixels_crop_tensor_device)(
+            ds[k], ctx, origins[2 * k], origins[2 * k + 1], w, h, dtype, out_layout, scale, bias, flip ? flip[k] : 0,
+            (uint8_t*)d_out + k * img, img, nullptr);
     };
     std::vector<zj_frame_desc> fds(n);
     std::vector<const int16_t*> py(n), pcb(n), pcr(n);
@@ -3210,7 +3258,10 @@ int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, siz
         if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
         // what the mixed call does not take, or the single-file call refuses with a text of its own: that call
         if (!img || !d->seen_sof || d->err_code || d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd ||
-            (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE)) { rcs[k] = single(k); continue; }
+            (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE) || (oriented && d->orientation >= 2 && d->orientation <= 8)) {
+            rcs[k] = single(k);
+            continue;
+        }
         fill_info(d, nullptr, &fds[k]);
         const WindowLayout g = window_layout(&fds[k], w, h, 0);
         if (fds[k].out_layout != ZJ_LAYOUT_HWC || !window_inside(g, origins[2 * k], origins[2 * k + 1], w, h, fds[k].width, fds[k].height)) {
@@ -3236,6 +3287,21 @@ int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, siz
     return ZJ_OK;
 }
 
+int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* origins,
+                                                      unsigned w, unsigned h, int dtype, int out_layout, const float* scale,
+                                                      const float* bias, const uint8_t* flip, void* d_out, size_t out_cap, int* rcs)
+{
+    return crop_tensor_batch(ds, n, ctx, origins, w, h, dtype, out_layout, scale, bias, flip, d_out, out_cap, rcs, false);
+}
+
+int zj_decoder_finish_pixels_crop_tensor_batch_oriented_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* origins,
+                                                               unsigned w, unsigned h, int dtype, int out_layout,
+                                                               const float* scale, const float* bias, const uint8_t* flip,
+                                                               void* d_out, size_t out_cap, int* rcs)
+{
+    return crop_tensor_batch(ds, n, ctx, origins, w, h, dtype, out_layout, scale, bias, flip, d_out, out_cap, rcs, true);
+}
+
 // The decoder's last prepared file at 1 / 2^scale_log2, cut to the window x, y, w, h of the REDUCED frame (all four 0: the
 // whole reduced frame): zj_decode_crops_scaled_device's contract.  With the CPU walker only the MCU rows the window's blocks
 // lie in are uploaded; with device entropy the planes in HBM are used.
@@ -3254,12 +3320,15 @@ int zj_decoder_finish_pixels_scaled_device(zj_decoder* d, zj_ctx* ctx, int scale
 // finish_resized's checks of its arguments, up to the stored window x, y, w, h (given in displayed pixels when o != 1); fd, ch:
 // the file's descriptor and channel count.  A one-component file of a decoder that asks for RGB with ZJ_FLAG_GRAY_TO_RGB
 // (DESIGN.md 3.11): fd is the one-component RGB descriptor with the flag, as the frame calls take it, and ch is 3.
+// to_tensor: the call ends in the conversion at the image's own size (LastStage below): out_w x out_h is the displayed
+// window, of any size up to 65535
 static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsigned& w, unsigned& h, unsigned out_w, unsigned out_h,
-                          int dtype, int filter, size_t out_cap, size_t* out_len, int o, zj_frame_desc& fd, int& ch)
+                          int dtype, int filter, size_t out_cap, size_t* out_len, int o, zj_frame_desc& fd, int& ch,
+                          bool to_tensor = false)
 {
     using namespace zj;
     if (!resize_filter_valid(filter)) return fail(d, ZJ_ERR_ARG, "unknown resize filter");
-    if (!zjint_resize_scratch || !zjint_resize_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (!zjint_resize_scratch || !(to_tensor ? (bool)zjint_to_tensor_one : (bool)zjint_resize_one)) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
     fill_info(d, nullptr, &fd);
     if (d->ncomp == 4) {
@@ -3287,9 +3356,10 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
     if (!ch) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops have 1 or 3 channels");
     if (gray_to_rgb(&fd) && !zjint_gray_to_rgb_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (k && zero_output(&fd) && !gray_to_rgb(&fd)) return fail(d, ZJ_ERR_UNSUPPORTED, "resized crops of an all-zero output");
-    const size_t need = resized_len(ch, out_w, out_h, dtype);
+    const size_t need = !to_tensor ? resized_len(ch, out_w, out_h, dtype)
+                        : out_w - 1 < 65535 && out_h - 1 < 65535 ? (size_t)ch * out_w * out_h * (size_t)resize_elem_bytes(dtype) : 0;
     if (out_len) *out_len = need;
-    if (!need) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
+    if (!need) return fail(d, ZJ_ERR_ARG, to_tensor ? "not a valid crop window or dtype" : "not a valid output size or dtype");
     if (out_cap < need) return fail(d, ZJ_ERR_ARG, "output buffer too small");
     if (o != 1) {
         if (!zjint_orient_one) return ZJ_ERR_UNSUPPORTED;
@@ -3302,13 +3372,23 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
     return ZJ_OK;
 }
 
+// The last stage (LastStage, above) of a file call.  in: the tight u8 image of w x h, in_ch channels in `layout`; ch: the
+// output's channels (in_ch, or 3 from 1: replicated)
+static int last_stage(zj_decoder* d, zj_ctx* ctx, const LastStage& s, const uint8_t* in, unsigned w, unsigned h, int in_ch, int ch,
+                      int layout)
+{
+    const int rc = s.to_tensor ? zjint_to_tensor_one(ctx, in, w, h, in_ch, ch, s.dtype, s.out_layout, s.scale, s.bias, s.flip, s.d_out)
+                               : zjint_resize_one(ctx, in, w, h, ch, layout, s.out_w, s.out_h, s.dtype, s.out_layout, s.scale, s.bias,
+                                                  s.flip, s.filter, s.d_out);
+    return rc ? fail(d, rc, std::string(s.to_tensor ? "to tensor: " : "resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : (int)ZJ_OK;
+}
+
 // finish_resized for a four-component file, its arguments checked: fa the descriptor of A (resized_checks),
 // x, y, w, h the stored window, win the window the crop stage writes (at scale k: of the reduced frame).  In the context's
 // buffer: the crop of A, the crop of K behind it, turned: their displayed forms behind both; A's displayed image combined in
 // place with K's; the resize reads that.
 static int finish_resized_four(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& fa, int k, unsigned x, unsigned y, unsigned w, unsigned h,
-                               const unsigned win[4], int o, unsigned out_w, unsigned out_h, int dtype, int out_layout,
-                               const float* scale, const float* bias, int flip, int filter, void* d_out)
+                               const unsigned win[4], int o, const LastStage& ls)
 {
     using namespace zj;
     zj_frame_desc fk = fa;
@@ -3340,8 +3420,7 @@ static int finish_resized_four(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& 
     }
     rc = zjint_cmyk_to_rgb_one(ctx, a, kk, dw, dh, layout, d->adobe_transform >= 0);
     if (rc) return fail(d, rc, std::string("CMYK to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
-    rc = zjint_resize_one(ctx, a, dw, dh, 3, layout, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
-    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+    return last_stage(d, ctx, ls, a, dw, dh, 3, 3, layout);
 }
 
 // finish_resized for an odd-sampled or stored-RGB file, its arguments checked: x, y, w, h the stored window.
@@ -3349,8 +3428,7 @@ static int finish_resized_four(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& 
 // frame of the plane's padded size, cut to the samples the window shows --, the image E behind them, turned: its displayed
 // form behind that; the resize reads the last.
 static int finish_resized_odd(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& fd, unsigned x, unsigned y, unsigned w, unsigned h, int o,
-                              unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
-                              int flip, int filter, void* d_out)
+                              const LastStage& ls)
 {
     using namespace zj;
     const int layout = fd.out_layout == ZJ_LAYOUT_CHW ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
@@ -3394,27 +3472,27 @@ static int finish_resized_odd(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& f
         if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
         e = buf + off_e2;
     }
-    rc = zjint_resize_one(ctx, e, dw, dh, 3, layout, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
-    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+    return last_stage(d, ctx, ls, e, dw, dh, 3, 3, layout);
 }
 
-static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, unsigned out_w,
-                          unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, int flip, int filter,
-                          void* d_out, size_t out_cap, size_t* out_len, int o = 1)
+static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, const LastStage& ls,
+                          size_t out_cap, size_t* out_len, int o)
 {
     using namespace zj;
     zj_frame_desc fd;
     int ch = 0;
     if (d->odd) k = 0; // (the reduced decode is isotropic, these ratios are not: such a file is never prescaled)
-    int rc = resized_checks(d, k, x, y, w, h, out_w, out_h, dtype, filter, out_cap, out_len, o, fd, ch);
+    int rc = resized_checks(d, k, x, y, w, h, ls.out_w, ls.out_h, ls.dtype, ls.filter, out_cap, out_len, o, fd, ch, ls.to_tensor);
     if (rc) return rc;
-    if (d->odd) return finish_resized_odd(d, ctx, fd, x, y, w, h, o, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
+    if (d->odd) return finish_resized_odd(d, ctx, fd, x, y, w, h, o, ls);
     const unsigned full[4] = {x, y, w, h};
     unsigned win[4] = {x, y, w, h};
     if (k) prescale_window(full, k, fd.width, fd.height, win);
-    if (d->ncomp == 4) return finish_resized_four(d, ctx, fd, k, x, y, w, h, win, o, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out);
-    // (a gray file shown as RGB: the crop and its displayed form are the 1-channel images of the GRAYSCALE decode)
-    const bool expand = gray_to_rgb(&fd);
+    if (d->ncomp == 4) return finish_resized_four(d, ctx, fd, k, x, y, w, h, win, o, ls);
+    // (a gray file shown as RGB: the crop and its displayed form are the 1-channel images of the GRAYSCALE decode; the
+    // conversion to a tensor replicates the byte itself, so that call plans and runs no expand stage)
+    const bool replicate = gray_to_rgb(&fd) && ls.to_tensor, expand = gray_to_rgb(&fd) && !ls.to_tensor;
+    const int in_ch = replicate ? 1 : ch;
     const zj_frame_desc sd = resized_stage_desc(&fd);
     const WindowLayout g = window_layout(&sd, win[2], win[3], 0); // (the crop's own check of the window follows)
     const bool chw = ch == 3 && fd.out_layout == ZJ_LAYOUT_CHW && fd.out_colorspace == ZJ_CS_RGB;
@@ -3423,7 +3501,7 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     const RzFrame rf{win[2], win[3], o, expand};
     RzPlace at;
     size_t bytes = 0;
-    rz_group_next(&rf, 1, 0, ch, chw, RZ_GROUP_CAP, &at, &bytes);
+    rz_group_next(&rf, 1, 0, in_ch, chw, RZ_GROUP_CAP, &at, &bytes);
     uint8_t* crop = nullptr;
     rc = zjint_resize_scratch(ctx, bytes, &crop);
     if (rc) return fail(d, rc, std::string("resize buffer: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
@@ -3433,16 +3511,14 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     if (rc) return rc;
     const int layout = chw ? ZJ_LAYOUT_CHW : ZJ_LAYOUT_HWC;
     if (at.turned) {
-        rc = zjint_orient_one(ctx, crop, win[2], win[3], expand ? 1 : ch, layout, o, crop + at.gray.off);
+        rc = zjint_orient_one(ctx, crop, win[2], win[3], expand ? 1 : in_ch, layout, o, crop + at.gray.off);
         if (rc) return fail(d, rc, std::string("orient: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     }
     if (expand) {
         rc = zjint_gray_to_rgb_one(ctx, crop + at.gray.off, at.gray.w, at.gray.h, layout, crop + at.in.off);
         if (rc) return fail(d, rc, std::string("gray to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     }
-    rc = zjint_resize_one(ctx, crop + at.in.off, at.in.w, at.in.h, ch, layout, out_w, out_h, dtype, out_layout, scale, bias, flip,
-                          filter, d_out);
-    return rc ? fail(d, rc, std::string("resize: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : ZJ_OK;
+    return last_stage(d, ctx, ls, crop + at.in.off, at.in.w, at.in.h, in_ch, ch, layout);
 }
 
 int zj_decoder_finish_pixels_resized_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x, unsigned y, unsigned w, unsigned h,
@@ -3459,7 +3535,7 @@ int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder* d, zj_ctx*
                                                           void* d_out, size_t out_cap, size_t* out_len)
 {
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
-    return finish_resized(d, ctx, 0, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len);
+    return finish_resized(d, ctx, 0, x, y, w, h, LastStage{false, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out}, out_cap, out_len);
 }
 
 // zj_decoder_finish_pixels_resized_crop_filtered_device with a reduced-size decode under the resize
@@ -3472,7 +3548,7 @@ int zj_decoder_finish_pixels_resized_crop_prescaled_device(zj_decoder* d, zj_ctx
     if (!d || !ctx || !d_out) return ZJ_ERR_ARG;
     if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
     const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
-    return finish_resized(d, ctx, k, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len);
+    return finish_resized(d, ctx, k, x, y, w, h, LastStage{false, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out}, out_cap, out_len);
 }
 
 // The prescaled call with the window in DISPLAYED pixels of the file's own orientation; a file with
@@ -3486,7 +3562,7 @@ int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder* d, zj_ctx*
     if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
     // (the scale from the displayed window's sides: the ones the resize sees)
     const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
-    return finish_resized(d, ctx, k, x, y, w, h, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out, out_cap, out_len,
+    return finish_resized(d, ctx, k, x, y, w, h, LastStage{false, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out}, out_cap, out_len,
                           d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
 }
 

@@ -63,7 +63,7 @@ FLAG_CLAMP_DC = 2     # extension: DC-only shortcut value clamped to 0..255 (Q1 
 FLAG_EDGE_REPLICATE = 4  # extension: horizontal chroma filter per row with replicated edges (Q4 corrected)
 FLAG_CORRECTED = 7
 FLAG_FULL_AC_VALUES = 8  # zj_options.flags only: the front-end yields AC values as coded (the reference cuts some to six bits)
-FLAG_GRAY_TO_RGB = 16    # resized crops only: a one-component frame / file asked for RGB gives R = G = B
+FLAG_GRAY_TO_RGB = 16    # resized crops and the crop-tensor file calls only: a one-component frame / file asked for RGB gives R = G = B
 FLAG_CMYK_TO_RGB = 32    # decoder options only: four-component (Adobe CMYK / YCCK) files are accepted and the resized-crop
                          # calls show them as RGB
 FLAG_ANY_SAMPLING = 64   # decoder options only: three-component files of any sampling with factors 1, 2, 4 (4:1:1, 4:1:0,
@@ -198,6 +198,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_planes_to_rgb_device", "zj_decoder_stored_rgb", "zj_decoder_component_sampling",
     "zj_crop_tensor_out_len", "zj_decode_crops_tensor_device", "zj_decoder_finish_pixels_crop_tensor_device",
     "zj_decode_crops_tensor_mixed_device", "zj_decoder_finish_pixels_crop_tensor_batch_device",
+    "zj_to_tensor_device", "zj_decoder_finish_pixels_crop_tensor_oriented_device",
+    "zj_decoder_finish_pixels_crop_tensor_batch_oriented_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -348,6 +350,9 @@ def lib():
                                                       vp, vp]
     L.zj_decoder_finish_pixels_crop_tensor_batch_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp,
                                                                     vp, vp, sz, vp]
+    L.zj_decoder_finish_pixels_crop_tensor_oriented_device.argtypes = L.zj_decoder_finish_pixels_crop_tensor_device.argtypes
+    L.zj_decoder_finish_pixels_crop_tensor_batch_oriented_device.argtypes = L.zj_decoder_finish_pixels_crop_tensor_batch_device.argtypes
+    L.zj_to_tensor_device.argtypes = [vp, sz, vp, C.c_uint, C.c_uint, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.zj_resize_filtered_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp,
                                             vp, C.c_int, vp, vp]
     L.zj_decode_crops_resized_filtered_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
@@ -660,6 +665,19 @@ class Context:
             _check(lib().zj_resize_filtered_device(*args, filt, d_out, stream), "zj_resize_filtered_device", self._h)
         else:
             _check(lib().zj_resize_device(*args, d_out, stream), "zj_resize_device", self._h)
+
+    def to_tensor_device(self, d_in, w, h, in_channels, channels, dtype, out_layout, d_out, scale=None, bias=None, flips=None,
+                         pitches=None, stream=None):
+        """u8 images of ONE size into a normalised tensor, not resized (zj_to_tensor_device): d_in = device
+        pointers of interleaved u8 images of w x h with in_channels (1 or 3), pitches = bytes between rows (None: tight);
+        channels = the tensor's (1 or 3; 3 from 1 replicates); the dense output at d_out.  Asynchronous on `stream`."""
+        n = len(d_in)
+        if pitches is not None and len(pitches) != n:
+            raise ValueError("one pitch per image")
+        pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
+        _check(lib().zj_to_tensor_device(self._h, n, (C.c_void_p * n)(*d_in), w, h, pit, in_channels, channels, dtype, out_layout,
+                                         _floats(scale), _floats(bias), _flips(flips, n), d_out, stream), "zj_to_tensor_device",
+               self._h)
 
     def orient_device(self, d_in, sizes, channels, in_layout, orientations, d_out, in_pitches=None, out_pitches=None,
                       stream=None):
@@ -1070,16 +1088,19 @@ class Decoder:
             self._raise(rc)
         return n.value
 
-    def finish_pixels_crop_tensor_device(self, x, y, w, h, dtype, out_layout, d_out, cap, scale=None, bias=None, flip=False):
+    def finish_pixels_crop_tensor_device(self, x, y, w, h, dtype, out_layout, d_out, cap, scale=None, bias=None, flip=False,
+                                         apply_orientation=False):
         """Stage 2 cut to the w x h window at (x, y) and converted into one image of a normalised tensor, not resized (the
         contract of zj_decode_crops_tensor_device), left in HBM at device pointer d_out; returns the image's length in
-        bytes."""
+        bytes.  apply_orientation: the window is in DISPLAYED pixels of the file's EXIF orientation
+        (zj_decoder_finish_pixels_crop_tensor_oriented_device)."""
         if self._ctx is None:
             self._ctx = Context()
         n = C.c_size_t(0)
-        rc = lib().zj_decoder_finish_pixels_crop_tensor_device(self._d, self._ctx.handle, x, y, w, h, dtype, out_layout,
-                                                               _floats(scale), _floats(bias), 1 if flip else 0, d_out, cap,
-                                                               C.byref(n))
+        fn = (lib().zj_decoder_finish_pixels_crop_tensor_oriented_device if apply_orientation
+              else lib().zj_decoder_finish_pixels_crop_tensor_device)
+        rc = fn(self._d, self._ctx.handle, x, y, w, h, dtype, out_layout, _floats(scale), _floats(bias), 1 if flip else 0, d_out, cap,
+                C.byref(n))
         if rc:
             self._raise(rc)
         return n.value
@@ -1253,21 +1274,21 @@ def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype
 
 
 def finish_pixels_crop_tensor_batch(decoders, ctx, origins, w, h, dtype, out_layout, d_out, cap, scale=None, bias=None,
-                                    flips=None):
+                                    flips=None, apply_orientation=False):
     """zj_decoder_finish_pixels_crop_tensor_batch_device over Decoder objects that went through prepare() or
     decode_coefficients(), each with a file of its own size: origins = one (x, y) per decoder, every window w x h, image k
     left at device pointer d_out + k * crop_tensor_out_len.  Returns the list of statuses: image k is
-    Decoder.finish_pixels_crop_tensor_device's for decoder k alone, a failed file's slot is untouched."""
+    Decoder.finish_pixels_crop_tensor_device's for decoder k alone, a failed file's slot is untouched.  apply_orientation:
+    the origins are in DISPLAYED pixels of each file's own orientation (the _batch_oriented_ entry point)."""
     n = len(decoders)
     if len(origins) != n:
         raise ValueError("one origin per decoder")
     dptr = (C.c_void_p * n)(*[d._d for d in decoders])
     org = (C.c_uint * (2 * n))(*[int(v) for xy in origins for v in xy])
     rcs = (C.c_int * n)()
-    _check(lib().zj_decoder_finish_pixels_crop_tensor_batch_device(dptr, n, ctx.handle, org, w, h, dtype, out_layout,
-                                                                   _floats(scale), _floats(bias), _flips(flips, n), d_out, cap,
-                                                                   rcs),
-           "zj_decoder_finish_pixels_crop_tensor_batch_device", ctx.handle)
+    name = "zj_decoder_finish_pixels_crop_tensor_batch_oriented_device" if apply_orientation else "zj_decoder_finish_pixels_crop_tensor_batch_device"
+    _check(getattr(lib(), name)(dptr, n, ctx.handle, org, w, h, dtype, out_layout, _floats(scale), _floats(bias), _flips(flips, n),
+                                d_out, cap, rcs), name, ctx.handle)
     return list(rcs)
 
 

@@ -316,18 +316,21 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
 
 
 def decode_files_cropped_to_tensor(ctx, blobs, origins, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
-                                   options=None, workers=1, stream=None, decoders=None):
+                                   options=None, workers=1, stream=None, decoders=None, apply_orientation=False):
     """JPEG files -> ONE dense tensor of their size = (w, h) windows, converted and normalised but NOT resized
     (zj_decoder_finish_pixels_crop_tensor_batch_device): blobs = a list of bytes-like JPEG files, origins = one
     (x, y) per file, or None: the whole image, and then every file must measure exactly `size` (ValueError naming the
     first that does not).  Returns [N, C, h, w] ("NCHW") or [N, h, w, C] ("NHWC") of `dtype` (default bfloat16); image k
     is Decoder.finish_pixels_crop_tensor_device's for file k.  dtype, mean / std, flips, options, workers, decoders and
     stream as decode_files_resized_to_tensor.  The batch call runs on the context's stream and has finished when it
-    returns; a file that fails raises DecodeError naming its index (its image is untouched, the others are decoded).  Files that need FLAG_GRAY_TO_RGB,
-    FLAG_CMYK_TO_RGB or FLAG_ANY_SAMPLING, an orientation or a prescale are decode_files_resized_to_tensor's."""
+    returns; a file that fails raises DecodeError naming its index (its image is untouched, the others are decoded).
+    apply_orientation: origins and size are in DISPLAYED pixels of each file's own EXIF orientation; with
+    origins=None the displayed size must equal `size`.  With FLAG_GRAY_TO_RGB, FLAG_CMYK_TO_RGB or FLAG_ANY_SAMPLING in the
+    options' flags, gray files shown as RGB, CMYK / YCCK files and files of another sampling or stored RGB are decoded here
+    as well, through their u8 image and to_normalized_tensor's stage; a prescale is decode_files_resized_to_tensor's."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
-    from .host import DecodeError, Decoder, finish_pixels_crop_tensor_batch
+    from .host import DecodeError, Decoder, finish_pixels_crop_tensor_batch, oriented_size
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
     n = len(blobs)
@@ -357,8 +360,11 @@ def decode_files_cropped_to_tensor(ctx, blobs, origins, size, dtype=None, layout
     if origins is None:
         for k in range(n):
             info = prepared[k][1]
-            if (int(info.width), int(info.height)) != (w, h):
-                raise ValueError(f"file {k} is {info.width}x{info.height}, not {w}x{h}: give origins")
+            shown = (int(info.width), int(info.height))
+            if apply_orientation:
+                shown = tuple(oriented_size(decs[k].orientation, *shown))
+            if shown != (w, h):
+                raise ValueError(f"file {k} is {shown[0]}x{shown[1]}, not {w}x{h}: give origins")
         origins = [(0, 0)] * n
     channels = ColorSpace(decs[0]._out_cs).num_components()
     if channels not in (1, 3):
@@ -370,7 +376,8 @@ def decode_files_cropped_to_tensor(ctx, blobs, origins, size, dtype=None, layout
     out = _resized_out(n, channels, size, dtype, layout, dev, s)
     s.synchronize()  # (the allocator may hand out a block that work queued on `s` still uses: the files run on the context's stream)
     rcs = finish_pixels_crop_tensor_batch(decs, ctx, origins, w, h, code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC,
-                                          out.data_ptr(), out.numel() * out.element_size(), scale, bias, flips)
+                                          out.data_ptr(), out.numel() * out.element_size(), scale, bias, flips,
+                                          apply_orientation=bool(apply_orientation))
     for k, rc in enumerate(rcs):
         if rc:
             raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
@@ -576,4 +583,31 @@ def resize_to_tensor(ctx, images, size, dtype=None, layout="NCHW", in_layout="HW
     ctx.resize_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
                       size[0], size[1], code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias,
                       flips, pitches, s.cuda_stream, antialias, interpolation)
+    return out
+
+
+def to_normalized_tensor(ctx, images, dtype=None, layout="NCHW", mean=None, std=None, flips=None, channels=None, stream=None):
+    """u8 CUDA images of ONE size converted and normalised into one dense tensor, NOT resized (zj_to_tensor_device, DESIGN.md
+    3.15): images = [h, w, 3], [h, w, 1] or [h, w] tensors, all of one size, contiguous or row-strided.  channels: of the
+    output (None: the images'); 3 from one-channel images puts the byte into all three channels, each with its own mean /
+    std.  Returns [N, C, h, w] ("NCHW") or [N, h, w, C] ("NHWC") of `dtype` (default bfloat16).  mean / std, flips and
+    streams as resize_to_tensor.  No size limit but 65535 a side."""
+    import torch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    imgs, sizes, pitches, cin = _u8_images(images, "HWC")
+    if any(sz != sizes[0] for sz in sizes):
+        raise ValueError("every image has the same size")
+    channels = cin if channels is None else int(channels)
+    if channels not in (1, 3) or (cin == 3 and channels == 1):
+        raise ValueError("channels is 1 or 3, and 3 for 3-channel images")
+    n = len(imgs)
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, sizes[0], dtype, layout, dev, s)
+    _on_stream(s, cur, imgs)
+    ctx.to_tensor_device([im.data_ptr() for im in imgs], sizes[0][0], sizes[0][1], cin, channels, code,
+                         TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips, pitches, s.cuda_stream)
     return out
