@@ -39,6 +39,8 @@ pub const ZJ_TENSOR_NHWC: c_int = 1;
 pub const ZJ_RESIZE_BILINEAR: c_int = 0;
 pub const ZJ_RESIZE_BILINEAR_AA: c_int = 1;
 pub const ZJ_RESIZE_BICUBIC_AA: c_int = 4;
+pub const ZJ_WARP_FILL: c_int = 0;
+pub const ZJ_WARP_REPLICATE: c_int = 1;
 
 /// `ColorSpace`, `src/misc.rs:88-106` (same discriminants).
 #[repr(i32)]
@@ -245,6 +247,25 @@ extern "C" {
     pub fn zj_to_tensor_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, w: c_uint, h: c_uint, in_pitch: *const c_uint,
                                in_channels: c_int, channels: c_int, dtype: c_int, out_layout: c_int, scale: *const f32,
                                bias: *const f32, flip: *const u8, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_warped_device(d: *mut zj_decoder, ctx: *mut zj_ctx, matrix: *const f64, apply_orientation: c_int,
+                                                  out_w: c_uint, out_h: c_uint, dtype: c_int, out_layout: c_int,
+                                                  scale: *const f32, bias: *const f32, fill: *const u8, edge: c_int,
+                                                  d_out: *mut c_void, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn zj_decoder_finish_pixels_warped_batch_device(ds: *const *mut zj_decoder, n: usize, ctx: *mut zj_ctx, matrices: *const f64,
+                                                        apply_orientation: c_int, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                        out_layout: c_int, scale: *const f32, bias: *const f32, fill: *const u8,
+                                                        edge: c_int, d_out: *mut c_void, out_cap: usize, rcs: *mut c_int) -> c_int;
+    pub fn zj_warp_fixed(matrix: *const f64, fixed: *mut i64) -> c_int;
+    pub fn zj_warp_source_window(fixed: *const i64, frame_w: c_uint, frame_h: c_uint, out_w: c_uint, out_h: c_uint, edge: c_int,
+                                 window: *mut c_uint, shifted: *mut i64) -> c_int;
+    pub fn zj_warp_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                          channels: c_int, matrices: *const f64, out_w: c_uint, out_h: c_uint, dtype: c_int, out_layout: c_int,
+                          scale: *const f32, bias: *const f32, fill: *const u8, edge: c_int, d_out: *mut c_void,
+                          stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_warped_device(ctx: *mut zj_ctx, d: *const zj_frame_desc, nframes: usize, d_y: *const *const i16,
+                                         d_cb: *const *const i16, d_cr: *const *const i16, matrices: *const f64, out_w: c_uint,
+                                         out_h: c_uint, dtype: c_int, out_layout: c_int, scale: *const f32, bias: *const f32,
+                                         fill: *const u8, edge: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn zj_decoder_finish_pixels_resized_crop_device(d: *mut zj_decoder, ctx: *mut zj_ctx, x: c_uint, y: c_uint, w: c_uint,
                                                         h: c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
                                                         out_layout: c_int, scale: *const f32, bias: *const f32, flip: c_int,

@@ -404,6 +404,49 @@ ZJ_API int zj_decode_crops_tensor_mixed_device(zj_ctx *ctx, const zj_frame_desc 
 ZJ_API int zj_to_tensor_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, unsigned w, unsigned h,
                                const unsigned *in_pitch, int in_channels, int channels, int dtype, int out_layout,
                                const float *scale, const float *bias, const uint8_t *flip, void *d_out, void *stream);
+/* Affine-warped images into one normalised tensor: rotation, shear, scale, translation, the letterbox, any
+ * crop whose window leaves the image.  A matrix m = (a, b, c, d, e, f) of doubles maps an output pixel CENTRE to continuous
+ * source coordinates, pixel i covering [i, i + 1): sx = a (X + 1/2) + b (Y + 1/2) + c, sy = d (X + 1/2) + e (Y + 1/2) + f.
+ * zj_warp_fixed gives its six integers, Q = 24: A = floor(a 2^24 + 1/2), B, D, E likewise, C0 = floor((a / 2 + b / 2 + c -
+ * 1/2) 2^24 + 1/2), F0 likewise from d, e, f (the sums formed in doubles, from left to right); ZJ_ERR_ARG: a non-finite
+ * entry, |a|, |b|, |d|, |e| >= 128 or |c|, |f| >= 2^31.  In 64-bit integers Ux = A X + B Y + C0, ux = Ux >> 16 (a floor: 1/256
+ * pixel), x0 = ux >> 8, fx = ux & 255, and Uy, y0, fy likewise.  The four taps are (y0, x0), (y0, x0 + 1), (y0 + 1, x0),
+ * (y0 + 1, x0 + 1).  edge ZJ_WARP_FILL: a tap with x outside [0, w) or y outside [0, h) reads fill[c], a byte per output
+ * channel (NULL: 0); ZJ_WARP_REPLICATE: the tap's indices are clamped to the image.  The value is zj_resize_device's
+ * v = top (256 - fy) + bot fy over those taps, the element its conversion of v.  There is no flip: a mirror is a matrix.
+ * The identity gives zj_to_tensor_device byte for byte, the integer matrix of an EXIF orientation the displayed image's, a
+ * scale by 2, 4, 1/2 or 1/4 per axis with ZJ_WARP_REPLICATE zj_resize_device's.  Nothing is antialiased.
+ * zj_warp_source_window: the window x, y, w, h of a frame of frame_w x frame_h that an out_w x out_h output under `fixed`
+ * can read -- U is affine, so the box of the taps is spanned by the output's four corner pixels -- and `shifted`, the
+ * integers relative to it (C0 - x 2^24, F0 - y 2^24).  ZJ_WARP_FILL: the box cut to the frame; an empty cut gives w = h = 0
+ * and the output is all fill.  ZJ_WARP_REPLICATE: both ends of the box clamped into the frame.  In both modes warping the
+ * window's crop under `shifted` equals warping the whole frame under `fixed`.  ZJ_ERR_ARG: a NULL pointer, integers no
+ * matrix gives, a size outside 1..65535 (frame) or 1..8192 (output), another edge.  Both functions run without a device. */
+#define ZJ_WARP_FILL 0
+#define ZJ_WARP_REPLICATE 1
+ZJ_API int zj_warp_fixed(const double matrix[6], int64_t fixed[6]);
+ZJ_API int zj_warp_source_window(const int64_t fixed[6], unsigned frame_w, unsigned frame_h, unsigned out_w, unsigned out_h,
+                                 int edge, unsigned window[4], int64_t shifted[6]);
+/* n u8 images in device memory, interleaved, channels 1 or 3, each under its own matrix (matrices: 6 doubles per image): d_in,
+ * in_wh, in_pitch as in zj_resize_device (ZJ_LAYOUT_HWC alone); out_w, out_h, dtype, out_layout, scale, bias and their
+ * checks as there too, d_out aligned to the element; image f lies at d_out + f * channels * out_w * out_h * the element's
+ * bytes (zj_resized_out_len).  ZJ_ERR_ARG as well: a matrix zj_warp_fixed refuses, another edge.  One kernel per channel
+ * count, up to 48 images per launch; a tap outside an image is never loaded and no byte outside an image's own h rows of
+ * w * channels bytes is read.  Asynchronous on `stream` (NULL: the context's); nothing is launched after an error. */
+ZJ_API int zj_warp_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                          int channels, const double *matrices, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                          const float *scale, const float *bias, const uint8_t *fill, int edge, void *d_out, void *stream);
+/* nframes frames of ONE geometry, frame f warped under matrices[6f .. 6f + 5], given in FRAME pixels: the output is by
+ * definition zj_warp_device applied to EXACTLY the bytes zj_decode_crops_device writes for the whole frame (its zeros and
+ * ZJ_FLAG_CORRECTED included).  Only each frame's source window (zj_warp_source_window) is decoded, by the crop stage into
+ * the context's buffer in the launch groups of zj_decode_crops_resized_device and under its ordering; a frame whose output
+ * sees nothing of the frame decodes nothing.  d and its refusals as in zj_decode_crops_resized_device (ZJ_FLAG_GRAY_TO_RGB
+ * included), out_layout ZJ_LAYOUT_HWC; the tail as zj_warp_device.  Asynchronous on `stream`; nothing is launched after an
+ * error. */
+ZJ_API int zj_decode_crops_warped_device(zj_ctx *ctx, const zj_frame_desc *d, size_t nframes, const int16_t *const *d_y,
+                                         const int16_t *const *d_cb, const int16_t *const *d_cr, const double *matrices,
+                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float *scale,
+                                         const float *bias, const uint8_t *fill, int edge, void *d_out, void *stream);
 /* Resize filters of the *_filtered_device entry points:
  *   ZJ_RESIZE_BILINEAR     the bilinear definition above: the entry points without a filter, byte for byte
  *   ZJ_RESIZE_BILINEAR_AA  antialiased: the triangle filter of Pillow's bilinear / F.interpolate(antialias=True), in exact
@@ -718,6 +761,32 @@ ZJ_API int zj_decoder_finish_pixels_crop_tensor_batch_oriented_device(zj_decoder
                                                                       int dtype, int out_layout, const float *scale,
                                                                       const float *bias, const uint8_t *flip, void *d_out,
                                                                       size_t out_cap, int *rcs);
+/* The decoder's last prepared file warped into one image of a normalised tensor: `matrix` as in zj_warp_device,
+ * in pixels of the stored frame, or, with apply_orientation != 0, of the DISPLAYED frame of the file's EXIF orientation -- the
+ * definition is orient first, then warp.  The image is zj_warp_device's of the u8 image the file decodes to (what
+ * zj_decoder_finish_pixels_resized_crop_oriented_device resizes: a one-component file of an RGB decoder with
+ * ZJ_FLAG_GRAY_TO_RGB as R = G = B, a four-component file with ZJ_FLAG_CMYK_TO_RGB, another sampling or stored RGB with
+ * ZJ_FLAG_ANY_SAMPLING), but only the part of the frame the output can see (zj_warp_source_window) is decoded and, under the
+ * CPU walker, uploaded; an output that sees nothing of the frame is all fill and decodes nothing.  The decoder's out_layout
+ * must be ZJ_LAYOUT_HWC (ZJ_ERR_UNSUPPORTED otherwise); the other refusals are that call's and zj_warp_device's.  *out_len:
+ * zj_resized_out_len's bytes.  Synchronous. */
+ZJ_API int zj_decoder_finish_pixels_warped_device(zj_decoder *d, zj_ctx *ctx, const double matrix[6], int apply_orientation,
+                                                  unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                  const float *scale, const float *bias, const uint8_t *fill, int edge,
+                                                  void *d_out, size_t out_cap, size_t *out_len);
+/* n decoders' last prepared files, of any sizes, each under its own matrix (matrices: 6 doubles per file), into ONE warped
+ * tensor: file k's image lies at d_out + k * zj_resized_out_len's bytes and is what the single-file call above writes for
+ * file k.  The decoders must agree in out_colorspace and out_layout (ZJ_ERR_ARG).  Consecutive files the CPU walker decoded
+ * whose output sees some of their frame share the mixed-geometry crop launches of
+ * zj_decoder_finish_pixels_resized_crop_batch_device, each cut to its own source window, and the warp launches over each
+ * group's crops (48 files a launch); files prepared for device entropy, four-component files, files of another sampling or
+ * stored RGB, an output that sees nothing of its frame and every file the single-file call refuses (a damaged file, a matrix
+ * the warp does not take) go through that call, which sets the decoder's error text.  rcs[k]: file k's status; a failed file
+ * leaves its image untouched and stops no other.  out_cap below n images is ZJ_ERR_ARG.  Synchronous. */
+ZJ_API int zj_decoder_finish_pixels_warped_batch_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx, const double *matrices,
+                                                        int apply_orientation, unsigned out_w, unsigned out_h, int dtype,
+                                                        int out_layout, const float *scale, const float *bias,
+                                                        const uint8_t *fill, int edge, void *d_out, size_t out_cap, int *rcs);
 /* ... with a resize filter (ZJ_RESIZE_*; any other is ZJ_ERR_ARG) */
 ZJ_API int zj_decoder_finish_pixels_resized_crop_filtered_device(zj_decoder *d, zj_ctx *ctx, unsigned x, unsigned y,
                                                                  unsigned w, unsigned h, unsigned out_w, unsigned out_h,

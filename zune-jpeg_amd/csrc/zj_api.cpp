@@ -25,6 +25,8 @@
 #include "zj_rzgroup.h"
 #include "zj_scaled_launch.h"
 #include "zj_to_tensor_launch.h"
+#include "zj_warp_fixed.h"
+#include "zj_warp_launch.h"
 
 using namespace zj;
 static_assert(SCATTER_MAX == ZJ_SCATTER_MAX, "include/zjhip.h and zj_device.h disagree");
@@ -838,6 +840,10 @@ struct ResizeOut {
     bool chw;                   // the u8 images are CHW planes (the caller's to set)
 };
 
+// The affine warp's own arguments next to a ResizeOut (whose flip and filter it ignores): the fill bytes,
+// fill[c] << 8 c, and the edge mode
+struct WarpTail { uint32_t fill; int edge; };
+
 ResizeOut resize_out(unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
                      const uint8_t* flip, int filter, void* d_out)
 {
@@ -1022,8 +1028,15 @@ int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t
 // The end of the launch group [g0, g1) of a resized call, its crops written into buf where `place` says (zj_rzgroup.h):
 // the turned frames, gathered: crop -> its displayed form, tight, in the second region; the resize over the images place[f].in
 // names, in order, into images [g0, g1) of the output; the event that orders the buffer's reuse.
+// warp (nullptr: the resize): the group ends in the affine warp instead, frame f under the integers
+// warp_q[6f .. 6f + 5].  Only the warp's calls have frames of an EMPTY window (w == 0: the output sees nothing of the frame,
+// fill mode): such a frame has no crop, passes no stage in front of the warp -- the `p.in.w` below -- and gets a record no
+// lane loads from (warp_launches).  The resized calls refuse an empty window before they come here.
+int warp_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const int64_t* q,
+                  const ResizeOut& o, const WarpTail& t, size_t first, hipStream_t st);
+
 int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g0, size_t g1, uint8_t* buf, const ResizeOut& o,
-                    hipStream_t st)
+                    hipStream_t st, const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr)
 {
     // the images of one stage of the group, gathered
     struct Stage {
@@ -1049,7 +1062,7 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
         wh[2 * (f - g0)] = p.in.w; wh[2 * (f - g0) + 1] = p.in.h;
         pitch[f - g0] = p.in.pitch;
         if (p.turned) (p.expand ? turn_gray : turn).add(buf, p.crop, p.gray, fr[f].o);
-        if (p.expand) expand.add(buf, p.gray, p.in, 1);
+        if (p.expand && p.in.w) expand.add(buf, p.gray, p.in, 1);
     }
     int rc;
     if (!turn.in.empty() && (rc = orient_launches(c, turn.in.size(), turn.in.data(), turn.wh.data(), turn.ip.data(), o.ch, o.chw,
@@ -1062,7 +1075,9 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
     if (!expand.in.empty() && (rc = expand_launches(c, expand.in.size(), expand.in.data(), expand.wh.data(), expand.ip.data(),
                                                     o.chw, expand.out.data(), expand.op.data(), st)))
         return rc;
-    if ((rc = resize_launches(c, ng, in.data(), wh.data(), pitch.data(), o, g0, st))) return rc;
+    if ((rc = warp ? warp_launches(c, ng, in.data(), wh.data(), pitch.data(), warp_q + 6 * g0, o, *warp, g0, st)
+                   : resize_launches(c, ng, in.data(), wh.data(), pitch.data(), o, g0, st)))
+        return rc;
     return resize_scratch_done(c, st);
 }
 } // namespace
@@ -1287,6 +1302,184 @@ int zj_decode_crops_resized_oriented_device(zj_ctx* c, const zj_frame_desc* d, s
                               orientation, stream);
 }
 
+/* ---- affine warp ----------------------------------------------------------------- */
+namespace {
+int warp_tail_args(const uint8_t* fill, int edge, int channels, WarpTail& t)
+{
+    if (edge != ZJ_WARP_FILL && edge != ZJ_WARP_REPLICATE) return ZJ_ERR_ARG;
+    t.edge = edge;
+    t.fill = 0;
+    for (int k = 0; fill && k < channels; k++) t.fill |= (uint32_t)fill[k] << (8 * k);
+    return ZJ_OK;
+}
+
+// the six integers of n matrices of doubles, 6 each
+int warp_matrices(const double* matrices, size_t n, std::vector<int64_t>& q)
+{
+    if (!matrices) return ZJ_ERR_ARG;
+    q.resize(6 * n);
+    for (size_t f = 0; f < n; f++)
+        if (!warp_fixed(matrices + 6 * f, q.data() + 6 * f)) return ZJ_ERR_ARG;
+    return ZJ_OK;
+}
+
+// images [0, n) -> images [first, first + n) of the output, launches of up to WARP_BATCH images; wh[2i], wh[2i + 1]: image
+// i's size, pitch[i] resolved, q: its six integers.  wh[2i] == 0: no image at all -- every tap of the output is outside
+// (fill mode alone): the record is a 1 x 1 image that no lane loads from, under a map that sends every pixel to x0 = -4
+int warp_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const int64_t* q,
+                  const ResizeOut& o, const WarpTail& t, size_t first, hipStream_t st)
+{
+    WarpParams p{};
+    p.out_w = (int)o.out_w; p.out_h = (int)o.out_h; p.dtype = o.dtype; p.nhwc = o.layout == ZJ_TENSOR_NHWC;
+    p.fill = t.fill; p.edge = t.edge;
+    for (int k = 0; k < 3; k++) { p.scale[k] = o.s[k]; p.bias[k] = o.b[k]; }
+    for (size_t f0 = 0; f0 < n; f0 += WARP_BATCH) {
+        const int m = (int)(n - f0 < (size_t)WARP_BATCH ? n - f0 : (size_t)WARP_BATCH);
+        p.nimg = m;
+        p.out = (uint64_t)(uintptr_t)(o.d_out + (first + f0) * o.img_bytes);
+        for (int i = 0; i < WARP_BATCH; i++) {
+            const size_t f = f0 + i;
+            WarpImage& im = p.img[i];
+            im = WarpImage{};
+            if (i >= m) continue;
+            if (wh[2 * f] == 0) {
+                im.in = (uint64_t)(uintptr_t)o.d_out; // (never loaded from)
+                im.wh = 1u | 1u << 16; im.pitch = 1;
+                im.m[2] = im.m[5] = -((int64_t)4 << WARP_Q);
+                continue;
+            }
+            im.in = (uint64_t)(uintptr_t)in[f];
+            im.wh = wh[2 * f] | (wh[2 * f + 1] << 16);
+            im.pitch = pitch[f];
+            for (int k = 0; k < 6; k++) im.m[k] = q[6 * f + k];
+        }
+        ZJ_HIP(c, launch_warp(o.ch, p, st));
+    }
+    return ZJ_OK;
+}
+} // namespace
+
+int zj_warp_fixed(const double matrix[6], int64_t fixed[6])
+{
+    if (!matrix || !fixed) return ZJ_ERR_ARG;
+    int64_t q[6];
+    if (!warp_fixed(matrix, q)) return ZJ_ERR_ARG;
+    for (int k = 0; k < 6; k++) fixed[k] = q[k];
+    return ZJ_OK;
+}
+
+int zj_warp_source_window(const int64_t fixed[6], unsigned frame_w, unsigned frame_h, unsigned out_w, unsigned out_h, int edge,
+                          unsigned window[4], int64_t shifted[6])
+{
+    if (!fixed || !window || !shifted || !warp_ints_valid(fixed)) return ZJ_ERR_ARG;
+    if (frame_w == 0 || frame_h == 0 || frame_w > 65535 || frame_h > 65535) return ZJ_ERR_ARG;
+    if (out_w == 0 || out_h == 0 || out_w > (unsigned)RESIZE_MAX_OUT || out_h > (unsigned)RESIZE_MAX_OUT) return ZJ_ERR_ARG;
+    if (edge != ZJ_WARP_FILL && edge != ZJ_WARP_REPLICATE) return ZJ_ERR_ARG;
+    unsigned w[4];
+    int64_t s[6];
+    warp_source_window(fixed, frame_w, frame_h, out_w, out_h, edge == ZJ_WARP_REPLICATE, w, s);
+    for (int k = 0; k < 4; k++) window[k] = w[k];
+    for (int k = 0; k < 6; k++) shifted[k] = s[k];
+    return ZJ_OK;
+}
+
+int zj_warp_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int channels,
+                   const double* matrices, unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                   const float* bias, const uint8_t* fill, int edge, void* d_out, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
+    if (channels != 1 && channels != 3) return ZJ_ERR_ARG;
+    ResizeOut ro = resize_out(out_w, out_h, dtype, out_layout, scale, bias, nullptr, ZJ_RESIZE_BILINEAR, d_out);
+    int rc = resize_out_args(ro, channels);
+    if (rc) return rc;
+    if ((uintptr_t)d_out % (uintptr_t)resize_elem_bytes(dtype)) return ZJ_ERR_ARG; // (the kernel's stores are whole elements)
+    WarpTail wt;
+    if ((rc = warp_tail_args(fill, edge, channels, wt))) return rc;
+    std::vector<int64_t> q;
+    if ((rc = warp_matrices(matrices, n, q))) return rc;
+    std::vector<unsigned> pitch(n);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_in[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        const size_t row = (size_t)w * channels;
+        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : (unsigned)row;
+        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return warp_launches(c, n, d_in, in_wh, pitch.data(), q.data(), ro, wt, 0, st);
+}
+
+// Each frame's source window (zj_warp_fixed.h: warp_source_window of its matrix, in frame pixels) through the crop stage into
+// the context's buffer, in the launch groups of the resized calls (zj_rzgroup.h) and under their reuse events; then the warp
+// over the group's crops with the integers relative to the windows.  A frame whose output sees nothing of the frame (fill
+// mode) decodes nothing.  ZJ_FLAG_GRAY_TO_RGB as in crops_resized_impl: the crop is one channel, the expand stage makes
+// the image the warp reads.
+int zj_decode_crops_warped_device(zj_ctx* c, const zj_frame_desc* caller_d, size_t nframes, const int16_t* const* d_y,
+                                  const int16_t* const* d_cb, const int16_t* const* d_cr, const double* matrices, unsigned out_w,
+                                  unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                                  const uint8_t* fill, int edge, void* d_out, void* stream)
+{
+    if (!c || !caller_d || !matrices || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !d_out) return ZJ_ERR_ARG;
+    const bool gray = gray_to_rgb(caller_d);
+    const zj_frame_desc stage_d = resized_stage_desc(caller_d);
+    const zj_frame_desc* const d = &stage_d;
+    const int ch = resize_channels(caller_d);
+    if (!ch || gray_to_rgb_refused(caller_d)) return ZJ_ERR_UNSUPPORTED;
+    Plan pl;
+    CropPlan cp;
+    int rc = make_crop_plan(d, 1, 1, 0, pl, cp);
+    if (rc) return rc;
+    ResizeOut ro = resize_out(out_w, out_h, dtype, out_layout, scale, bias, nullptr, ZJ_RESIZE_BILINEAR, d_out);
+    if ((rc = resize_out_args(ro, ch))) return rc;
+    if ((uintptr_t)d_out % (uintptr_t)resize_elem_bytes(dtype)) return ZJ_ERR_ARG;
+    WarpTail wt;
+    if ((rc = warp_tail_args(fill, edge, ch, wt))) return rc;
+    const bool chroma = pl.out != OUT_GRAY;
+    if ((rc = check_plane_ptrs(d_y, d_cb, d_cr, chroma, nframes))) return rc;
+    if (caller_d->out_layout != ZJ_LAYOUT_HWC) return ZJ_ERR_UNSUPPORTED; // (the warp reads interleaved images)
+    if (d->width == 0 || d->height == 0 || d->width > 65535 || d->height > 65535) return ZJ_ERR_ARG;
+    std::vector<int64_t> q, qs(6 * nframes);
+    if ((rc = warp_matrices(matrices, nframes, q))) return rc;
+    std::vector<unsigned> windows(4 * nframes);
+    for (size_t f = 0; f < nframes; f++) {
+        unsigned* const w = windows.data() + 4 * f;
+        warp_source_window(q.data() + 6 * f, (unsigned)d->width, (unsigned)d->height, out_w, out_h, edge == ZJ_WARP_REPLICATE, w,
+                           qs.data() + 6 * f);
+        if (w[2] == 0) continue;
+        CropPlan cw = cp;
+        cw.w = (int)w[2]; cw.h = (int)w[3];
+        int s0, s1, k0, k1;
+        if ((rc = crop_window(d, pl, cw, w[0], w[1], s0, s1, k0, k1))) return rc;
+    }
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    ro.chw = false;
+    std::vector<RzFrame> rzf(nframes);
+    for (size_t f = 0; f < nframes; f++) rzf[f] = RzFrame{windows[4 * f + 2], windows[4 * f + 3], 1, gray};
+    uint8_t* buf = nullptr;
+    if ((rc = resize_scratch(c, rz_scratch_need(rzf.data(), nframes, ch, false, RZ_GROUP_CAP) + 16, st, &buf))) return rc;
+    std::vector<RzPlace> place(nframes);
+    std::vector<const int16_t*> gy, gcb, gcr; // the frames of a group that decode something, gathered
+    std::vector<uint8_t*> gout;
+    std::vector<unsigned> gwin;
+    for (size_t g0 = 0, g1, bytes; g0 < nframes; g0 = g1) {
+        g1 = rz_group_next(rzf.data(), nframes, g0, ch, false, RZ_GROUP_CAP, place.data(), &bytes);
+        gy.clear(); gcb.clear(); gcr.clear(); gout.clear(); gwin.clear();
+        for (size_t f = g0; f < g1; f++) {
+            if (windows[4 * f + 2] == 0) continue;
+            gy.push_back(d_y[f]); gcb.push_back(chroma ? d_cb[f] : nullptr); gcr.push_back(chroma ? d_cr[f] : nullptr);
+            gout.push_back(buf + place[f].crop.off);
+            gwin.insert(gwin.end(), windows.begin() + 4 * f, windows.begin() + 4 * f + 4);
+        }
+        if (!gy.empty() && (rc = decode_crops_impl(c, d, pl, cp, gy.size(), gy.data(), chroma ? gcb.data() : nullptr,
+                                                   chroma ? gcr.data() : nullptr, gwin.data(), 4, gout.data(), st)))
+            return rc;
+        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, &wt, qs.data()))) return rc;
+    }
+    return ZJ_OK;
+}
+
 /* ---- mixed-geometry resized crops ----------------------------------------------- */
 namespace {
 // the pinned staging and the device table, at least `bytes` each, the staging free for the host to write: the last copy out
@@ -1315,7 +1508,8 @@ int mixed_tables(zj_ctx* c, size_t bytes)
 // stay as they are until the stream has run: the caller synchronises).  Otherwise they are device planes.
 int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
                              const int16_t* const* d_cb, const int16_t* const* d_cr, bool host_planes, const unsigned* windows,
-                             ResizeOut ro, int max_prescale_log2, const uint8_t* orientation, void* stream)
+                             ResizeOut ro, int max_prescale_log2, const uint8_t* orientation, void* stream,
+                             const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr)
 {
     if (!resize_filter_valid(ro.filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
     if (!c || !descs || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
@@ -1411,7 +1605,7 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
         // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
         (void)hipEventRecord(c->mx_done, st);
         ZJ_HIP(c, e);
-        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st))) return rc;
+        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, warp, warp_q))) return rc;
     }
     return ZJ_OK;
 }
@@ -1439,6 +1633,31 @@ int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t
                                             resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
                                             max_prescale_log2, orientation, nullptr);
     if (c && c->stream) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
+    }
+    return rc;
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_warped_batch_device): the mixed-geometry crops of several files'
+// host planes -- windows: each file's source window, not empty, in displayed pixels with `orientation` -- and, in place of the
+// resize, the warp of each group's images under q[6f .. 6f + 5], the integers relative to the windows; on the
+// context stream, synchronised
+int zjint_crops_warped_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                  const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows, const int64_t* q,
+                                  unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                                  const uint8_t* fill, int edge, const uint8_t* orientation, void* d_out)
+{
+    if (!c || !descs || !nframes || !q || !d_out) return ZJ_ERR_ARG;
+    if (descs[0].out_layout != ZJ_LAYOUT_HWC) return ZJ_ERR_UNSUPPORTED; // (the warp reads interleaved images)
+    if ((uintptr_t)d_out % (uintptr_t)(resize_elem_bytes(dtype) ? resize_elem_bytes(dtype) : 1)) return ZJ_ERR_ARG;
+    WarpTail wt;
+    int rc = warp_tail_args(fill, edge, resize_channels(&descs[0]) == 1 ? 1 : 3, wt);
+    if (rc) return rc;
+    rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
+                                  resize_out(out_w, out_h, dtype, out_layout, scale, bias, nullptr, ZJ_RESIZE_BILINEAR, d_out), 0,
+                                  orientation, nullptr, &wt, q);
+    if (c->stream) {
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
     }
@@ -2050,6 +2269,29 @@ int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, in
     const uint8_t fl = flip ? 1 : 0;
     int rc = zj_to_tensor_device(c, 1, &in, w, h, nullptr, in_channels, channels, dtype, out_layout, scale, bias, &fl, d_out, nullptr);
     if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+// ... and the warp of that image under the integers q; w == 0: there is no image, the output is all fill
+int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, const int64_t q[6], unsigned out_w,
+                   unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, const uint8_t* fill, int edge,
+                   void* d_out)
+{
+    if (!c || !q || !d_out || (w != 0 && !in) || (channels != 1 && channels != 3)) return ZJ_ERR_ARG;
+    if (w != 0 && (h == 0 || w > 65535 || h > 65535)) return ZJ_ERR_ARG;
+    ResizeOut ro = resize_out(out_w, out_h, dtype, out_layout, scale, bias, nullptr, ZJ_RESIZE_BILINEAR, d_out);
+    int rc = resize_out_args(ro, channels);
+    if (rc) return rc;
+    if ((uintptr_t)d_out % (uintptr_t)resize_elem_bytes(dtype)) return ZJ_ERR_ARG;
+    WarpTail wt;
+    if ((rc = warp_tail_args(fill, edge, channels, wt))) return rc;
+    if (w == 0 && edge != ZJ_WARP_FILL) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    const unsigned wh[2] = {w, h}, pitch = w * (unsigned)channels;
+    if ((rc = warp_launches(c, 1, &in, wh, &pitch, q, ro, wt, 0, c->stream))) return rc;
     if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
     if ((rc = resize_scratch_done(c, c->stream))) return rc;
     ZJ_HIP(c, hipStreamSynchronize(c->stream));

@@ -34,6 +34,7 @@
 #include "zj_crew.h"
 #include "zj_geom.h"
 #include "zj_rzgroup.h"
+#include "zj_warp_fixed.h"
 #include "zj_huff.h"
 
 namespace {
@@ -2949,6 +2950,18 @@ __attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, 
 __attribute__((weak)) int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int in_channels, int channels,
                                               int dtype, int out_layout, const float* scale, const float* bias, int flip, void* d_out);
 
+// ... and one u8 image warped into a tensor image under six integers (w == 0: no image, all fill)
+__attribute__((weak)) int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, const int64_t q[6],
+                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                         const float* bias, const uint8_t* fill, int edge, void* d_out);
+
+// ... and the mixed-geometry crops of several files' host planes, each group's images warped
+__attribute__((weak)) int zjint_crops_warped_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                                        const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
+                                                        const int64_t* q, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                        const float* scale, const float* bias, const uint8_t* fill, int edge,
+                                                        const uint8_t* orientation, void* d_out);
+
 // The last stage of a single-file call that passes its u8 image through the context's buffer: the resize to out_w x out_h
 // (the resized-crop calls), or the conversion at the image's own size (to_tensor: the crop-tensor calls, DESIGN.md 3.15;
 // out_w x out_h is then the displayed window itself and filter is not used).  Everything in front of it -- the buffer's
@@ -2960,6 +2973,10 @@ struct LastStage {
     const float *scale, *bias;
     int flip, filter;
     void* d_out;
+    // the affine warp instead: the integers relative to the window the call decodes, the fill bytes, the edge mode
+    const int64_t* warp_q = nullptr;
+    const uint8_t* fill = nullptr;
+    int edge = 0;
 };
 static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, const LastStage& ls,
                           size_t out_cap, size_t* out_len, int o = 1);
@@ -3377,6 +3394,12 @@ static int resized_checks(zj_decoder* d, int k, unsigned& x, unsigned& y, unsign
 static int last_stage(zj_decoder* d, zj_ctx* ctx, const LastStage& s, const uint8_t* in, unsigned w, unsigned h, int in_ch, int ch,
                       int layout)
 {
+    if (s.warp_q) {
+        const int rc = layout != ZJ_LAYOUT_HWC && ch == 3 ? (int)ZJ_ERR_UNSUPPORTED
+                                                          : zjint_warp_one(ctx, in, w, h, ch, s.warp_q, s.out_w, s.out_h, s.dtype, s.out_layout,
+                                                                           s.scale, s.bias, s.fill, s.edge, s.d_out);
+        return rc ? fail(d, rc, std::string("warp: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : (int)ZJ_OK;
+    }
     const int rc = s.to_tensor ? zjint_to_tensor_one(ctx, in, w, h, in_ch, ch, s.dtype, s.out_layout, s.scale, s.bias, s.flip, s.d_out)
                                : zjint_resize_one(ctx, in, w, h, ch, layout, s.out_w, s.out_h, s.dtype, s.out_layout, s.scale, s.bias,
                                                   s.flip, s.filter, s.d_out);
@@ -3564,6 +3587,120 @@ int zj_decoder_finish_pixels_resized_crop_oriented_device(zj_decoder* d, zj_ctx*
     const int k = out_w && out_h ? zj::prescale_pick(w, h, out_w, out_h, max_prescale_log2) : 0;
     return finish_resized(d, ctx, k, x, y, w, h, LastStage{false, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out}, out_cap, out_len,
                           d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
+}
+
+// The decoder's last prepared file warped into one image of a normalised tensor: the part of the frame the
+// output can see (zj_warp_fixed.h: warp_source_window, in displayed pixels with apply_orientation) takes finish_resized's
+// composition -- crop, turn, gray to RGB, CMYK, any sampling -- and the warp under the integers relative to that window is
+// its last stage.  An output that sees nothing of the frame (fill mode) decodes nothing.
+int zj_decoder_finish_pixels_warped_device(zj_decoder* d, zj_ctx* ctx, const double matrix[6], int apply_orientation, unsigned out_w,
+                                           unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias,
+                                           const uint8_t* fill, int edge, void* d_out, size_t out_cap, size_t* out_len)
+{
+    using namespace zj;
+    if (!d || !ctx || !d_out || !matrix) return ZJ_ERR_ARG;
+    if (!zjint_warp_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    if (edge != ZJ_WARP_FILL && edge != ZJ_WARP_REPLICATE) return fail(d, ZJ_ERR_ARG, "unknown edge mode");
+    int64_t q[6], qs[6];
+    if (!warp_fixed(matrix, q)) return fail(d, ZJ_ERR_ARG, "not a matrix the warp takes");
+    if (!d->seen_sof || d->err_code || (!d->coef_valid && !d->scan_ready)) return fail(d, ZJ_ERR_ARG, "no successfully decoded coefficients to finish");
+    if (d->out_layout == ZJ_LAYOUT_CHW) return fail(d, ZJ_ERR_UNSUPPORTED, "the warp reads interleaved images: a decoder with ZJ_LAYOUT_HWC");
+    if (out_w == 0 || out_h == 0 || out_w > (unsigned)RESIZE_MAX_OUT || out_h > (unsigned)RESIZE_MAX_OUT) return fail(d, ZJ_ERR_ARG, "not a valid output size or dtype");
+    zj_frame_desc fd;
+    fill_info(d, nullptr, &fd);
+    const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
+    unsigned dw = 0, dh = 0, win[4];
+    if (!orient_size(o, (unsigned)fd.width, (unsigned)fd.height, &dw, &dh) || dw == 0 || dh == 0 || dw > 65535 || dh > 65535)
+        return fail(d, ZJ_ERR_ARG, "not a frame the warp takes");
+    warp_source_window(q, dw, dh, out_w, out_h, edge == ZJ_WARP_REPLICATE, win, qs);
+    LastStage ls{false, out_w, out_h, dtype, out_layout, scale, bias, 0, ZJ_RESIZE_BILINEAR, d_out};
+    ls.warp_q = qs; ls.fill = fill; ls.edge = edge;
+    if (win[2] == 0) { // nothing of the frame: the checks of a 1 x 1 window, then the fill alone
+        unsigned x = 0, y = 0, w = 1, h = 1;
+        int ch = 0;
+        const int rc = resized_checks(d, 0, x, y, w, h, out_w, out_h, dtype, ZJ_RESIZE_BILINEAR, out_cap, out_len, o, fd, ch);
+        if (rc) return rc;
+        return last_stage(d, ctx, ls, nullptr, 0, 0, ch, ch, ZJ_LAYOUT_HWC);
+    }
+    return finish_resized(d, ctx, 0, win[0], win[1], win[2], win[3], ls, out_cap, out_len, o);
+}
+
+// Several prepared files of any sizes, each under its own matrix, into one warped tensor, after the batch body
+// of 3.10 / 3.14.  The files the CPU walker decoded and whose output sees some of the frame go through the mixed-geometry
+// crop launches, consecutive ones in one call, each cut to its own source window, and the warp launches over each group's
+// crops; every other file -- a scan left for the device, four components, another sampling, an all-zero output, an output
+// that sees nothing of the frame, anything refused -- goes through the single-file call, which gives the same bytes and
+// sets the decoder's error text.
+int zj_decoder_finish_pixels_warped_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const double* matrices,
+                                                 int apply_orientation, unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                 const float* scale, const float* bias, const uint8_t* fill, int edge, void* d_out,
+                                                 size_t out_cap, int* rcs)
+{
+    using namespace zj;
+    if (!ds || !n || !ctx || !matrices || !d_out || !rcs) return ZJ_ERR_ARG;
+    if (!zjint_crops_warped_mixed_host || !zjint_warp_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+    const zj_decoder* first = nullptr;
+    for (size_t k = 0; k < n; k++) {
+        if (!ds[k]) continue;
+        if (!first) first = ds[k];
+        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
+    }
+    if (!first) return ZJ_ERR_ARG;
+    zj_frame_desc fd0{};
+    fd0.out_colorspace = (uint32_t)first->out_colorspace;
+    const size_t img = resized_len(resize_channels(&fd0), out_w, out_h, dtype); // (0: every file's own call says why)
+    if (img && out_cap / img < n) return ZJ_ERR_ARG;
+    const auto single = [&](size_t k) {
+        return zj_decoder_finish_pixels_warped_device(ds[k], ctx, matrices + 6 * k, apply_orientation, out_w, out_h, dtype, out_layout,
+                                                      scale, bias, fill, edge, (uint8_t*)d_out + k * img, img, nullptr);
+    };
+    std::vector<zj_frame_desc> fds(n);
+    std::vector<const int16_t*> py(n), pcb(n), pcr(n);
+    std::vector<uint8_t> ori(n, 1);
+    std::vector<unsigned> wins(4 * n, 0);
+    std::vector<int64_t> qs(6 * n, 0);
+    std::vector<char> mixed(n, 0);
+    for (size_t k = 0; k < n; k++) {
+        zj_decoder* const d = ds[k];
+        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
+        int64_t q[6];
+        const bool plain = img && (edge == ZJ_WARP_FILL || edge == ZJ_WARP_REPLICATE) && warp_fixed(matrices + 6 * k, q) &&
+                           d->seen_sof && !d->err_code && d->coef_valid && !d->scan_ready && d->out_layout != ZJ_LAYOUT_CHW;
+        if (!plain) { rcs[k] = single(k); continue; }
+        const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
+        fill_info(d, nullptr, &fds[k]);
+        unsigned dw = 0, dh = 0;
+        unsigned* const win = wins.data() + 4 * k;
+        if (!orient_size(o, (unsigned)fds[k].width, (unsigned)fds[k].height, &dw, &dh) || dw == 0 || dh == 0 || dw > 65535 || dh > 65535) {
+            rcs[k] = single(k);
+            continue;
+        }
+        warp_source_window(q, dw, dh, out_w, out_h, edge == ZJ_WARP_REPLICATE, win, qs.data() + 6 * k);
+        if (win[2] == 0) { rcs[k] = single(k); continue; } // (all fill: nothing to decode)
+        unsigned x = win[0], y = win[1], w = win[2], h = win[3]; // (resized_checks turns its copy into the stored window)
+        int ch = 0;
+        if ((rcs[k] = resized_checks(d, 0, x, y, w, h, out_w, out_h, dtype, ZJ_RESIZE_BILINEAR, img, nullptr, o, fds[k], ch))) continue;
+        if (d->ncomp == 4 || d->odd || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
+        py[k] = d->comps[0].coef;
+        pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
+        ori[k] = (uint8_t)o;
+        mixed[k] = 1;
+    }
+    for (size_t k0 = 0; k0 < n;) {
+        if (!mixed[k0]) { k0++; continue; }
+        size_t k1 = k0;
+        while (k1 < n && mixed[k1]) k1++;
+        const int rc = zjint_crops_warped_mixed_host(ctx, fds.data() + k0, k1 - k0, py.data() + k0, pcb.data() + k0, pcr.data() + k0,
+                                                     wins.data() + 4 * k0, qs.data() + 6 * k0, out_w, out_h, dtype, out_layout, scale,
+                                                     bias, fill, edge, apply_orientation ? ori.data() + k0 : nullptr,
+                                                     (uint8_t*)d_out + k0 * img);
+        // a run that fails: each of its files through its own call, which names the failing one.  A run refused for its
+        // arguments has launched nothing; after a HIP error in a later launch group the earlier groups' images are written
+        // again, with the same bytes
+        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(k) : (int)ZJ_OK;
+        k0 = k1;
+    }
+    return ZJ_OK;
 }
 
 // Several prepared files of any sizes into one resized-crop tensor.  The files the CPU walker decoded go

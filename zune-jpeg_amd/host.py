@@ -200,6 +200,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decode_crops_tensor_mixed_device", "zj_decoder_finish_pixels_crop_tensor_batch_device",
     "zj_to_tensor_device", "zj_decoder_finish_pixels_crop_tensor_oriented_device",
     "zj_decoder_finish_pixels_crop_tensor_batch_oriented_device",
+    "zj_warp_fixed", "zj_warp_source_window", "zj_warp_device", "zj_decode_crops_warped_device",
+    "zj_decoder_finish_pixels_warped_device", "zj_decoder_finish_pixels_warped_batch_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -353,6 +355,16 @@ def lib():
     L.zj_decoder_finish_pixels_crop_tensor_oriented_device.argtypes = L.zj_decoder_finish_pixels_crop_tensor_device.argtypes
     L.zj_decoder_finish_pixels_crop_tensor_batch_oriented_device.argtypes = L.zj_decoder_finish_pixels_crop_tensor_batch_device.argtypes
     L.zj_to_tensor_device.argtypes = [vp, sz, vp, C.c_uint, C.c_uint, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.zj_warp_fixed.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.zj_warp_source_window.argtypes = [C.POINTER(C.c_int64), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_uint),
+                                        C.POINTER(C.c_int64)]
+    L.zj_warp_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    L.zj_decode_crops_warped_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                vp, vp, vp, C.c_int, vp, vp]
+    L.zj_decoder_finish_pixels_warped_device.argtypes = [vp, vp, C.POINTER(C.c_double), C.c_int, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                         vp, vp, vp, C.c_int, vp, sz, C.POINTER(sz)]
+    L.zj_decoder_finish_pixels_warped_batch_device.argtypes = [vp, sz, vp, vp, C.c_int, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp, vp,
+                                                               C.c_int, vp, sz, vp]
     L.zj_resize_filtered_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, C.c_int, vp, vp,
                                             vp, C.c_int, vp, vp]
     L.zj_decode_crops_resized_filtered_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
@@ -476,6 +488,51 @@ def orient_window(orientation, frame_w, frame_h, window):
     st = (C.c_uint * 4)()
     _check(lib().zj_orient_window(int(orientation), frame_w, frame_h, win, st), "zj_orient_window")
     return tuple(st)
+
+
+WARP_FILL, WARP_REPLICATE = 0, 1  # ZJ_WARP_*
+
+
+def warp_edge(edge):
+    """"fill" / "replicate" (or the codes) -> ZJ_WARP_FILL / ZJ_WARP_REPLICATE"""
+    try:
+        return {"fill": WARP_FILL, "replicate": WARP_REPLICATE, WARP_FILL: WARP_FILL, WARP_REPLICATE: WARP_REPLICATE}[edge]
+    except (KeyError, TypeError):
+        raise ValueError(f'edge must be "fill" or "replicate", not {edge!r}') from None
+
+
+def warp_fixed(matrix):
+    """The six Q24 integers (A, B, C0, D, E, F0) of an affine matrix (a, b, c, d, e, f) that maps an output pixel centre to
+    source coordinates (zj_warp_fixed); ZjError: an entry the warp refuses"""
+    m = (C.c_double * 6)(*[float(v) for v in matrix])
+    q = (C.c_int64 * 6)()
+    _check(lib().zj_warp_fixed(m, q), "zj_warp_fixed")
+    return [int(v) for v in q]
+
+
+def warp_source_window(fixed, frame_w, frame_h, out_w, out_h, edge="fill"):
+    """((x, y, w, h), shifted integers): the part of a frame_w x frame_h frame an out_w x out_h output under the integers
+    `fixed` can read, and the integers relative to it (zj_warp_source_window); w = h = 0: the output is all fill"""
+    q = (C.c_int64 * 6)(*[int(v) for v in fixed])
+    win = (C.c_uint * 4)()
+    sh = (C.c_int64 * 6)()
+    _check(lib().zj_warp_source_window(q, frame_w, frame_h, out_w, out_h, warp_edge(edge), win, sh), "zj_warp_source_window")
+    return tuple(int(v) for v in win), [int(v) for v in sh]
+
+
+def _matrices(matrices, n):
+    if len(matrices) != n or any(len(m) != 6 for m in matrices):
+        raise ValueError("one matrix of six numbers per image")
+    return (C.c_double * (6 * n))(*[float(v) for m in matrices for v in m])
+
+
+def _fill(fill):
+    if fill is None:
+        return None
+    f = [int(v) for v in fill]
+    if not 1 <= len(f) <= 3 or any(not 0 <= v <= 255 for v in f):
+        raise ValueError("fill: one byte per channel")
+    return (C.c_uint8 * 3)(*(f + [0] * (3 - len(f))))
 
 
 def _floats(v):
@@ -678,6 +735,33 @@ class Context:
         _check(lib().zj_to_tensor_device(self._h, n, (C.c_void_p * n)(*d_in), w, h, pit, in_channels, channels, dtype, out_layout,
                                          _floats(scale), _floats(bias), _flips(flips, n), d_out, stream), "zj_to_tensor_device",
                self._h)
+
+    def warp_device(self, d_in, sizes, channels, matrices, out_w, out_h, dtype, out_layout, d_out, scale=None, bias=None,
+                    fill=None, edge="fill", pitches=None, stream=None):
+        """Affine-warped images into a normalised tensor (zj_warp_device): d_in = device pointers of
+        interleaved u8 images, sizes = one (w, h) each, matrices = one (a, b, c, d, e, f) each, output pixel centre -> source
+        coordinates; fill = one byte per channel (None: 0), edge "fill" or "replicate"; pitches = bytes between rows
+        (None: tight); the dense output at d_out.  Asynchronous on `stream`."""
+        n = len(d_in)
+        if len(sizes) != n or (pitches is not None and len(pitches) != n):
+            raise ValueError("one size (and pitch) per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
+        _check(lib().zj_warp_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, _matrices(matrices, n), out_w, out_h,
+                                    dtype, out_layout, _floats(scale), _floats(bias), _fill(fill), warp_edge(edge), d_out, stream),
+               "zj_warp_device", self._h)
+
+    def decode_crops_warped_device(self, desc, d_y, d_cb, d_cr, matrices, out_w, out_h, dtype, out_layout, d_out, scale=None,
+                                   bias=None, fill=None, edge="fill", stream=None):
+        """Frames of one geometry warped into a normalised tensor (zj_decode_crops_warped_device): pointers as in
+        decode_crops_device, matrices = one per frame, in frame pixels; only the part of each frame its output can see is
+        decoded.  The other arguments as warp_device.  Asynchronous on `stream`."""
+        n = len(d_y)
+        arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
+        _check(lib().zj_decode_crops_warped_device(self._h, C.byref(desc), n, arr(d_y), arr(d_cb), arr(d_cr), _matrices(matrices, n),
+                                                   out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias), _fill(fill),
+                                                   warp_edge(edge), d_out, stream),
+               "zj_decode_crops_warped_device", self._h)
 
     def orient_device(self, d_in, sizes, channels, in_layout, orientations, d_out, in_pitches=None, out_pitches=None,
                       stream=None):
@@ -1105,6 +1189,23 @@ class Decoder:
             self._raise(rc)
         return n.value
 
+    def finish_pixels_warped_device(self, matrix, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None, fill=None,
+                                    edge="fill", apply_orientation=False):
+        """Stage 2 warped under the affine `matrix` (a, b, c, d, e, f: output pixel centre -> frame coordinates) into one image
+        of a normalised tensor (zj_decoder_finish_pixels_warped_device, DESIGN.md 3.16), left in HBM at device pointer d_out;
+        returns the image's length in bytes.  Only the part of the frame the output sees is decoded.  apply_orientation: the
+        matrix is in DISPLAYED pixels of the file's EXIF orientation."""
+        if self._ctx is None:
+            self._ctx = Context()
+        n = C.c_size_t(0)
+        m = (C.c_double * 6)(*[float(v) for v in matrix])
+        rc = lib().zj_decoder_finish_pixels_warped_device(self._d, self._ctx.handle, m, 1 if apply_orientation else 0, out_w, out_h,
+                                                          dtype, out_layout, _floats(scale), _floats(bias), _fill(fill),
+                                                          warp_edge(edge), d_out, cap, C.byref(n))
+        if rc:
+            self._raise(rc)
+        return n.value
+
     def finish_pixels_scaled_device(self, scale, d_out, cap, window=None, out_pitch=0):
         """Stage 2 at 1/scale (2, 4 or 8), cut to window = (x, y, w, h) of the reduced frame (None: all of it), pixels left
         in HBM at device pointer d_out (the contract of zj_decode_crops_scaled_device); returns the length in bytes."""
@@ -1289,6 +1390,22 @@ def finish_pixels_crop_tensor_batch(decoders, ctx, origins, w, h, dtype, out_lay
     name = "zj_decoder_finish_pixels_crop_tensor_batch_oriented_device" if apply_orientation else "zj_decoder_finish_pixels_crop_tensor_batch_device"
     _check(getattr(lib(), name)(dptr, n, ctx.handle, org, w, h, dtype, out_layout, _floats(scale), _floats(bias), _flips(flips, n),
                                 d_out, cap, rcs), name, ctx.handle)
+    return list(rcs)
+
+
+def finish_pixels_warped_batch(decoders, ctx, matrices, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
+                               fill=None, edge="fill", apply_orientation=False):
+    """zj_decoder_finish_pixels_warped_batch_device over Decoder objects that went through prepare() or decode_coefficients(),
+    each with a file of its own size: matrices = one (a, b, c, d, e, f) per decoder, in pixels of its frame (of its DISPLAYED
+    frame with apply_orientation); image k left at device pointer d_out + k * resized_out_len.  Returns the list of
+    statuses: image k is Decoder.finish_pixels_warped_device's for decoder k alone, a failed file's slot is untouched."""
+    n = len(decoders)
+    dptr = (C.c_void_p * n)(*[d._d for d in decoders])
+    rcs = (C.c_int * n)()
+    _check(lib().zj_decoder_finish_pixels_warped_batch_device(dptr, n, ctx.handle, _matrices(matrices, n), 1 if apply_orientation else 0,
+                                                              out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
+                                                              _fill(fill), warp_edge(edge), d_out, cap, rcs),
+           "zj_decoder_finish_pixels_warped_batch_device", ctx.handle)
     return list(rcs)
 
 

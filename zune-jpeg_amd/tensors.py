@@ -611,3 +611,160 @@ def to_normalized_tensor(ctx, images, dtype=None, layout="NCHW", mean=None, std=
     ctx.to_tensor_device([im.data_ptr() for im in imgs], sizes[0][0], sizes[0][1], cin, channels, code,
                          TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips, pitches, s.cuda_stream)
     return out
+
+
+def warp_matrix(out_size, center, angle=0.0, scale=1.0, shear=(0.0, 0.0), translate=(0.0, 0.0), hflip=False):
+    """The matrix (a, b, c, d, e, f) of float64 that warp_to_tensor and its kin take -- output pixel centre -> continuous
+    source coordinates, x to the right, y DOWN, pixel i covering [i, i + 1) -- for an augmentation given the forward way.
+    With out_size = (out_w, out_h) and homogeneous 3 x 3 matrices acting on source coordinates,
+
+        M = T(out_w / 2 + tx, out_h / 2 + ty) . R(angle) . Sh(shear) . S(scale) . [F] . T(-cx, -cy)
+
+    takes a source point to its place in the output, and the result is the first two rows of M^-1:
+        T(x, y)    the translation by (x, y); center = (cx, cy) is the source point that lands on the output's centre,
+                   moved by translate = (tx, ty) output pixels
+        F          diag(-1, 1): the source mirrored left to right about `center` first (hflip)
+        S(scale)   diag(sx, sy), scale a number or (sx, sy): > 1 enlarges
+        Sh(shear)  [[1, tan shx], [tan shy, 1]], shear = (shx, shy) in degrees
+        R(angle)   [[cos t, sin t], [-sin t, cos t]], t = angle in degrees: with y down, a positive angle turns the image
+                   COUNTER-clockwise as displayed (90 is numpy's rot90)
+    A letterbox of a w x h image into S x S is warp_matrix((S, S), (w / 2, h / 2), scale=min(S / w, S / h)) with edge
+    "fill"; ValueError: a singular M."""
+    import math
+    import numpy as np
+    ow, oh = out_size
+    sx, sy = (scale, scale) if np.isscalar(scale) else scale
+    t = math.radians(angle)
+
+    def T(x, y):
+        return np.array([[1.0, 0.0, x], [0.0, 1.0, y], [0.0, 0.0, 1.0]])
+
+    def L(m00, m01, m10, m11):
+        return np.array([[m00, m01, 0.0], [m10, m11, 0.0], [0.0, 0.0, 1.0]])
+
+    M = T(ow / 2.0 + translate[0], oh / 2.0 + translate[1]) @ L(math.cos(t), math.sin(t), -math.sin(t), math.cos(t)) \
+        @ L(1.0, math.tan(math.radians(shear[0])), math.tan(math.radians(shear[1])), 1.0) @ L(float(sx), 0.0, 0.0, float(sy)) \
+        @ L(-1.0 if hflip else 1.0, 0.0, 0.0, 1.0) @ T(-float(center[0]), -float(center[1]))
+    det = M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0]
+    if not math.isfinite(det) or det == 0.0:
+        raise ValueError("warp_matrix: the map is singular")
+    inv = np.linalg.inv(M)
+    return tuple(float(v) for v in inv[:2].reshape(-1))
+
+
+def warp_to_tensor(ctx, images, matrices, size, dtype=None, layout="NCHW", mean=None, std=None, fill=None, edge="fill",
+                   stream=None):
+    """u8 CUDA images of their own sizes, each under its own affine map, into ONE dense normalised tensor (zj_warp_device,
+    DESIGN.md 3.16): images = [H, W, 3], [H, W, 1] or [H, W] tensors, rows may be strided; matrices = one (a, b, c, d, e, f)
+    per image, output pixel centre -> source coordinates (warp_matrix builds them); size = (out_w, out_h).  Bilinear taps,
+    not antialiased.  edge "fill": outside the image the taps read fill, one byte 0..255 per channel (None: 0), which
+    becomes (fill / 255 - mean) / std; "replicate": the image's edge pixels.  Output, dtype, mean / std and streams as
+    resize_to_tensor."""
+    import torch
+    from .host import warp_edge
+    warp_edge(edge)
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    imgs, sizes, pitches, channels = _u8_images(images, "HWC")
+    n = len(imgs)
+    if len(matrices) != n:
+        raise ValueError("one matrix per image")
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    _on_stream(s, cur, imgs)
+    ctx.warp_device([im.data_ptr() for im in imgs], sizes, channels, matrices, size[0], size[1], code,
+                    TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, fill, edge, pitches,
+                    s.cuda_stream)
+    return out
+
+
+def decode_warped_to_tensor(ctx, desc, frames, matrices, size, dtype=None, layout="NCHW", mean=None, std=None, fill=None,
+                            edge="fill", stream=None):
+    """Frames of one geometry decoded and warped into ONE dense normalised tensor (zj_decode_crops_warped_device, DESIGN.md
+    3.16): frames as decode_resized_crops_to_tensor takes them, matrices = one per frame in FRAME pixels (warp_matrix).  Only
+    the part of each frame its output can see is decoded; the result is warp_to_tensor's of the whole decoded frame.
+    desc.flags | FLAG_GRAY_TO_RGB as decode_resized_crops_to_tensor.  The other arguments as warp_to_tensor."""
+    import torch
+    from .host import warp_edge
+    warp_edge(edge)
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(frames)
+    if n == 0 or len(matrices) != n:
+        raise ValueError("one matrix per frame, at least one frame")
+    ow, oh = size
+    if lib().zj_resized_out_len(C.byref(desc), ow, oh, code) == 0:
+        raise ValueError(f"{ow}x{oh} {dtype} is not a supported warped output of this frame descriptor")
+    channels = ColorSpace(desc.out_colorspace).num_components()
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = frames[0][0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    _on_stream(s, cur, [p for fr in frames for p in fr])
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ctx.decode_crops_warped_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
+                                   [ptr(fr[2]) for fr in frames], matrices, ow, oh, code,
+                                   TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, fill, edge,
+                                   s.cuda_stream)
+    return out
+
+
+def decode_files_warped_to_tensor(ctx, blobs, matrices, size, dtype=None, layout="NCHW", mean=None, std=None, fill=None,
+                                  edge="fill", apply_orientation=False, options=None, workers=1, stream=None, decoders=None):
+    """JPEG files of ANY sizes, each under its own affine map, -> ONE dense normalised tensor: blobs = a list of
+    bytes-like JPEG files, matrices = one (a, b, c, d, e, f) per file, output pixel centre -> coordinates of the file's frame
+    (of its DISPLAYED frame with apply_orientation; warp_matrix builds them), size = (out_w, out_h).  Image k is
+    Decoder.finish_pixels_warped_device's for file k (zj_decoder_finish_pixels_warped_batch_device): only the part of each
+    frame its output sees is decoded, ordinary files in shared launches.  fill and edge as warp_to_tensor; dtype, mean / std,
+    options (FLAG_GRAY_TO_RGB, FLAG_CMYK_TO_RGB, FLAG_ANY_SAMPLING included), workers, decoders and stream as
+    decode_files_resized_to_tensor.  The batch call runs on the context's stream and has finished when it returns; a file
+    that fails raises DecodeError naming its index (its image is untouched, the others are decoded)."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from .host import DecodeError, Decoder, finish_pixels_warped_batch, warp_edge
+    warp_edge(edge)
+    dtype = torch.bfloat16 if dtype is None else dtype
+    code = _resize_dtype(dtype)
+    n = len(blobs)
+    if n == 0 or len(matrices) != n:
+        raise ValueError("one matrix per file, at least one file")
+    decs = decoders if decoders is not None else []
+    while len(decs) < n:
+        decs.append(Decoder(options, ctx))
+    decs = decs[:n]
+
+    def prep(k):
+        try:
+            return decs[k].prepare(blobs[k])
+        except DecodeError as e:
+            return e
+
+    nw = max(1, min(int(workers), 16, n))
+    if nw > 1:
+        with ThreadPoolExecutor(nw) as ex:
+            prepared = list(ex.map(prep, range(n)))
+    else:
+        prepared = [prep(k) for k in range(n)]
+    for k, r in enumerate(prepared):
+        if isinstance(r, DecodeError):
+            raise DecodeError(r.status, f"file {k}: {r.text}")
+    channels = ColorSpace(decs[0]._out_cs).num_components()
+    if channels not in (1, 3):
+        raise ValueError("warped outputs have 1 or 3 channels")
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    out = _resized_out(n, channels, size, dtype, layout, dev, s)
+    s.synchronize()  # (the files run on the context's stream)
+    rcs = finish_pixels_warped_batch(decs, ctx, matrices, size[0], size[1], code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC,
+                                     out.data_ptr(), out.numel() * out.element_size(), scale, bias, fill, edge,
+                                     bool(apply_orientation))
+    for k, rc in enumerate(rcs):
+        if rc:
+            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+    return out
