@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/zjhip.h"
+#include "zj_internal.h"
 #include "zj_launch.h"
 #include "zj_crop_tensor_launch.h"
 #include "zj_mixed_launch.h"
@@ -545,7 +546,8 @@ static int decode_device_impl(zj_ctx* c, const zj_frame_desc* d, const Plan& pl,
         for (int r = 0; r < split; r++) {
             const int s0 = r * per, s1 = (s0 + per < pl.n_strips) ? s0 + per : pl.n_strips;
             Params q = p;
-            const long long yrow = (long long)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8), crow = (long long)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+            size_t yrow, crow;
+            plan_strip_elems(pl, yrow, crow);
             q.y = p.y + s0 * yrow; q.cb = p.cb ? p.cb + s0 * crow : nullptr; q.cr = p.cr ? p.cr + s0 * crow : nullptr;
             q.out = p.out + (size_t)s0 * pl.strip_rows * pl.out_pitch;
             q.height = (int)d->height - s0 * pl.strip_rows;
@@ -796,7 +798,8 @@ int zjint_crop_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const 
         int s0, s1, k0, k1;
         crop_window(d, pl, cp, x, yy, s0, s1, k0, k1);
         // i16 elements per strip (the split of decode_device_impl's ZJ_SPLIT experiment)
-        const size_t yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8), crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+        size_t yrow, crow;
+        plan_strip_elems(pl, yrow, crow);
         if ((rc = upload_plane_rows(c, pl, chroma, y, cb, cr, (size_t)s0, (size_t)s1, yrow, crow, p))) return rc;
     }
     if ((rc = decode_crops_impl(c, d, pl, cp, 1, &p[0], &p[1], &p[2], origin, 2, &d_out, c->stream))) return rc;
@@ -823,6 +826,36 @@ int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy,
 /* ---- resize + normalise ---------------------------------------------------------- */
 namespace {
 bool finite_f32(float v) { return v - v == 0.f; }
+
+// The per-channel factors of the tensor kernels from the caller's scale / bias (nullptr: 1, 0; read for the first `channels`
+// only): s_c = scale_c * 2^-16 -- exact: a power of two, above float32's smallest normal for every |scale| >= 2^-110 -- and
+// b_c = bias_c.  false: a factor that is not finite.
+bool kernel_factors(const float* scale, const float* bias, int channels, float s[3], float b[3])
+{
+    for (int k = 0; k < 3; k++) {
+        const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
+        if (!finite_f32(sc) || !finite_f32(bi)) return false;
+        s[k] = sc * (1.f / 65536.f);
+        b[k] = bi;
+    }
+    return true;
+}
+
+// The images of a u8 stage call checked and their pitches resolved: image f is in_wh[2f] x in_wh[2f + 1] pixels of
+// row_channels bytes each in a row, its rows in_pitch[f] bytes apart (in_pitch nullptr or 0: tight)
+int stage_images(size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int row_channels,
+                 std::vector<unsigned>& pitch)
+{
+    pitch.resize(n);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_in[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        const size_t row = (size_t)w * row_channels;
+        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : (unsigned)row;
+        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    return ZJ_OK;
+}
 
 // The output side of a resized call, as every layer below the entry points takes it: the dense tensor at d_out, image i of
 // the call at d_out + i * img_bytes, flipped if flip[i] (nullptr: none).
@@ -860,13 +893,7 @@ int resize_out_args(ResizeOut& o, int channels)
     o.img_bytes = resized_len(channels, o.out_w, o.out_h, o.dtype);
     if (!o.img_bytes) return ZJ_ERR_ARG; // (the size or the dtype)
     if (o.layout != ZJ_TENSOR_NCHW && o.layout != ZJ_TENSOR_NHWC) return ZJ_ERR_ARG;
-    for (int k = 0; k < 3; k++) {
-        const float sc = o.scale && k < channels ? o.scale[k] : 1.f, bi = o.bias && k < channels ? o.bias[k] : 0.f;
-        if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
-        o.s[k] = sc * (1.f / 65536.f); // (exact: a power of two, above float32's smallest normal for every |scale| >= 2^-110)
-        o.b[k] = bi;
-    }
-    return ZJ_OK;
+    return kernel_factors(o.scale, o.bias, channels, o.s, o.b) ? ZJ_OK : ZJ_ERR_ARG;
 }
 
 // images [0, n) -> images [first, first + n) of the output, launches of up to RESIZE_BATCH images; wh[2i], wh[2i + 1]: image
@@ -1114,15 +1141,10 @@ int zj_resize_filtered_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, c
     int rc = resize_out_args(ro, channels);
     if (rc) return rc;
     const bool chw = ro.chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
-    std::vector<unsigned> pitch(n);
-    for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_in[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
-        const size_t row = (size_t)w * (chw ? 1 : channels);
-        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : (unsigned)row;
-        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
-        if (chw && (size_t)pitch[f] * h * 3 > ((size_t)1 << 31)) return ZJ_ERR_ARG; // (the kernel's plane offsets)
-    }
+    std::vector<unsigned> pitch;
+    if ((rc = stage_images(n, d_in, in_wh, in_pitch, chw ? 1 : channels, pitch))) return rc;
+    for (size_t f = 0; chw && f < n; f++)
+        if ((size_t)pitch[f] * in_wh[2 * f + 1] * 3 > ((size_t)1 << 31)) return ZJ_ERR_ARG; // (the kernel's plane offsets)
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return resize_launches(c, n, d_in, in_wh, pitch.data(), ro, 0, st);
@@ -1397,14 +1419,8 @@ int zj_warp_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsign
     if ((rc = warp_tail_args(fill, edge, channels, wt))) return rc;
     std::vector<int64_t> q;
     if ((rc = warp_matrices(matrices, n, q))) return rc;
-    std::vector<unsigned> pitch(n);
-    for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_in[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
-        const size_t row = (size_t)w * channels;
-        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : (unsigned)row;
-        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
-    }
+    std::vector<unsigned> pitch;
+    if ((rc = stage_images(n, d_in, in_wh, in_pitch, channels, pitch))) return rc;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return warp_launches(c, n, d_in, in_wh, pitch.data(), q.data(), ro, wt, 0, st);
@@ -1503,6 +1519,74 @@ int mixed_tables(zj_ctx* c, size_t bytes)
     return ZJ_OK;
 }
 
+// The records the caller has written into the pinned staging (after mixed_tables) -> the device table in one copy of `bytes`,
+// then launches(table), the launches that read it, all on st.  st waits for the last launch that read the table before the
+// copy; mx_up says when the staging may be written again, mx_done when the table may.
+extern "C++" template <class Launches>
+int mixed_submit(zj_ctx* c, size_t bytes, hipStream_t st, Launches launches)
+{
+    if (c->mx_used) ZJ_HIP(c, hipStreamWaitEvent(st, c->mx_done, 0));
+    ZJ_HIP(c, hipMemcpyAsync(c->mx_dev, c->mx_host, bytes, hipMemcpyHostToDevice, st));
+    ZJ_HIP(c, hipEventRecord(c->mx_up, st));
+    c->mx_used = true;
+    const hipError_t e = launches((const uint8_t*)c->mx_dev);
+    // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
+    (void)hipEventRecord(c->mx_done, st);
+    ZJ_HIP(c, e);
+    return ZJ_OK;
+}
+
+// The plane rows one frame's crop stage reads: rows [r0, r1) of yrow (luma) / crow (each chroma plane) i16 elements
+struct PlaneRows { size_t r0, r1, yrow, crow; bool chroma; };
+
+// The rows of n frames' planes in HOST memory, packed: host planes -> pinned staging -> ONE copy into the context's arena on
+// st (mixed_tables first: it waits for the last copy out of the staging).  py / pcb / pcr[f]: the address the plane's row 0
+// would have -- every address a lane forms lies in a strip or MCU row of its own window (zj_device.h: locate, halo_locate;
+// zj_scaled.h: scaled_block_loc), all of them uploaded; nullptr for the chroma planes of a frame without.
+int upload_host_planes(zj_ctx* c, size_t n, const PlaneRows* rows, const int16_t* const* y, const int16_t* const* cb,
+                       const int16_t* const* cr, const int16_t** py, const int16_t** pcb, const int16_t** pcr, hipStream_t st)
+{
+    size_t total = 0;
+    for (size_t f = 0; f < n; f++) total += (rows[f].r1 - rows[f].r0) * (rows[f].yrow + (rows[f].chroma ? 2 * rows[f].crow : 0)) * 2;
+    if (total > c->mx_arena_cap) {
+        ZJ_HIP(c, hipStreamSynchronize(st));
+        if (c->mx_arena) { ZJ_HIP(c, hipFree(c->mx_arena)); c->mx_arena = nullptr; }
+        if (c->mx_stage) { ZJ_HIP(c, hipHostFree(c->mx_stage)); c->mx_stage = nullptr; }
+        c->mx_arena_cap = 0;
+        const size_t cap = total + total / 4 + 4096;
+        ZJ_HIP(c, hipHostMalloc(&c->mx_stage, cap, hipHostMallocDefault));
+        ZJ_HIP(c, hipMalloc(&c->mx_arena, cap));
+        c->mx_arena_cap = cap;
+    }
+    size_t at = 0; // i16 elements into staging and arena alike
+    for (size_t f = 0; f < n; f++) {
+        const PlaneRows& r = rows[f];
+        const int16_t* const src[3] = {y[f], r.chroma ? cb[f] : nullptr, r.chroma ? cr[f] : nullptr};
+        const int16_t** const dst[3] = {&py[f], &pcb[f], &pcr[f]};
+        for (int k = 0; k < 3; k++) {
+            const size_t row = k ? r.crow : r.yrow, len = (r.r1 - r.r0) * row;
+            *dst[k] = nullptr;
+            if (!src[k]) continue;
+            *dst[k] = (const int16_t*)((uintptr_t)c->mx_arena + 2 * at - 2 * r.r0 * row);
+            if (len) memcpy((int16_t*)c->mx_stage + at, src[k] + r.r0 * row, len * 2);
+            at += len;
+        }
+    }
+    if (at) ZJ_HIP(c, hipMemcpyAsync(c->mx_arena, c->mx_stage, at * 2, hipMemcpyHostToDevice, st));
+    return ZJ_OK;
+}
+
+// The tail of the zjint_*_mixed_host calls: the context stream synchronised (the caller's planes are free again); a
+// synchronise error is reported only when the call itself succeeded
+int mixed_host_end(zj_ctx* c, int rc)
+{
+    if (c && c->stream) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
+    }
+    return rc;
+}
+
 // The call behind both mixed entry points.  host_planes: y / cb / cr are the CPU walker's planes in host memory; the rows
 // each frame's window needs go into the context's arena, a group's uploads all queued before its launches (the planes must
 // stay as they are until the stream has run: the caller synchronises).  Otherwise they are device planes.
@@ -1535,6 +1619,7 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
     std::vector<uint8_t*> crops(nframes);
     std::vector<const int16_t*> py(nframes), pcb(nframes), pcr(nframes);
     MixedTables tabs;
+    std::vector<PlaneRows> rows;
     for (size_t g0 = 0, g1, bytes; g0 < nframes; g0 = g1) {
         g1 = rz_group_next(rzf.data(), nframes, g0, ch, chw, RZ_GROUP_CAP, place.data(), &bytes);
         for (size_t f = g0; f < g1; f++) crops[f] = buf + place[f].crop.off;
@@ -1542,42 +1627,17 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
         // (first: it waits until the copies out of the pinned staging, the planes' and the tables', have finished)
         if ((rc = mixed_tables(c, mixed_table_bytes(fr.data() + g0, ng)))) return rc;
         if (host_planes) {
-            // The rows each window needs (mixed_plane_rows), packed: host planes -> pinned staging -> ONE copy into the arena.
-            // A frame's plane address is the one its row 0 would have: every address a lane forms lies in a strip or MCU
-            // row of its own window (zj_device.h: locate, halo_locate; zj_scaled.h: scaled_block_loc), all of them uploaded.
-            size_t total = 0;
+            // the rows each window of the group needs (mixed_plane_rows)
+            rows.resize(ng);
             for (size_t f = g0; f < g1; f++) {
-                size_t r0, r1, yrow, crow;
-                mixed_plane_rows(&descs[f], fr[f], r0, r1, yrow, crow);
-                total += (r1 - r0) * (yrow + (fr[f].pl.out != OUT_GRAY ? 2 * crow : 0)) * 2;
+                PlaneRows& r = rows[f - g0];
+                mixed_plane_rows(&descs[f], fr[f], r.r0, r.r1, r.yrow, r.crow);
+                r.chroma = fr[f].pl.out != OUT_GRAY;
             }
-            if (total > c->mx_arena_cap) {
-                ZJ_HIP(c, hipStreamSynchronize(st));
-                if (c->mx_arena) { ZJ_HIP(c, hipFree(c->mx_arena)); c->mx_arena = nullptr; }
-                if (c->mx_stage) { ZJ_HIP(c, hipHostFree(c->mx_stage)); c->mx_stage = nullptr; }
-                c->mx_arena_cap = 0;
-                const size_t cap = total + total / 4 + 4096;
-                ZJ_HIP(c, hipHostMalloc(&c->mx_stage, cap, hipHostMallocDefault));
-                ZJ_HIP(c, hipMalloc(&c->mx_arena, cap));
-                c->mx_arena_cap = cap;
-            }
-            size_t at = 0; // i16 elements into staging and arena alike
-            for (size_t f = g0; f < g1; f++) {
-                size_t r0, r1, yrow, crow;
-                mixed_plane_rows(&descs[f], fr[f], r0, r1, yrow, crow);
-                const bool chroma = fr[f].pl.out != OUT_GRAY;
-                const int16_t* const src[3] = {d_y[f], chroma ? d_cb[f] : nullptr, chroma ? d_cr[f] : nullptr};
-                const int16_t** const dst[3] = {&py[f], &pcb[f], &pcr[f]};
-                for (int k = 0; k < 3; k++) {
-                    const size_t row = k ? crow : yrow, n = (r1 - r0) * row;
-                    *dst[k] = nullptr;
-                    if (!src[k]) continue;
-                    *dst[k] = (const int16_t*)((uintptr_t)c->mx_arena + 2 * at - 2 * r0 * row);
-                    if (n) memcpy((int16_t*)c->mx_stage + at, src[k] + r0 * row, n * 2);
-                    at += n;
-                }
-            }
-            if (at) ZJ_HIP(c, hipMemcpyAsync(c->mx_arena, c->mx_stage, at * 2, hipMemcpyHostToDevice, st));
+            // (a frame without chroma: its d_cb / d_cr entries are not read, and the arrays may be null)
+            if ((rc = upload_host_planes(c, ng, rows.data(), d_y + g0, d_cb ? d_cb + g0 : nullptr, d_cr ? d_cr + g0 : nullptr,
+                                         py.data() + g0, pcb.data() + g0, pcr.data() + g0, st)))
+                return rc;
         } else {
             for (size_t f = g0; f < g1; f++) {
                 const bool chroma = fr[f].pl.out != OUT_GRAY;
@@ -1587,24 +1647,20 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
         // the group's records: staging -> device table, then one launch per run
         mixed_fill_tables(descs + g0, fr.data() + g0, ng, py.data() + g0, pcb.data() + g0, pcr.data() + g0, crops.data() + g0,
                           (uint8_t*)c->mx_host, tabs);
-        if (c->mx_used) ZJ_HIP(c, hipStreamWaitEvent(st, c->mx_done, 0));
-        ZJ_HIP(c, hipMemcpyAsync(c->mx_dev, c->mx_host, tabs.bytes, hipMemcpyHostToDevice, st));
-        ZJ_HIP(c, hipEventRecord(c->mx_up, st));
-        c->mx_used = true;
-        const uint8_t* const tab = (const uint8_t*)c->mx_dev;
-        hipError_t e = hipSuccess;
-        if (tabs.zero.n) e = launch_crop_zero_mixed((const MixedZero*)(tab + tabs.zero.off), tabs.zero.n, tabs.zero.gx, tabs.zero.gy, st);
-        for (size_t i = 0; e == hipSuccess && i < tabs.crop.size(); i++) {
-            const MixedLaunch& l = tabs.crop[i];
-            e = launch_crop_mixed(l.hs, l.vs, l.out, (const CropParams*)(tab + l.off), l.n, l.gx, l.gy, st);
-        }
-        for (size_t i = 0; e == hipSuccess && i < tabs.scaled.size(); i++) {
-            const MixedLaunch& l = tabs.scaled[i];
-            e = launch_scaled_mixed(l.hs, l.vs, l.out, l.sl, (const ScaledParams*)(tab + l.off), l.n, l.gx, l.gy, st);
-        }
-        // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
-        (void)hipEventRecord(c->mx_done, st);
-        ZJ_HIP(c, e);
+        rc = mixed_submit(c, tabs.bytes, st, [&](const uint8_t* tab) {
+            hipError_t e = hipSuccess;
+            if (tabs.zero.n) e = launch_crop_zero_mixed((const MixedZero*)(tab + tabs.zero.off), tabs.zero.n, tabs.zero.gx, tabs.zero.gy, st);
+            for (size_t i = 0; e == hipSuccess && i < tabs.crop.size(); i++) {
+                const MixedLaunch& l = tabs.crop[i];
+                e = launch_crop_mixed(l.hs, l.vs, l.out, (const CropParams*)(tab + l.off), l.n, l.gx, l.gy, st);
+            }
+            for (size_t i = 0; e == hipSuccess && i < tabs.scaled.size(); i++) {
+                const MixedLaunch& l = tabs.scaled[i];
+                e = launch_scaled_mixed(l.hs, l.vs, l.out, l.sl, (const ScaledParams*)(tab + l.off), l.n, l.gx, l.gy, st);
+            }
+            return e;
+        });
+        if (rc) return rc;
         if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, warp, warp_q))) return rc;
     }
     return ZJ_OK;
@@ -1632,11 +1688,7 @@ int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t
     const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
                                             resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
                                             max_prescale_log2, orientation, nullptr);
-    if (c && c->stream) {
-        const hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
-    }
-    return rc;
+    return mixed_host_end(c, rc);
 }
 
 // Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_warped_batch_device): the mixed-geometry crops of several files'
@@ -1657,11 +1709,7 @@ int zjint_crops_warped_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t 
     rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
                                   resize_out(out_w, out_h, dtype, out_layout, scale, bias, nullptr, ZJ_RESIZE_BILINEAR, d_out), 0,
                                   orientation, nullptr, &wt, q);
-    if (c->stream) {
-        const hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
-    }
-    return rc;
+    return mixed_host_end(c, rc);
 }
 
 /* ---- crop windows into a normalised tensor, no resize ------------------------------ */
@@ -1685,12 +1733,7 @@ int crop_tensor_args(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const un
     const int ch = resize_channels(d);
     if (!resize_elem_bytes(dtype) || (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC)) return ZJ_ERR_ARG;
     if ((uintptr_t)d_out % (uintptr_t)resize_elem_bytes(dtype)) return ZJ_ERR_ARG;
-    for (int k = 0; k < 3; k++) {
-        const float sc = scale && k < ch ? scale[k] : 1.f, bi = bias && k < ch ? bias[k] : 0.f;
-        if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
-        s[k] = sc * (1.f / 65536.f); // (resize_out_args: exact)
-        b[k] = bi;
-    }
+    if (!kernel_factors(scale, bias, ch, s, b)) return ZJ_ERR_ARG;
     int rc = make_crop_plan(d, w, h, 0, pl, cp);
     if (rc) return rc;
     if (!(img_bytes = crop_tensor_len(ch, w, h, dtype))) return ZJ_ERR_ARG;
@@ -1716,28 +1759,22 @@ int crop_tensor_submit(zj_ctx* c, const std::vector<CropTensorParams>& recs, con
     if (rc) return rc;
     memcpy(c->mx_host, recs.data(), rb);
     if (zb) memcpy((uint8_t*)c->mx_host + rb, zeros.data(), zb);
-    if (c->mx_used) ZJ_HIP(c, hipStreamWaitEvent(st, c->mx_done, 0));
-    ZJ_HIP(c, hipMemcpyAsync(c->mx_dev, c->mx_host, rb + zb, hipMemcpyHostToDevice, st));
-    ZJ_HIP(c, hipEventRecord(c->mx_up, st));
-    c->mx_used = true;
-    const uint8_t* const tab = (const uint8_t*)c->mx_dev;
-    hipError_t e = hipSuccess;
-    if (!zeros.empty()) {
-        int rows = 0, frames = 0;
-        for (const CropTensorZero& z : zeros) {
-            if (z.h - z.rmin > rows) rows = z.h - z.rmin;
-            if (z.nframes > frames) frames = z.nframes;
+    return mixed_submit(c, rb + zb, st, [&](const uint8_t* tab) {
+        hipError_t e = hipSuccess;
+        if (!zeros.empty()) {
+            int rows = 0, frames = 0;
+            for (const CropTensorZero& z : zeros) {
+                if (z.h - z.rmin > rows) rows = z.h - z.rmin;
+                if (z.nframes > frames) frames = z.nframes;
+            }
+            e = launch_crop_tensor_zero((const CropTensorZero*)(tab + rb), (int)zeros.size(), rows, frames, st);
         }
-        e = launch_crop_tensor_zero((const CropTensorZero*)(tab + rb), (int)zeros.size(), rows, frames, st);
-    }
-    for (size_t i = 0; e == hipSuccess && i < runs.size(); i++) {
-        const CropTensorRun& r = runs[i];
-        e = launch_crop_tensor(r.hs, r.vs, r.out, (const CropTensorParams*)tab + r.first, r.n, r.shift, r.gx, r.gy, st);
-    }
-    // (recorded whether or not a launch failed: the table may be in use by the ones that went out)
-    (void)hipEventRecord(c->mx_done, st);
-    ZJ_HIP(c, e);
-    return ZJ_OK;
+        for (size_t i = 0; e == hipSuccess && i < runs.size(); i++) {
+            const CropTensorRun& r = runs[i];
+            e = launch_crop_tensor(r.hs, r.vs, r.out, (const CropTensorParams*)tab + r.first, r.n, r.shift, r.gx, r.gy, st);
+        }
+        return e;
+    });
 }
 
 // frames [0, nframes) of ONE geometry, checked: one record per SCATTER_MAX frames, all of them one launch, with the
@@ -1795,42 +1832,16 @@ int crops_tensor_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframe
     if (rc) return rc;
     std::vector<const int16_t*> py(nframes), pcb(nframes), pcr(nframes);
     if (host_planes) {
-        std::vector<size_t> r0(nframes), r1(nframes), yrow(nframes), crow(nframes);
-        size_t total = 0;
+        // the strips each window needs
+        std::vector<PlaneRows> rows(nframes);
         for (size_t f = 0; f < nframes; f++) {
-            const Plan& pl = pls[f];
             int s0, s1, k0, k1;
-            crop_window(&descs[f], pl, cps[f], origins[2 * f], origins[2 * f + 1], s0, s1, k0, k1);
-            r0[f] = (size_t)s0; r1[f] = (size_t)s1;
-            yrow[f] = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8); crow[f] = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
-            total += (r1[f] - r0[f]) * (yrow[f] + (pl.out != OUT_GRAY ? 2 * crow[f] : 0)) * 2;
+            crop_window(&descs[f], pls[f], cps[f], origins[2 * f], origins[2 * f + 1], s0, s1, k0, k1);
+            rows[f].r0 = (size_t)s0; rows[f].r1 = (size_t)s1;
+            plan_strip_elems(pls[f], rows[f].yrow, rows[f].crow);
+            rows[f].chroma = pls[f].out != OUT_GRAY;
         }
-        if (total > c->mx_arena_cap) {
-            ZJ_HIP(c, hipStreamSynchronize(st));
-            if (c->mx_arena) { ZJ_HIP(c, hipFree(c->mx_arena)); c->mx_arena = nullptr; }
-            if (c->mx_stage) { ZJ_HIP(c, hipHostFree(c->mx_stage)); c->mx_stage = nullptr; }
-            c->mx_arena_cap = 0;
-            const size_t cap = total + total / 4 + 4096;
-            ZJ_HIP(c, hipHostMalloc(&c->mx_stage, cap, hipHostMallocDefault));
-            ZJ_HIP(c, hipMalloc(&c->mx_arena, cap));
-            c->mx_arena_cap = cap;
-        }
-        size_t at = 0; // i16 elements into staging and arena alike
-        for (size_t f = 0; f < nframes; f++) {
-            const bool chroma = pls[f].out != OUT_GRAY;
-            const int16_t* const src[3] = {y[f], chroma ? cb[f] : nullptr, chroma ? cr[f] : nullptr};
-            const int16_t** const dst[3] = {&py[f], &pcb[f], &pcr[f]};
-            for (int k = 0; k < 3; k++) {
-                const size_t row = k ? crow[f] : yrow[f], n = (r1[f] - r0[f]) * row;
-                *dst[k] = nullptr;
-                if (!src[k]) continue;
-                // (the address the plane's row 0 would have: every address a lane forms lies in a strip of its window)
-                *dst[k] = (const int16_t*)((uintptr_t)c->mx_arena + 2 * at - 2 * r0[f] * row);
-                if (n) memcpy((int16_t*)c->mx_stage + at, src[k] + r0[f] * row, n * 2);
-                at += n;
-            }
-        }
-        if (at) ZJ_HIP(c, hipMemcpyAsync(c->mx_arena, c->mx_stage, at * 2, hipMemcpyHostToDevice, st));
+        if ((rc = upload_host_planes(c, nframes, rows.data(), y, cb, cr, py.data(), pcb.data(), pcr.data(), st))) return rc;
     } else {
         for (size_t f = 0; f < nframes; f++) {
             const bool chroma = pls[f].out != OUT_GRAY;
@@ -1881,11 +1892,7 @@ int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t 
 {
     const int rc = crops_tensor_mixed_impl(c, descs, nframes, y, cb, cr, true, origins, w, h, dtype, out_layout, scale, bias, flip,
                                            d_out, nullptr);
-    if (c && c->stream) {
-        const hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == ZJ_OK && e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); return ZJ_ERR_HIP; }
-    }
-    return rc;
+    return mixed_host_end(c, rc);
 }
 
 int zj_decode_crops_tensor_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* const* d_y,
@@ -1926,7 +1933,8 @@ int zjint_crop_tensor_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y,
     if (!planes_on_device) {
         int s0, s1, k0, k1;
         crop_window(d, pl, cp, x, yy, s0, s1, k0, k1);
-        const size_t yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8), crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+        size_t yrow, crow;
+        plan_strip_elems(pl, yrow, crow);
         if ((rc = upload_plane_rows(c, pl, chroma, y, cb, cr, (size_t)s0, (size_t)s1, yrow, crow, p))) return rc;
     }
     const uint8_t fl = flip ? 1 : 0;
@@ -2229,12 +2237,7 @@ int zj_to_tensor_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, unsigne
     if (!E || (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC)) return ZJ_ERR_ARG;
     if ((uintptr_t)d_out % (uintptr_t)E) return ZJ_ERR_ARG; // (the kernel's blocks are counted from element boundaries)
     ToTensorParams p{};
-    for (int k = 0; k < 3; k++) {
-        const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
-        if (!finite_f32(sc) || !finite_f32(bi)) return ZJ_ERR_ARG;
-        p.scale[k] = sc * (1.f / 65536.f); // (resize_out_args: exact)
-        p.bias[k] = bi;
-    }
+    if (!kernel_factors(scale, bias, channels, p.scale, p.bias)) return ZJ_ERR_ARG;
     const unsigned row = w * (unsigned)in_channels;
     std::vector<unsigned> pitch(n);
     for (size_t f = 0; f < n; f++) {

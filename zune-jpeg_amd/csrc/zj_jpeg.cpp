@@ -36,6 +36,9 @@
 #include "zj_rzgroup.h"
 #include "zj_warp_fixed.h"
 #include "zj_huff.h"
+// the internal calls of the pixel path, weak here: this file is also built without them (zj_internal.h)
+#define ZJINT_DECL __attribute__((weak))
+#include "zj_internal.h"
 
 namespace {
 
@@ -2913,55 +2916,6 @@ int zj_decoder_scan_blob(const zj_decoder* d, const void** blob, size_t* len)
     return ZJ_OK;
 }
 
-// library-internal (zj_api.cpp): crop windows from host or device planes, the entropy stage alone, an all-zero window.
-// Weak: the front-end's CPU-only builds (the sanitizer and fuzz harnesses, which stub the GPU calls) link without them.
-__attribute__((weak)) int zjint_crop_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
-                     int planes_on_device, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch);
-__attribute__((weak)) int zjint_scan_to_planes(zj_ctx* c, const zj_frame_desc* d, const void* blob, size_t blob_bytes,
-                                              const int16_t* planes[3], unsigned* status_bits);
-__attribute__((weak)) int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy, unsigned w, unsigned h, uint8_t* d_out, unsigned out_pitch);
-// ... and the resized crop's buffer and resize
-__attribute__((weak)) int zjint_resize_scratch(zj_ctx* c, size_t bytes, uint8_t** p);
-__attribute__((weak)) int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout,
-                                           unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
-                                           const float* bias, int flip, int filter, void* d_out);
-// ... and one image turned to its displayed form
-__attribute__((weak)) int zjint_scratch_idle(zj_ctx* c, size_t bytes, uint8_t** p);
-__attribute__((weak)) int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, int o,
-                                           uint8_t* d_out);
-// ... and one plane expanded to an RGB image with R = G = B
-__attribute__((weak)) int zjint_gray_to_rgb_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int out_layout, uint8_t* d_out);
-// ... and one image combined in place with one plane, (a * k + 127) / 255
-__attribute__((weak)) int zjint_cmyk_to_rgb_one(zj_ctx* c, uint8_t* a, const uint8_t* k, unsigned w, unsigned h, int layout, int inverted);
-
-// ... and the resized crops of several files' planes in host memory, each of its own geometry
-__attribute__((weak)) int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
-                                                         const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
-                                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
-                                                         const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
-                                                         const uint8_t* orientation, void* d_out);
-
-// ... and the reduced-size decode of one frame's window
-__attribute__((weak)) int zjint_scaled_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
-                                             int planes_on_device, int scale_log2, unsigned x, unsigned yy, unsigned w, unsigned h,
-                                             uint8_t* d_out, unsigned out_pitch);
-
-// ... and one u8 image converted into a tensor image at its own size
-__attribute__((weak)) int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int in_channels, int channels,
-                                              int dtype, int out_layout, const float* scale, const float* bias, int flip, void* d_out);
-
-// ... and one u8 image warped into a tensor image under six integers (w == 0: no image, all fill)
-__attribute__((weak)) int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, const int64_t q[6],
-                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
-                                         const float* bias, const uint8_t* fill, int edge, void* d_out);
-
-// ... and the mixed-geometry crops of several files' host planes, each group's images warped
-__attribute__((weak)) int zjint_crops_warped_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
-                                                        const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
-                                                        const int64_t* q, unsigned out_w, unsigned out_h, int dtype, int out_layout,
-                                                        const float* scale, const float* bias, const uint8_t* fill, int edge,
-                                                        const uint8_t* orientation, void* d_out);
-
 // The last stage of a single-file call that passes its u8 image through the context's buffer: the resize to out_w x out_h
 // (the resized-crop calls), or the conversion at the image's own size (to_tensor: the crop-tensor calls, DESIGN.md 3.15;
 // out_w x out_h is then the displayed window itself and filter is not used).  Everything in front of it -- the buffer's
@@ -2983,10 +2937,6 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
 
 static const char* const kFourOnlyResized = "four-component files are finished by the resized-crop calls only (ZJ_FLAG_CMYK_TO_RGB)";
 static const char* const kOddOnlyResized = "files of this sampling or stored RGB are finished by the resized-crop calls only (ZJ_FLAG_ANY_SAMPLING)";
-// ... and three component planes box-replicated and converted into one image
-__attribute__((weak)) int zjint_planes_to_rgb_one(zj_ctx* c, const uint8_t* const planes[3], unsigned w, unsigned h,
-                                                  const uint8_t ratios[6], const uint8_t phases[6], int stored_rgb, int layout,
-                                                  uint8_t* d_out);
 
 static int finish_impl(zj_decoder* d, zj_ctx* ctx, uint8_t* out, size_t out_cap, size_t* out_len, int on_device)
 {
@@ -3154,11 +3104,6 @@ int zj_decoder_finish_pixels_crop_device(zj_decoder* d, zj_ctx* ctx, unsigned x,
     return finish_window(d, ctx, false, 0, x, y, w, h, d_out, out_cap, out_pitch, out_len);
 }
 
-// ... and one frame's window converted straight into a tensor image
-__attribute__((weak)) int zjint_crop_tensor_frame(zj_ctx* c, const zj_frame_desc* d, const int16_t* y, const int16_t* cb, const int16_t* cr,
-                                                  int planes_on_device, unsigned x, unsigned yy, unsigned w, unsigned h, int dtype,
-                                                  int out_layout, const float* scale, const float* bias, int flip, void* d_out);
-
 // The window x, y, w, h of the decoder's last file converted into one image of a normalised tensor, not resized:
 // zj_decode_crops_tensor_device's contract over the crop file path (finish_window: with a scan prepared for the device the
 // planes in HBM, otherwise the CPU walker's planes uploaded by the strips the window needs).
@@ -3231,11 +3176,72 @@ int zj_decoder_finish_pixels_crop_tensor_oriented_device(zj_decoder* d, zj_ctx* 
                               d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
 }
 
-// ... and the crop tensors of several files' planes in host memory, each of its own geometry
-__attribute__((weak)) int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
-                                                        const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins,
-                                                        unsigned w, unsigned h, int dtype, int out_layout, const float* scale,
-                                                        const float* bias, const uint8_t* flip, void* d_out);
+// The one body of the file-batch calls: n prepared decoders, each with its own file of any size,
+// into one dense output of n images.  The files the mixed-geometry launches take ("mixed") go there, consecutive ones in one
+// call; every other file through its single-file call, which gives the same bytes and sets the decoder's error text.
+// rcs[k]: file k's status; a failed file leaves its image untouched and stops no other.
+// What a call hands in:
+//   chan_len        bytes of one channel of one image by the call's own length rule; 0: no such output
+//   classify(b, k)  FILE_MIXED (b.fds[k] then holds the file's descriptor), FILE_SINGLE, or the status of a file the checks
+//                   refuse, which reaches no call
+//   single(b, k)    the single-file call for file k
+//   run(b, k0, k1)  the *_mixed_host call over the files [k0, k1)
+// The files that go alone are finished while the batch is classified, the runs afterwards.
+namespace {
+struct FileBatch {
+    size_t img = 0; // bytes of one image; 0: every file's own call says why
+    std::vector<zj_frame_desc> fds;
+    std::vector<const int16_t*> py, pcb, pcr;
+    std::vector<uint8_t> ori; // each file's orientation as the call applies it: 1 until classify says otherwise
+};
+enum FileRoute { FILE_MIXED = 1000, FILE_SINGLE }; // what classify returns where it returns no status (none has these values)
+
+extern "C++" { // (a template has no C linkage)
+template <class Classify, class Single, class Run>
+int file_batch(zj_decoder* const* ds, size_t n, size_t chan_len, size_t out_cap, int* rcs, Classify classify, Single single, Run run)
+{
+    const zj_decoder* first = nullptr;
+    for (size_t k = 0; k < n; k++) {
+        if (!ds[k]) continue;
+        if (!first) first = ds[k];
+        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
+    }
+    if (!first) return ZJ_ERR_ARG;
+    zj_frame_desc fd0{};
+    fd0.out_colorspace = (uint32_t)first->out_colorspace;
+    FileBatch b;
+    b.img = (size_t)zj::resize_channels(&fd0) * chan_len; // (a gray file that does not become RGB: 1 channel of its slot)
+    if (b.img && out_cap / b.img < n) return ZJ_ERR_ARG;
+    b.fds.resize(n);
+    b.py.resize(n); b.pcb.resize(n); b.pcr.resize(n);
+    b.ori.assign(n, 1);
+    std::vector<char> mixed(n, 0);
+    for (size_t k = 0; k < n; k++) {
+        const zj_decoder* const d = ds[k];
+        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
+        const int what = classify(b, k);
+        if (what == FILE_SINGLE) { rcs[k] = single(b, k); continue; }
+        if (what != FILE_MIXED) { rcs[k] = what; continue; }
+        b.py[k] = d->comps[0].coef;
+        b.pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; b.pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
+        rcs[k] = ZJ_OK;
+        mixed[k] = 1;
+    }
+    for (size_t k0 = 0; k0 < n;) {
+        if (!mixed[k0]) { k0++; continue; }
+        size_t k1 = k0;
+        while (k1 < n && mixed[k1]) k1++;
+        const int rc = run(b, k0, k1);
+        // a run that fails: each of its files through its own call, which names the failing one.  A run refused for its
+        // arguments has launched nothing; after a HIP error in a later launch group the earlier groups' images are written
+        // again, with the same bytes
+        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(b, k) : (int)ZJ_OK;
+        k0 = k1;
+    }
+    return ZJ_OK;
+}
+} // extern "C++"
+} // namespace
 
 // Several prepared files of any sizes into one crop tensor, every window w x h (after 3.10's batch call).  The
 // files the CPU walker decoded go through the mixed-geometry launches, consecutive ones in one call; a decoder with a scan
@@ -3250,58 +3256,31 @@ static int crop_tensor_batch(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const
     using namespace zj;
     if (!ds || !n || !ctx || !origins || !d_out || !rcs) return ZJ_ERR_ARG;
     if (!zjint_crops_tensor_mixed_host || !zjint_crop_tensor_frame) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
-    const zj_decoder* first = nullptr;
-    for (size_t k = 0; k < n; k++) {
-        if (!ds[k]) continue;
-        if (!first) first = ds[k];
-        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
-    }
-    if (!first) return ZJ_ERR_ARG;
-    zj_frame_desc fd0{};
-    fd0.out_colorspace = (uint32_t)first->out_colorspace;
-    // (0: every file's own call says why)
-    const size_t img = (size_t)resize_channels(&fd0) * w * h * (size_t)resize_elem_bytes(dtype);
-    if (img && out_cap / img < n) return ZJ_ERR_ARG;
-    const auto single = [&](size_t k) {
-        return (oriented ? zj_decoder_finish_pixels_crop_tensor_oriented_device : zj_decoder_finish_pixels_crop_tensor_device)(
-            ds[k], ctx, origins[2 * k], origins[2 * k + 1], w, h, dtype, out_layout, scale, bias, flip ? flip[k] : 0,
-            (uint8_t*)d_out + k * img, img, nullptr);
-    };
-    std::vector<zj_frame_desc> fds(n);
-    std::vector<const int16_t*> py(n), pcb(n), pcr(n);
-    std::vector<char> mixed(n, 0);
-    for (size_t k = 0; k < n; k++) {
-        zj_decoder* const d = ds[k];
-        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
-        // what the mixed call does not take, or the single-file call refuses with a text of its own: that call
-        if (!img || !d->seen_sof || d->err_code || d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd ||
-            (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE) || (oriented && d->orientation >= 2 && d->orientation <= 8)) {
-            rcs[k] = single(k);
-            continue;
-        }
-        fill_info(d, nullptr, &fds[k]);
-        const WindowLayout g = window_layout(&fds[k], w, h, 0);
-        if (fds[k].out_layout != ZJ_LAYOUT_HWC || !window_inside(g, origins[2 * k], origins[2 * k + 1], w, h, fds[k].width, fds[k].height)) {
-            rcs[k] = single(k);
-            continue;
-        }
-        py[k] = d->comps[0].coef;
-        pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
-        rcs[k] = ZJ_OK;
-        mixed[k] = 1;
-    }
-    for (size_t k0 = 0; k0 < n;) {
-        if (!mixed[k0]) { k0++; continue; }
-        size_t k1 = k0;
-        while (k1 < n && mixed[k1]) k1++;
-        const int rc = zjint_crops_tensor_mixed_host(ctx, fds.data() + k0, k1 - k0, py.data() + k0, pcb.data() + k0, pcr.data() + k0,
-                                                     origins + 2 * k0, w, h, dtype, out_layout, scale, bias, flip ? flip + k0 : nullptr,
-                                                     (uint8_t*)d_out + k0 * img);
-        // a run that is refused has launched nothing: each of its files through its own call, which names the failing one
-        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(k) : (int)ZJ_OK;
-        k0 = k1;
-    }
-    return ZJ_OK;
+    return file_batch(
+        ds, n, (size_t)w * h * (size_t)resize_elem_bytes(dtype), out_cap, rcs,
+        [&](FileBatch& b, size_t k) -> int {
+            const zj_decoder* const d = ds[k];
+            // what the mixed call does not take, or the single-file call refuses with a text of its own: that call
+            if (!b.img || !d->seen_sof || d->err_code || d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd ||
+                (d->ncomp == 1 && d->out_colorspace != ZJ_CS_GRAYSCALE) || (oriented && d->orientation >= 2 && d->orientation <= 8))
+                return FILE_SINGLE;
+            fill_info(d, nullptr, &b.fds[k]);
+            const WindowLayout g = window_layout(&b.fds[k], w, h, 0);
+            if (b.fds[k].out_layout != ZJ_LAYOUT_HWC ||
+                !window_inside(g, origins[2 * k], origins[2 * k + 1], w, h, b.fds[k].width, b.fds[k].height))
+                return FILE_SINGLE;
+            return FILE_MIXED;
+        },
+        [&](const FileBatch& b, size_t k) {
+            return (oriented ? zj_decoder_finish_pixels_crop_tensor_oriented_device : zj_decoder_finish_pixels_crop_tensor_device)(
+                ds[k], ctx, origins[2 * k], origins[2 * k + 1], w, h, dtype, out_layout, scale, bias, flip ? flip[k] : 0,
+                (uint8_t*)d_out + k * b.img, b.img, nullptr);
+        },
+        [&](const FileBatch& b, size_t k0, size_t k1) {
+            return zjint_crops_tensor_mixed_host(ctx, b.fds.data() + k0, k1 - k0, b.py.data() + k0, b.pcb.data() + k0, b.pcr.data() + k0,
+                                                 origins + 2 * k0, w, h, dtype, out_layout, scale, bias, flip ? flip + k0 : nullptr,
+                                                 (uint8_t*)d_out + k0 * b.img);
+        });
 }
 
 int zj_decoder_finish_pixels_crop_tensor_batch_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* origins,
@@ -3639,68 +3618,41 @@ int zj_decoder_finish_pixels_warped_batch_device(zj_decoder* const* ds, size_t n
     using namespace zj;
     if (!ds || !n || !ctx || !matrices || !d_out || !rcs) return ZJ_ERR_ARG;
     if (!zjint_crops_warped_mixed_host || !zjint_warp_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
-    const zj_decoder* first = nullptr;
-    for (size_t k = 0; k < n; k++) {
-        if (!ds[k]) continue;
-        if (!first) first = ds[k];
-        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
-    }
-    if (!first) return ZJ_ERR_ARG;
-    zj_frame_desc fd0{};
-    fd0.out_colorspace = (uint32_t)first->out_colorspace;
-    const size_t img = resized_len(resize_channels(&fd0), out_w, out_h, dtype); // (0: every file's own call says why)
-    if (img && out_cap / img < n) return ZJ_ERR_ARG;
-    const auto single = [&](size_t k) {
-        return zj_decoder_finish_pixels_warped_device(ds[k], ctx, matrices + 6 * k, apply_orientation, out_w, out_h, dtype, out_layout,
-                                                      scale, bias, fill, edge, (uint8_t*)d_out + k * img, img, nullptr);
-    };
-    std::vector<zj_frame_desc> fds(n);
-    std::vector<const int16_t*> py(n), pcb(n), pcr(n);
-    std::vector<uint8_t> ori(n, 1);
-    std::vector<unsigned> wins(4 * n, 0);
-    std::vector<int64_t> qs(6 * n, 0);
-    std::vector<char> mixed(n, 0);
-    for (size_t k = 0; k < n; k++) {
-        zj_decoder* const d = ds[k];
-        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
-        int64_t q[6];
-        const bool plain = img && (edge == ZJ_WARP_FILL || edge == ZJ_WARP_REPLICATE) && warp_fixed(matrices + 6 * k, q) &&
-                           d->seen_sof && !d->err_code && d->coef_valid && !d->scan_ready && d->out_layout != ZJ_LAYOUT_CHW;
-        if (!plain) { rcs[k] = single(k); continue; }
-        const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
-        fill_info(d, nullptr, &fds[k]);
-        unsigned dw = 0, dh = 0;
-        unsigned* const win = wins.data() + 4 * k;
-        if (!orient_size(o, (unsigned)fds[k].width, (unsigned)fds[k].height, &dw, &dh) || dw == 0 || dh == 0 || dw > 65535 || dh > 65535) {
-            rcs[k] = single(k);
-            continue;
-        }
-        warp_source_window(q, dw, dh, out_w, out_h, edge == ZJ_WARP_REPLICATE, win, qs.data() + 6 * k);
-        if (win[2] == 0) { rcs[k] = single(k); continue; } // (all fill: nothing to decode)
-        unsigned x = win[0], y = win[1], w = win[2], h = win[3]; // (resized_checks turns its copy into the stored window)
-        int ch = 0;
-        if ((rcs[k] = resized_checks(d, 0, x, y, w, h, out_w, out_h, dtype, ZJ_RESIZE_BILINEAR, img, nullptr, o, fds[k], ch))) continue;
-        if (d->ncomp == 4 || d->odd || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
-        py[k] = d->comps[0].coef;
-        pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
-        ori[k] = (uint8_t)o;
-        mixed[k] = 1;
-    }
-    for (size_t k0 = 0; k0 < n;) {
-        if (!mixed[k0]) { k0++; continue; }
-        size_t k1 = k0;
-        while (k1 < n && mixed[k1]) k1++;
-        const int rc = zjint_crops_warped_mixed_host(ctx, fds.data() + k0, k1 - k0, py.data() + k0, pcb.data() + k0, pcr.data() + k0,
-                                                     wins.data() + 4 * k0, qs.data() + 6 * k0, out_w, out_h, dtype, out_layout, scale,
-                                                     bias, fill, edge, apply_orientation ? ori.data() + k0 : nullptr,
-                                                     (uint8_t*)d_out + k0 * img);
-        // a run that fails: each of its files through its own call, which names the failing one.  A run refused for its
-        // arguments has launched nothing; after a HIP error in a later launch group the earlier groups' images are written
-        // again, with the same bytes
-        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(k) : (int)ZJ_OK;
-        k0 = k1;
-    }
-    return ZJ_OK;
+    std::vector<unsigned> wins(4 * n, 0); // per file: the source window in displayed pixels
+    std::vector<int64_t> qs(6 * n, 0);    // ... and the six integers relative to it
+    return file_batch(
+        ds, n, resized_len(1, out_w, out_h, dtype), out_cap, rcs,
+        [&](FileBatch& b, size_t k) -> int {
+            zj_decoder* const d = ds[k];
+            int64_t q[6];
+            const bool plain = b.img && (edge == ZJ_WARP_FILL || edge == ZJ_WARP_REPLICATE) && warp_fixed(matrices + 6 * k, q) &&
+                               d->seen_sof && !d->err_code && d->coef_valid && !d->scan_ready && d->out_layout != ZJ_LAYOUT_CHW;
+            if (!plain) return FILE_SINGLE;
+            const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
+            zj_frame_desc& fd = b.fds[k];
+            fill_info(d, nullptr, &fd);
+            unsigned dw = 0, dh = 0;
+            unsigned* const win = wins.data() + 4 * k;
+            if (!orient_size(o, (unsigned)fd.width, (unsigned)fd.height, &dw, &dh) || dw == 0 || dh == 0 || dw > 65535 || dh > 65535)
+                return FILE_SINGLE;
+            warp_source_window(q, dw, dh, out_w, out_h, edge == ZJ_WARP_REPLICATE, win, qs.data() + 6 * k);
+            if (win[2] == 0) return FILE_SINGLE; // (all fill: nothing to decode)
+            unsigned x = win[0], y = win[1], w = win[2], h = win[3]; // (resized_checks turns its copy into the stored window)
+            int ch = 0;
+            if (const int rc = resized_checks(d, 0, x, y, w, h, out_w, out_h, dtype, ZJ_RESIZE_BILINEAR, b.img, nullptr, o, fd, ch)) return rc;
+            if (d->ncomp == 4 || d->odd || (zero_output(&fd) && !gray_to_rgb(&fd))) return FILE_SINGLE;
+            b.ori[k] = (uint8_t)o;
+            return FILE_MIXED;
+        },
+        [&](const FileBatch& b, size_t k) {
+            return zj_decoder_finish_pixels_warped_device(ds[k], ctx, matrices + 6 * k, apply_orientation, out_w, out_h, dtype, out_layout,
+                                                          scale, bias, fill, edge, (uint8_t*)d_out + k * b.img, b.img, nullptr);
+        },
+        [&](const FileBatch& b, size_t k0, size_t k1) {
+            return zjint_crops_warped_mixed_host(ctx, b.fds.data() + k0, k1 - k0, b.py.data() + k0, b.pcb.data() + k0, b.pcr.data() + k0,
+                                                 wins.data() + 4 * k0, qs.data() + 6 * k0, out_w, out_h, dtype, out_layout, scale, bias,
+                                                 fill, edge, apply_orientation ? b.ori.data() + k0 : nullptr, (uint8_t*)d_out + k0 * b.img);
+        });
 }
 
 // Several prepared files of any sizes into one resized-crop tensor.  The files the CPU walker decoded go
@@ -3716,57 +3668,33 @@ int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, si
     using namespace zj;
     if (!ds || !n || !ctx || !windows || !d_out || !rcs) return ZJ_ERR_ARG;
     if (!zjint_crops_resized_mixed_host) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
-    const zj_decoder* first = nullptr;
-    for (size_t k = 0; k < n; k++) {
-        if (!ds[k]) continue;
-        if (!first) first = ds[k];
-        if (ds[k]->out_colorspace != first->out_colorspace || ds[k]->out_layout != first->out_layout) return ZJ_ERR_ARG;
-    }
-    if (!first) return ZJ_ERR_ARG;
-    zj_frame_desc fd0{};
-    fd0.out_colorspace = (uint32_t)first->out_colorspace;
-    const size_t img = resized_len(resize_channels(&fd0), out_w, out_h, dtype); // (0: every file's own call says why; a gray
-                                                                                // file that does not become RGB: 1 channel)
-    if (img && out_cap / img < n) return ZJ_ERR_ARG;
-    const auto single = [&](size_t k) {
-        const unsigned* const w = windows + 4 * k;
-        void* const o = (uint8_t*)d_out + k * img;
-        const int fl = flip ? flip[k] : 0;
-        return apply_orientation ? zj_decoder_finish_pixels_resized_crop_oriented_device(ds[k], ctx, w[0], w[1], w[2], w[3], out_w, out_h, dtype, out_layout, scale, bias, fl, filter, max_prescale_log2, o, img, nullptr)
-                                 : zj_decoder_finish_pixels_resized_crop_prescaled_device(ds[k], ctx, w[0], w[1], w[2], w[3], out_w, out_h, dtype, out_layout, scale, bias, fl, filter, max_prescale_log2, o, img, nullptr);
-    };
-    std::vector<zj_frame_desc> fds(n);
-    std::vector<const int16_t*> py(n), pcb(n), pcr(n);
-    std::vector<uint8_t> ori(n, 1);
-    std::vector<char> mixed(n, 0);
-    for (size_t k = 0; k < n; k++) {
-        zj_decoder* const d = ds[k];
-        if (!d) { rcs[k] = ZJ_ERR_ARG; continue; }
-        if (max_prescale_log2 < 0 || max_prescale_log2 > 3 || !img) { rcs[k] = single(k); continue; }
-        const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
-        unsigned x = windows[4 * k], y = windows[4 * k + 1], w = windows[4 * k + 2], h = windows[4 * k + 3];
-        const int kk = prescale_pick(w, h, out_w, out_h, max_prescale_log2);
-        int ch = 0;
-        if ((rcs[k] = resized_checks(d, kk, x, y, w, h, out_w, out_h, dtype, filter, img, nullptr, o, fds[k], ch))) continue;
-        if (d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd || (zero_output(&fds[k]) && !gray_to_rgb(&fds[k]))) { rcs[k] = single(k); continue; }
-        py[k] = d->comps[0].coef;
-        pcb[k] = d->ncomp == 3 ? d->comps[1].coef : nullptr; pcr[k] = d->ncomp == 3 ? d->comps[2].coef : nullptr;
-        ori[k] = (uint8_t)o;
-        mixed[k] = 1;
-    }
-    for (size_t k0 = 0; k0 < n;) {
-        if (!mixed[k0]) { k0++; continue; }
-        size_t k1 = k0;
-        while (k1 < n && mixed[k1]) k1++;
-        const int rc = zjint_crops_resized_mixed_host(ctx, fds.data() + k0, k1 - k0, py.data() + k0, pcb.data() + k0, pcr.data() + k0,
-                                                      windows + 4 * k0, out_w, out_h, dtype, out_layout, scale, bias,
-                                                      flip ? flip + k0 : nullptr, filter, max_prescale_log2,
-                                                      apply_orientation ? ori.data() + k0 : nullptr, (uint8_t*)d_out + k0 * img);
-        // a run that is refused has launched nothing: each of its files through its own call, which names the failing one
-        for (size_t k = k0; k < k1; k++) rcs[k] = rc ? single(k) : (int)ZJ_OK;
-        k0 = k1;
-    }
-    return ZJ_OK;
+    return file_batch(
+        ds, n, resized_len(1, out_w, out_h, dtype), out_cap, rcs,
+        [&](FileBatch& b, size_t k) -> int {
+            zj_decoder* const d = ds[k];
+            if (max_prescale_log2 < 0 || max_prescale_log2 > 3 || !b.img) return FILE_SINGLE;
+            const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
+            unsigned x = windows[4 * k], y = windows[4 * k + 1], w = windows[4 * k + 2], h = windows[4 * k + 3];
+            const int kk = prescale_pick(w, h, out_w, out_h, max_prescale_log2);
+            zj_frame_desc& fd = b.fds[k];
+            int ch = 0;
+            if (const int rc = resized_checks(d, kk, x, y, w, h, out_w, out_h, dtype, filter, b.img, nullptr, o, fd, ch)) return rc;
+            if (d->scan_ready || !d->coef_valid || d->ncomp == 4 || d->odd || (zero_output(&fd) && !gray_to_rgb(&fd))) return FILE_SINGLE;
+            b.ori[k] = (uint8_t)o;
+            return FILE_MIXED;
+        },
+        [&](const FileBatch& b, size_t k) {
+            const unsigned* const w = windows + 4 * k;
+            return (apply_orientation ? zj_decoder_finish_pixels_resized_crop_oriented_device : zj_decoder_finish_pixels_resized_crop_prescaled_device)(
+                ds[k], ctx, w[0], w[1], w[2], w[3], out_w, out_h, dtype, out_layout, scale, bias, flip ? flip[k] : 0, filter, max_prescale_log2,
+                (uint8_t*)d_out + k * b.img, b.img, nullptr);
+        },
+        [&](const FileBatch& b, size_t k0, size_t k1) {
+            return zjint_crops_resized_mixed_host(ctx, b.fds.data() + k0, k1 - k0, b.py.data() + k0, b.pcb.data() + k0, b.pcr.data() + k0,
+                                                  windows + 4 * k0, out_w, out_h, dtype, out_layout, scale, bias, flip ? flip + k0 : nullptr,
+                                                  filter, max_prescale_log2, apply_orientation ? b.ori.data() + k0 : nullptr,
+                                                  (uint8_t*)d_out + k0 * b.img);
+        });
 }
 
 // The whole displayed image of the prepared file, tight, in the decoder's colour space and layout: orientation 1 decodes

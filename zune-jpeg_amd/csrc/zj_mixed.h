@@ -122,7 +122,7 @@ inline void mixed_plane_rows(const zj_frame_desc* d, const MixedFrame& m, size_t
     int s0, s1, k0, k1;
     crop_window(d, pl, m.cp, m.stored[0], m.stored[1], s0, s1, k0, k1);
     r0 = (size_t)s0; r1 = (size_t)s1;
-    yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8); crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+    plan_strip_elems(pl, yrow, crow);
 }
 
 // One launch of a group: the n records at byte offset `off` of the table, its grid the widest ranges over them.  (The

@@ -130,6 +130,14 @@ inline int make_plan(const zj_frame_desc* d, Plan& pl)
     return ZJ_OK;
 }
 
+// i16 elements of one strip of the plan's luma plane (yrow) and of each chroma plane (crow): a plane is its strips one after
+// the other, so strips [s0, s1) are the elements [s0 * row, s1 * row)
+inline void plan_strip_elems(const Plan& pl, size_t& yrow, size_t& crow)
+{
+    yrow = (size_t)pl.mcu_x * pl.hs * 64 * (pl.strip_rows / 8);
+    crow = (size_t)pl.mcu_x * 64 * (pl.strip_rows / (8 * pl.vs));
+}
+
 // Byte ranges of one frame's output that the strips never reach (rows below the last complete strip,
 // Q6: the reference leaves them 0).  HWC: one range; CHW: one per plane.  Returns the number of ranges.
 inline int uncovered_ranges(const zj_frame_desc* d, const Plan& pl, size_t off[3], size_t len[3])

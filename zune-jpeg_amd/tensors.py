@@ -230,6 +230,58 @@ def decode_crops_to_normalized_tensor(ctx, desc, frames, origins, size, dtype=No
     return out
 
 
+def _prepare_files(ctx, blobs, options, workers, decoders):
+    """(decs, prepared) of the decode_files_* calls: one Decoder per blob, made as needed and kept in `decoders`, each
+    prepared on a pool of at most 16 threads; the first file that fails raises DecodeError naming its index."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .host import DecodeError, Decoder
+    n = len(blobs)
+    decs = decoders if decoders is not None else []
+    while len(decs) < n:
+        decs.append(Decoder(options, ctx))
+    decs = decs[:n]
+
+    def prep(k):
+        try:
+            return decs[k].prepare(blobs[k])
+        except DecodeError as e:
+            return e
+
+    nw = max(1, min(int(workers), 16, n))
+    if nw > 1:
+        with ThreadPoolExecutor(nw) as ex:
+            prepared = list(ex.map(prep, range(n)))
+    else:
+        prepared = [prep(k) for k in range(n)]
+    for k, r in enumerate(prepared):
+        if isinstance(r, DecodeError):
+            raise DecodeError(r.status, f"file {k}: {r.text}")
+    return decs, prepared
+
+
+def _files_out(ctx, decs, what, size, dtype, layout, mean, std, stream):
+    """(out, scale, bias) of the decode_files_* calls: the dense output of len(decs) images allocated under `stream` (None:
+    torch's current) and that stream synchronised -- the allocator may hand out a block that work queued on it still uses,
+    and the batch calls run on the context's stream."""
+    import torch
+    channels = ColorSpace(decs[0]._out_cs).num_components()
+    if channels not in (1, 3):
+        raise ValueError(f"{what} have 1 or 3 channels")
+    scale, bias = normalize_factors(channels, mean, std)
+    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    out = _resized_out(len(decs), channels, size, dtype, layout, dev, s)
+    s.synchronize()
+    return out, scale, bias
+
+
+def _raise_first_failed(decs, rcs):
+    from .host import DecodeError
+    for k, rc in enumerate(rcs):
+        if rc:
+            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+
+
 def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
                                    antialias=False, interpolation="bilinear", max_prescale=1, apply_orientation=False,
                                    options=None, workers=1, stream=None, decoders=None):
@@ -257,8 +309,7 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
     the stream the output is allocated under, synchronised before the call writes it."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from .host import DecodeError, Decoder, finish_pixels_resized_crop_batch, oriented_size, resize_filter, scale_log2
+    from .host import finish_pixels_resized_crop_batch, oriented_size, resize_filter, scale_log2
     scale_log2(max_prescale)
     resize_filter(antialias, interpolation)
     dtype = torch.bfloat16 if dtype is None else dtype
@@ -266,26 +317,7 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     n = len(blobs)
     if n == 0 or (windows is not None and len(windows) != n):
         raise ValueError("one window per file, at least one file")
-    decs = decoders if decoders is not None else []
-    while len(decs) < n:
-        decs.append(Decoder(options, ctx))
-    decs = decs[:n]
-
-    def prep(k):
-        try:
-            return decs[k].prepare(blobs[k])
-        except DecodeError as e:
-            return e
-
-    nw = max(1, min(int(workers), 16, n))
-    if nw > 1:
-        with ThreadPoolExecutor(nw) as ex:
-            prepared = list(ex.map(prep, range(n)))
-    else:
-        prepared = [prep(k) for k in range(n)]
-    for k, r in enumerate(prepared):
-        if isinstance(r, DecodeError):
-            raise DecodeError(r.status, f"file {k}: {r.text}")
+    decs, prepared = _prepare_files(ctx, blobs, options, workers, decoders)
     wins = []
     for k in range(n):
         w = windows[k] if windows is not None else None
@@ -296,22 +328,12 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
                 iw, ih = oriented_size(decs[k].orientation, iw, ih)
             w = (0, 0, iw, ih)
         wins.append(w)
-    channels = ColorSpace(decs[0]._out_cs).num_components()
-    if channels not in (1, 3):
-        raise ValueError("resized outputs have 1 or 3 channels")
-    scale, bias = normalize_factors(channels, mean, std)
-    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
-    cur = torch.cuda.current_stream(dev)
-    s = stream if stream is not None else cur
-    out = _resized_out(n, channels, size, dtype, layout, dev, s)
-    s.synchronize()  # (the allocator may hand out a block that work queued on `s` still uses: the batch runs on the context's stream)
+    out, scale, bias = _files_out(ctx, decs, "resized outputs", size, dtype, layout, mean, std, stream)
     rcs = finish_pixels_resized_crop_batch(decs, ctx, wins, size[0], size[1], code,
                                            TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(),
                                            out.numel() * out.element_size(), scale, bias, flips, antialias, max_prescale,
                                            apply_orientation, interpolation)
-    for k, rc in enumerate(rcs):
-        if rc:
-            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+    _raise_first_failed(decs, rcs)
     return out
 
 
@@ -329,33 +351,13 @@ def decode_files_cropped_to_tensor(ctx, blobs, origins, size, dtype=None, layout
     options' flags, gray files shown as RGB, CMYK / YCCK files and files of another sampling or stored RGB are decoded here
     as well, through their u8 image and to_normalized_tensor's stage; a prescale is decode_files_resized_to_tensor's."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from .host import DecodeError, Decoder, finish_pixels_crop_tensor_batch, oriented_size
+    from .host import finish_pixels_crop_tensor_batch, oriented_size
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
     n = len(blobs)
     if n == 0 or (origins is not None and len(origins) != n) or (flips is not None and len(flips) != n):
         raise ValueError("one origin (and flip) per file, at least one file")
-    decs = decoders if decoders is not None else []
-    while len(decs) < n:
-        decs.append(Decoder(options, ctx))
-    decs = decs[:n]
-
-    def prep(k):
-        try:
-            return decs[k].prepare(blobs[k])
-        except DecodeError as e:
-            return e
-
-    nw = max(1, min(int(workers), 16, n))
-    if nw > 1:
-        with ThreadPoolExecutor(nw) as ex:
-            prepared = list(ex.map(prep, range(n)))
-    else:
-        prepared = [prep(k) for k in range(n)]
-    for k, r in enumerate(prepared):
-        if isinstance(r, DecodeError):
-            raise DecodeError(r.status, f"file {k}: {r.text}")
+    decs, prepared = _prepare_files(ctx, blobs, options, workers, decoders)
     w, h = size
     if origins is None:
         for k in range(n):
@@ -366,21 +368,11 @@ def decode_files_cropped_to_tensor(ctx, blobs, origins, size, dtype=None, layout
             if shown != (w, h):
                 raise ValueError(f"file {k} is {shown[0]}x{shown[1]}, not {w}x{h}: give origins")
         origins = [(0, 0)] * n
-    channels = ColorSpace(decs[0]._out_cs).num_components()
-    if channels not in (1, 3):
-        raise ValueError("crop tensors have 1 or 3 channels")
-    scale, bias = normalize_factors(channels, mean, std)
-    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
-    cur = torch.cuda.current_stream(dev)
-    s = stream if stream is not None else cur
-    out = _resized_out(n, channels, size, dtype, layout, dev, s)
-    s.synchronize()  # (the allocator may hand out a block that work queued on `s` still uses: the files run on the context's stream)
+    out, scale, bias = _files_out(ctx, decs, "crop tensors", size, dtype, layout, mean, std, stream)
     rcs = finish_pixels_crop_tensor_batch(decs, ctx, origins, w, h, code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC,
                                           out.data_ptr(), out.numel() * out.element_size(), scale, bias, flips,
                                           apply_orientation=bool(apply_orientation))
-    for k, rc in enumerate(rcs):
-        if rc:
-            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+    _raise_first_failed(decs, rcs)
     return out
 
 
@@ -724,47 +716,17 @@ def decode_files_warped_to_tensor(ctx, blobs, matrices, size, dtype=None, layout
     decode_files_resized_to_tensor.  The batch call runs on the context's stream and has finished when it returns; a file
     that fails raises DecodeError naming its index (its image is untouched, the others are decoded)."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from .host import DecodeError, Decoder, finish_pixels_warped_batch, warp_edge
+    from .host import finish_pixels_warped_batch, warp_edge
     warp_edge(edge)
     dtype = torch.bfloat16 if dtype is None else dtype
     code = _resize_dtype(dtype)
     n = len(blobs)
     if n == 0 or len(matrices) != n:
         raise ValueError("one matrix per file, at least one file")
-    decs = decoders if decoders is not None else []
-    while len(decs) < n:
-        decs.append(Decoder(options, ctx))
-    decs = decs[:n]
-
-    def prep(k):
-        try:
-            return decs[k].prepare(blobs[k])
-        except DecodeError as e:
-            return e
-
-    nw = max(1, min(int(workers), 16, n))
-    if nw > 1:
-        with ThreadPoolExecutor(nw) as ex:
-            prepared = list(ex.map(prep, range(n)))
-    else:
-        prepared = [prep(k) for k in range(n)]
-    for k, r in enumerate(prepared):
-        if isinstance(r, DecodeError):
-            raise DecodeError(r.status, f"file {k}: {r.text}")
-    channels = ColorSpace(decs[0]._out_cs).num_components()
-    if channels not in (1, 3):
-        raise ValueError("warped outputs have 1 or 3 channels")
-    scale, bias = normalize_factors(channels, mean, std)
-    dev = torch.device("cuda", ctx.device) if hasattr(ctx, "device") else torch.device("cuda")
-    cur = torch.cuda.current_stream(dev)
-    s = stream if stream is not None else cur
-    out = _resized_out(n, channels, size, dtype, layout, dev, s)
-    s.synchronize()  # (the files run on the context's stream)
+    decs, prepared = _prepare_files(ctx, blobs, options, workers, decoders)
+    out, scale, bias = _files_out(ctx, decs, "warped outputs", size, dtype, layout, mean, std, stream)
     rcs = finish_pixels_warped_batch(decs, ctx, matrices, size[0], size[1], code, TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC,
                                      out.data_ptr(), out.numel() * out.element_size(), scale, bias, fill, edge,
                                      bool(apply_orientation))
-    for k, rc in enumerate(rcs):
-        if rc:
-            raise DecodeError(rc, f"file {k}: " + lib().zj_decoder_error(decs[k]._d).decode(errors="replace"))
+    _raise_first_failed(decs, rcs)
     return out
