@@ -338,6 +338,23 @@ extern "C" {
                                                               bias: *const f32, flip: *const u8, filter: c_int,
                                                               max_prescale_log2: c_int, apply_orientation: c_int,
                                                               d_out: *mut c_void, out_cap: usize, rcs: *mut c_int) -> c_int;
+    pub fn zj_color_fixed(matrix: *const f64, fixed: *mut i32) -> c_int;
+    pub fn zj_color_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                           layout: c_int, matrices: *const f64, d_out: *const *mut u8, out_pitch: *const c_uint,
+                           stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_resized_mixed_colored_device(ctx: *mut zj_ctx, descs: *const zj_frame_desc, nframes: usize,
+                                                        d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                                        windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                        out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                                        filter: c_int, max_prescale_log2: c_int, orientation: *const u8,
+                                                        color: *const f64, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_resized_crop_batch_colored_device(ds: *const *mut zj_decoder, n: usize, ctx: *mut zj_ctx,
+                                                                      windows: *const c_uint, out_w: c_uint, out_h: c_uint,
+                                                                      dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                                      bias: *const f32, flip: *const u8, filter: c_int,
+                                                                      max_prescale_log2: c_int, apply_orientation: c_int,
+                                                                      color: *const f64, d_out: *mut c_void, out_cap: usize,
+                                                                      rcs: *mut c_int) -> c_int;
     pub fn zj_decoder_orientation(d: *const zj_decoder) -> c_int;
     pub fn zj_decoder_adobe_transform(d: *const zj_decoder) -> c_int;
     pub fn zj_decoder_stored_rgb(d: *const zj_decoder) -> c_int;

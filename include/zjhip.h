@@ -602,6 +602,40 @@ ZJ_API int zj_decode_crops_resized_mixed_device(zj_ctx *ctx, const zj_frame_desc
                                                 unsigned out_h, int dtype, int out_layout, const float *scale,
                                                 const float *bias, const uint8_t *flip, int filter, int max_prescale_log2,
                                                 const uint8_t *orientation, void *d_out, void *stream);
+/* ---- colour matrices: brightness, contrast, saturation, hue, grayscale, a channel order -----------------
+ * A colour matrix is 12 doubles, m[4c + k]: m[c][0..2] multiply R, G, B in output channel c, m[c][3] is an offset in grey
+ * levels.  zj_color_fixed gives its 12 integers, q = floor(m 65536 + 1/2) evaluated in doubles, and refuses (ZJ_ERR_ARG) a NULL
+ * pointer, an entry that is not finite, |m[c][0..2]| > 16 and |m[c][3]| > 4096.  Runs without a device.
+ * DEFINITION, for a pixel of bytes (R, G, B):  v = q[c][0] R + q[c][1] G + q[c][2] B + q[c][3],
+ * out[c] = clamp((v + 32768) >> 16, 0, 255) with an arithmetic shift; |v| < 2^31 under the limits above.  The identity gives
+ * the input bytes, a permutation matrix the permuted bytes, three rows (0.299, 0.587, 0.114, 0) Pillow's convert("L"). */
+ZJ_API int zj_color_fixed(const double matrix[12], int32_t fixed[12]);
+/* n 3-channel u8 images in device memory, each of its own size and under its own matrix (matrices: 12 doubles per image) ->
+ * 3-channel u8 images of the same sizes by the definition above.  in_wh (width and height, 1..65535); `layout` of the input
+ * and of the output, ZJ_LAYOUT_HWC or ZJ_LAYOUT_CHW (three planes, pitch x height apart); in_pitch, out_pitch bytes between
+ * rows (NULL or 0: tight; the padding is never read or written).  Any addresses and pitches.  d_out[i] == d_in[i] with equal
+ * pitches is allowed (a lane reads its run before it writes it); any other overlap of an output with an input is the
+ * caller's error.  One launch per 48 images (76 bytes of kernel arguments each), whatever their sizes.  Asynchronous on
+ * `stream` (NULL: the context's); every argument, the matrices included, is checked first and nothing is launched after an
+ * error. */
+ZJ_API int zj_color_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                           int layout, const double *matrices /* 12 per image */, uint8_t *const *d_out,
+                           const unsigned *out_pitch, void *stream);
+/* zj_decode_crops_resized_mixed_device with frame f's image under the matrix color[12f .. 12f + 11] in front of the resize.
+ * DEFINITION: image f equals zj_resize_filtered_device applied to zj_color_device of EXACTLY the u8 image the call without
+ * `color` resizes -- after the crop or reduced decode, the turn and the gray expand, in place in the context's buffer.  The
+ * flip, the filter and the normalisation are untouched.  color NULL: the call IS zj_decode_crops_resized_mixed_device, byte
+ * for byte and launch for launch; frames whose integers are the identity's are left out of the colour launch (one per 48
+ * frames of a group).  All matrices are checked before anything is launched (ZJ_ERR_ARG: one zj_color_fixed refuses).  The
+ * output colour space must have three components: ZJ_CS_GRAYSCALE with a non-NULL color is ZJ_ERR_UNSUPPORTED. */
+ZJ_API int zj_decode_crops_resized_mixed_colored_device(zj_ctx *ctx, const zj_frame_desc *descs /* [nframes] */, size_t nframes,
+                                                        const int16_t *const *d_y, const int16_t *const *d_cb,
+                                                        const int16_t *const *d_cr, const unsigned *windows, unsigned out_w,
+                                                        unsigned out_h, int dtype, int out_layout, const float *scale,
+                                                        const float *bias, const uint8_t *flip, int filter,
+                                                        int max_prescale_log2, const uint8_t *orientation,
+                                                        const double *color /* 12 per frame, or NULL */, void *d_out,
+                                                        void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -862,6 +896,20 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder *const 
                                                               const float *bias, const uint8_t *flip, int filter,
                                                               int max_prescale_log2, int apply_orientation, void *d_out,
                                                               size_t out_cap, int *rcs);
+/* zj_decoder_finish_pixels_resized_crop_batch_device with file k's image under the colour matrix color[12k .. 12k + 11]
+ * (zj_color_fixed's definition) in front of the resize: the matrix acts on exactly the u8 image the call
+ * without it resizes -- after the crop or reduced decode, the turn, the gray expand (ZJ_FLAG_GRAY_TO_RGB), the CMYK combine
+ * (ZJ_FLAG_CMYK_TO_RGB) and the plane combine (ZJ_FLAG_ANY_SAMPLING) -- in place.  color NULL: the call above.  A matrix
+ * zj_color_fixed refuses gives rcs[k] = ZJ_ERR_ARG and the decoder's error text; that file's image is untouched and the
+ * others are decoded.  A decoder whose output has one channel: ZJ_ERR_UNSUPPORTED for that file.  n = 1 is the single-file
+ * call. */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_batch_colored_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx,
+                                                                      const unsigned *windows, unsigned out_w, unsigned out_h,
+                                                                      int dtype, int out_layout, const float *scale,
+                                                                      const float *bias, const uint8_t *flip, int filter,
+                                                                      int max_prescale_log2, int apply_orientation,
+                                                                      const double *color /* 12 per file, or NULL */,
+                                                                      void *d_out, size_t out_cap, int *rcs);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

@@ -16,4 +16,5 @@ from .host import (  # noqa: F401
     crop_out_len, resized_out_len, crop_tensor_out_len, scaled_size, scaled_crop_out_len, oriented_size, orient_window, DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8, TENSOR_NCHW, TENSOR_NHWC,
     RESIZE_BILINEAR, RESIZE_BILINEAR_AA, RESIZE_BICUBIC_AA, resize_filter,
     WARP_FILL, WARP_REPLICATE, warp_edge, warp_fixed, warp_source_window, finish_pixels_warped_batch,
+    color_fixed,
 )

@@ -20,6 +20,7 @@
 #include "zj_orient_launch.h"
 #include "zj_expand_launch.h"
 #include "zj_cmyk_launch.h"
+#include "zj_color_launch.h"
 #include "zj_planes_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
@@ -1026,6 +1027,38 @@ int cmyk_launches(zj_ctx* c, size_t n, const uint8_t* const* a, const uint8_t* c
     return ZJ_OK;
 }
 
+// images [0, n) under their colour matrices, launches of up to COLOR_BATCH images; wh: w, h pairs, the pitches
+// resolved, q: 12 integers per image (color_fixed)
+int color_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int chw,
+                   const int32_t* q, uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
+{
+    ColorParams p{};
+    for (size_t f0 = 0; f0 < n; f0 += COLOR_BATCH) {
+        const int m = (int)(n - f0 < (size_t)COLOR_BATCH ? n - f0 : (size_t)COLOR_BATCH);
+        p.nimg = m;
+        for (int i = 0; i < COLOR_BATCH; i++) {
+            const size_t f = f0 + i;
+            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
+            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
+            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
+            p.in_pitch[i] = i < m ? in_pitch[f] : 0;
+            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
+            for (int k = 0; k < 12; k++) p.q[i][k] = i < m ? q[12 * f + k] : 0;
+        }
+        ZJ_HIP(c, launch_color(chw, p, st));
+    }
+    return ZJ_OK;
+}
+
+// the 12 integers of each of n matrices of doubles, 12 each
+int color_matrices(const double* matrices, size_t n, std::vector<int32_t>& q)
+{
+    q.resize(12 * n);
+    for (size_t f = 0; f < n; f++)
+        if (!color_fixed(matrices + 12 * f, q.data() + 12 * f)) return ZJ_ERR_ARG;
+    return ZJ_OK;
+}
+
 // images [0, n) -> their three component planes box-replicated and converted, launches of up to PLANES_BATCH
 // images; wh: w, h pairs of the outputs, geo: planes_geo of the three components, pitch: three per image, all resolved
 int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t* const* p1, const uint8_t* const* p2,
@@ -1059,11 +1092,13 @@ int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t
 // warp_q[6f .. 6f + 5].  Only the warp's calls have frames of an EMPTY window (w == 0: the output sees nothing of the frame,
 // fill mode): such a frame has no crop, passes no stage in front of the warp -- the `p.in.w` below -- and gets a record no
 // lane loads from (warp_launches).  The resized calls refuse an empty window before they come here.
+// color_q (nullptr: none): frame f's image, the one the last stage reads, passes the colour stage in place
+// under the integers color_q[12f .. 12f + 11] first; a frame with the identity's integers is left out of the launch.
 int warp_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const int64_t* q,
                   const ResizeOut& o, const WarpTail& t, size_t first, hipStream_t st);
 
 int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g0, size_t g1, uint8_t* buf, const ResizeOut& o,
-                    hipStream_t st, const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr)
+                    hipStream_t st, const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr, const int32_t* color_q = nullptr)
 {
     // the images of one stage of the group, gathered
     struct Stage {
@@ -1082,7 +1117,8 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
     const size_t ng = g1 - g0;
     std::vector<const uint8_t*> in(ng);
     std::vector<unsigned> wh(2 * ng), pitch(ng);
-    Stage turn, turn_gray, expand; // (the gray frames of a 3-channel call are turned as the 1-channel images they still are)
+    Stage turn, turn_gray, expand, color; // (the gray frames of a 3-channel call are turned as the 1-channel images they still are)
+    std::vector<int32_t> cq;
     for (size_t f = g0; f < g1; f++) {
         const RzPlace& p = place[f];
         in[f - g0] = buf + p.in.off;
@@ -1090,6 +1126,10 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
         pitch[f - g0] = p.in.pitch;
         if (p.turned) (p.expand ? turn_gray : turn).add(buf, p.crop, p.gray, fr[f].o);
         if (p.expand && p.in.w) expand.add(buf, p.gray, p.in, 1);
+        if (color_q && p.in.w && !color_is_identity(color_q + 12 * f)) {
+            color.add(buf, p.in, p.in, 1);
+            cq.insert(cq.end(), color_q + 12 * f, color_q + 12 * f + 12);
+        }
     }
     int rc;
     if (!turn.in.empty() && (rc = orient_launches(c, turn.in.size(), turn.in.data(), turn.wh.data(), turn.ip.data(), o.ch, o.chw,
@@ -1101,6 +1141,9 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
         return rc;
     if (!expand.in.empty() && (rc = expand_launches(c, expand.in.size(), expand.in.data(), expand.wh.data(), expand.ip.data(),
                                                     o.chw, expand.out.data(), expand.op.data(), st)))
+        return rc;
+    if (!color.in.empty() && (rc = color_launches(c, color.in.size(), color.in.data(), color.wh.data(), color.ip.data(), o.chw,
+                                                  cq.data(), color.out.data(), color.op.data(), st)))
         return rc;
     if ((rc = warp ? warp_launches(c, ng, in.data(), wh.data(), pitch.data(), warp_q + 6 * g0, o, *warp, g0, st)
                    : resize_launches(c, ng, in.data(), wh.data(), pitch.data(), o, g0, st)))
@@ -1593,7 +1636,7 @@ int mixed_host_end(zj_ctx* c, int rc)
 int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
                              const int16_t* const* d_cb, const int16_t* const* d_cr, bool host_planes, const unsigned* windows,
                              ResizeOut ro, int max_prescale_log2, const uint8_t* orientation, void* stream,
-                             const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr)
+                             const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr, const int32_t* color_q = nullptr)
 {
     if (!resize_filter_valid(ro.filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
     if (!c || !descs || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
@@ -1607,6 +1650,7 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
     int rc = mixed_check_frames(descs, nframes, windows, orientation, ch ? resize_out_args(ro, ch) : 0, ro.out_w, ro.out_h,
                                 max_prescale_log2, planes, fr.data());
     if (rc) return rc;
+    if (color_q && ch != 3) return ZJ_ERR_UNSUPPORTED; // (a colour matrix maps three channels)
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const bool chw = ro.chw = ch == 3 && descs[0].out_layout == ZJ_LAYOUT_CHW; // (of RGB: make_plan refuses YCbCr planes)
@@ -1661,7 +1705,7 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
             return e;
         });
         if (rc) return rc;
-        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, warp, warp_q))) return rc;
+        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, warp, warp_q, color_q))) return rc;
     }
     return ZJ_OK;
 }
@@ -1688,6 +1732,38 @@ int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t
     const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
                                             resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
                                             max_prescale_log2, orientation, nullptr);
+    return mixed_host_end(c, rc);
+}
+
+/* ---- colour matrices in the resized-crop calls ------------------------------------ */
+// color (nullptr: zj_decode_crops_resized_mixed_device itself): 12 doubles per frame, all checked before anything is launched
+int zj_decode_crops_resized_mixed_colored_device(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
+                                                 const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                                 unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                                 const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                                 const uint8_t* orientation, const double* color, void* d_out, void* stream)
+{
+    std::vector<int32_t> q;
+    if (color) {
+        if (nframes == 0 || nframes > (size_t)1 << 20) return ZJ_ERR_ARG;
+        if (const int rc = color_matrices(color, nframes, q)) return rc;
+    }
+    return crops_resized_mixed_impl(c, descs, nframes, d_y, d_cb, d_cr, false, windows,
+                                    resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
+                                    max_prescale_log2, orientation, stream, nullptr, nullptr, color ? q.data() : nullptr);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_resized_crop_batch_colored_device): zjint_crops_resized_mixed_host
+// with file f's image under the integers color_q[12f .. 12f + 11] (nullptr: none) in front of the resize
+int zjint_crops_resized_mixed_colored_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                           const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
+                                           unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                           const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                           const uint8_t* orientation, const int32_t* color_q, void* d_out)
+{
+    const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
+                                            resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
+                                            max_prescale_log2, orientation, nullptr, nullptr, nullptr, color_q);
     return mixed_host_end(c, rc);
 }
 
@@ -2056,6 +2132,57 @@ int zjint_cmyk_to_rgb_one(zj_ctx* c, uint8_t* a, const uint8_t* k, unsigned w, u
     const uint8_t inv = inverted ? 1 : 0;
     const uint8_t* ca = a;
     int rc = zj_cmyk_to_rgb_device(c, 1, &ca, &k, wh, nullptr, nullptr, layout, &inv, &a, nullptr, nullptr);
+    if (rc) return rc;
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    if ((rc = resize_scratch_done(c, c->stream))) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
+/* ---- colour matrices -------------------------------------------------------------- */
+int zj_color_fixed(const double matrix[12], int32_t fixed[12])
+{
+    if (!matrix || !fixed) return ZJ_ERR_ARG;
+    int32_t q[12];
+    if (!color_fixed(matrix, q)) return ZJ_ERR_ARG;
+    for (int k = 0; k < 12; k++) fixed[k] = q[k];
+    return ZJ_OK;
+}
+
+int zj_color_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int layout,
+                    const double* matrices, uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !matrices || !d_out) return ZJ_ERR_ARG;
+    if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    const unsigned bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> ip(n), op(n);
+    for (size_t f = 0; f < n; f++) {
+        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
+        if (!d_in[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        ip[f] = in_pitch && in_pitch[f] ? in_pitch[f] : w * bpp;
+        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
+        if (ip[f] < w * bpp || op[f] < w * bpp || ip[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
+    }
+    std::vector<int32_t> q;
+    int rc = color_matrices(matrices, n, q);
+    if (rc) return rc;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return color_launches(c, n, d_in, in_wh, ip.data(), layout == ZJ_LAYOUT_CHW, q.data(), d_out, op.data(), st);
+}
+
+// Library-internal (zj_jpeg.cpp: the single-file resized crop under a colour matrix): one tight image mapped in place under the
+// 12 integers q on the context stream (the identity's: nothing is launched); the context's crop buffer counts as read by it;
+// synchronised
+int zjint_color_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int layout, const int32_t q[12])
+{
+    if (!c || !img || !q || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+    if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
+    if (color_is_identity(q)) return ZJ_OK;
+    const unsigned wh[2] = {w, h}, pitch = layout == ZJ_LAYOUT_CHW ? w : 3 * w;
+    const uint8_t* in = img;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    int rc = color_launches(c, 1, &in, wh, &pitch, layout == ZJ_LAYOUT_CHW, q, &img, &pitch, c->stream);
     if (rc) return rc;
     if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
     if ((rc = resize_scratch_done(c, c->stream))) return rc;

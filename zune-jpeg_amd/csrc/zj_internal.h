@@ -52,6 +52,8 @@ ZJINT_DECL int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, uns
 ZJINT_DECL int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, const int64_t q[6], unsigned out_w,
                               unsigned out_h, int dtype, int out_layout, const float* scale, const float* bias, const uint8_t* fill,
                               int edge, void* d_out);
+// ... and one image mapped in place under the 12 integers of a colour matrix (the identity's: no launch)
+ZJINT_DECL int zjint_color_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int layout, const int32_t q[12]);
 
 // The mixed-geometry calls over several files' planes in HOST memory, each file of its own geometry; d_out: the first file's
 // image, the others behind it.  Synchronous: the planes may be reused when they return.
@@ -61,6 +63,12 @@ ZJINT_DECL int zjint_crops_resized_mixed_host(zj_ctx* c, const zj_frame_desc* de
                                               unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                               const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
                                               const uint8_t* orientation, void* d_out);
+// ... the resized crops with file f's image under the integers color_q[12f .. 12f + 11] first (nullptr: none)
+ZJINT_DECL int zjint_crops_resized_mixed_colored_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                                      const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
+                                                      unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                                      const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                                      const uint8_t* orientation, const int32_t* color_q, void* d_out);
 // ... the crop tensors, every window w x h
 ZJINT_DECL int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
                                              const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins, unsigned w,

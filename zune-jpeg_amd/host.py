@@ -202,6 +202,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decoder_finish_pixels_crop_tensor_batch_oriented_device",
     "zj_warp_fixed", "zj_warp_source_window", "zj_warp_device", "zj_decode_crops_warped_device",
     "zj_decoder_finish_pixels_warped_device", "zj_decoder_finish_pixels_warped_batch_device",
+    "zj_color_fixed", "zj_color_device", "zj_decode_crops_resized_mixed_colored_device",
+    "zj_decoder_finish_pixels_resized_crop_batch_colored_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -406,6 +408,13 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_batch_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int, vp,
                                                                      vp, vp, C.c_int, C.c_int, C.c_int, vp, sz,
                                                                      C.POINTER(C.c_int)]
+    L.zj_color_fixed.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.zj_color_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.zj_decode_crops_resized_mixed_colored_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
+                                                               C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.zj_decoder_finish_pixels_resized_crop_batch_colored_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                                             vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, sz,
+                                                                             C.POINTER(C.c_int)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -518,6 +527,34 @@ def warp_source_window(fixed, frame_w, frame_h, out_w, out_h, edge="fill"):
     sh = (C.c_int64 * 6)()
     _check(lib().zj_warp_source_window(q, frame_w, frame_h, out_w, out_h, warp_edge(edge), win, sh), "zj_warp_source_window")
     return tuple(int(v) for v in win), [int(v) for v in sh]
+
+
+IDENTITY_COLOR = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def color_fixed(matrix):
+    """The 12 integers floor(m * 65536 + 1/2) of a colour matrix, [3, 4] or 12 numbers (zj_color_fixed, DESIGN.md 3.17);
+    ZjError: an entry the colour stage refuses"""
+    m = (C.c_double * 12)(*_color_flat(matrix))
+    q = (C.c_int32 * 12)()
+    _check(lib().zj_color_fixed(m, q), "zj_color_fixed")
+    return [int(v) for v in q]
+
+
+def _color_flat(matrix):
+    flat = [float(v) for row in matrix for v in (row if hasattr(row, "__len__") else (row,))]
+    if len(flat) != 12:
+        raise ValueError("a colour matrix is [3, 4]: 12 numbers")
+    return flat
+
+
+def _colors(matrices, n):
+    """one colour matrix per image (None entries: the identity) as 12 n doubles; None: no colour"""
+    if matrices is None:
+        return None
+    if len(matrices) != n:
+        raise ValueError("one colour matrix per image")
+    return (C.c_double * (12 * n))(*[v for m in matrices for v in (IDENTITY_COLOR if m is None else _color_flat(m))])
 
 
 def _matrices(matrices, n):
@@ -808,6 +845,19 @@ class Context:
                                            pit(k_pitches), layout, inv, (C.c_void_p * n)(*d_out), pit(out_pitches), stream),
                "zj_cmyk_to_rgb_device", self._h)
 
+    def color_device(self, d_in, sizes, layout, matrices, d_out, in_pitches=None, out_pitches=None, stream=None):
+        """One 3-channel u8 image each under its own colour matrix (zj_color_device): d_in = device pointers,
+        sizes = one (w, h) each, layout LAYOUT_HWC or LAYOUT_CHW of the input and of the output, matrices = one [3, 4] each
+        (None: the identity), d_out = one device pointer each (d_in[i] itself with the same pitch: in place); pitches = bytes
+        between rows (None: tight).  Asynchronous on `stream`."""
+        n = len(d_in)
+        if len(sizes) != n or len(d_out) != n or matrices is None:
+            raise ValueError("one size, matrix and output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+        _check(lib().zj_color_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), layout, _colors(matrices, n),
+                                     (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_color_device", self._h)
+
     def planes_to_rgb_device(self, d_p0, d_p1, d_p2, sizes, ratios, layout, d_out, stored_rgb=False, pitches=None,
                              out_pitches=None, stream=None):
         """Three u8 component planes per image, each at its own resolution -> the 3-channel u8 image whose pixel (r, c) is
@@ -896,10 +946,12 @@ class Context:
 
     def decode_crops_resized_mixed_device(self, descs, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out,
                                           scale=None, bias=None, flips=None, stream=None, antialias=False, max_prescale=1,
-                                          orientations=None, interpolation="bilinear"):
+                                          orientations=None, interpolation="bilinear", colors=None):
         """Resized crop windows of frames of MIXED geometry (zj_decode_crops_resized_mixed_device): descs = one FrameDesc
         per frame (sizes, sampling, tables, flags and in_components their own; out_colorspace and out_layout the same in
         all); the other arguments as decode_crops_resized_device.  Image f equals that call's for frame f alone.
+        colors: one [3, 4] colour matrix per frame (None entries: the identity), the u8 image under it in front of the
+        resize (zj_decode_crops_resized_mixed_colored_device); None: today's call.
         Asynchronous on `stream`."""
         filt = resize_filter(antialias, interpolation)
         n = len(d_y)
@@ -908,6 +960,12 @@ class Context:
         arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
         win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
         ori = (C.c_uint8 * n)(*[int(o) for o in orientations]) if orientations is not None else None
+        if colors is not None:
+            _check(lib().zj_decode_crops_resized_mixed_colored_device(
+                self._h, (FrameDesc * n)(*descs), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w, out_h, dtype, out_layout,
+                _floats(scale), _floats(bias), _flips(flips, n), filt, scale_log2(max_prescale), ori, _colors(colors, n), d_out,
+                stream), "zj_decode_crops_resized_mixed_colored_device", self._h)
+            return
         _check(lib().zj_decode_crops_resized_mixed_device(self._h, (FrameDesc * n)(*descs), n, arr(d_y), arr(d_cb), arr(d_cr), win,
                                                           out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias),
                                                           _flips(flips, n), filt, scale_log2(max_prescale), ori, d_out, stream),
@@ -1354,11 +1412,13 @@ def finish_pixels_batch(decoders, ctx, outs=None, device_ptrs=None):
 
 def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
                                      flips=None, antialias=False, max_prescale=1, apply_orientation=False,
-                                     interpolation="bilinear"):
+                                     interpolation="bilinear", colors=None):
     """zj_decoder_finish_pixels_resized_crop_batch_device over Decoder objects that went through prepare() or
     decode_coefficients(), each with a file of its own size: windows = one (x, y, w, h) per decoder (displayed pixels with
     apply_orientation), image k left at device pointer d_out + k * resized_out_len.  Returns the list of statuses: image k
-    is Decoder.finish_pixels_resized_crop_device's for decoder k alone, a failed file's slot is untouched."""
+    is Decoder.finish_pixels_resized_crop_device's for decoder k alone, a failed file's slot is untouched.
+    colors: one [3, 4] colour matrix per decoder (None entries: the identity), each file's u8 image under its matrix in
+    front of the resize (zj_decoder_finish_pixels_resized_crop_batch_colored_device); None: no colour stage."""
     filt = resize_filter(antialias, interpolation)
     n = len(decoders)
     if len(windows) != n:
@@ -1366,6 +1426,12 @@ def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype
     dptr = (C.c_void_p * n)(*[d._d for d in decoders])
     win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
     rcs = (C.c_int * n)()
+    if colors is not None:
+        _check(lib().zj_decoder_finish_pixels_resized_crop_batch_colored_device(
+            dptr, n, ctx.handle, win, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias), _flips(flips, n), filt,
+            scale_log2(max_prescale), 1 if apply_orientation else 0, _colors(colors, n), d_out, cap, rcs),
+            "zj_decoder_finish_pixels_resized_crop_batch_colored_device", ctx.handle)
+        return list(rcs)
     _check(lib().zj_decoder_finish_pixels_resized_crop_batch_device(dptr, n, ctx.handle, win, out_w, out_h, dtype, out_layout,
                                                                     _floats(scale), _floats(bias), _flips(flips, n), filt,
                                                                     scale_log2(max_prescale), 1 if apply_orientation else 0,

@@ -154,7 +154,7 @@ def _on_stream(s, cur, tensors):
 
 def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
                                    flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,
-                                   interpolation="bilinear"):
+                                   interpolation="bilinear", color=None):
     """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
     per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
@@ -170,7 +170,11 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     One-component frames: desc.flags | FLAG_GRAY_TO_RGB with ColorSpace.RGB gives the image a viewer shows, R = G = B
     (DESIGN.md 3.11): the GRAYSCALE crop, turned, copied into three channels, then resized.  Without the flag a
     one-component descriptor that asks for RGB is refused (ZjError: not supported); ask for GRAYSCALE and get C = 1.  The
-    flag does nothing for three-component frames.  Stream and allocator rules as decode_to_tensor."""
+    flag does nothing for three-component frames.
+    color: one [3, 4] colour matrix per frame (color_matrix; None in a frame's place: the identity), applied to the u8 image
+    in front of the resize, clamped as an 8-bit image is; the call then goes through
+    zj_decode_crops_resized_mixed_colored_device with the descriptor repeated.  None (default): none.  Needs a
+    three-channel output.  Stream and allocator rules as decode_to_tensor."""
     import torch
     from .host import resize_filter, scale_log2
     scale_log2(max_prescale)
@@ -191,6 +195,15 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     out = _resized_out(n, channels, size, dtype, layout, dev, s)
     _on_stream(s, cur, [p for fr in frames for p in fr])
     ptr = lambda t: t.data_ptr() if t is not None else None
+    if color is not None:
+        if len(color) != n:
+            raise ValueError("one colour matrix per frame")
+        cbs = [ptr(fr[1]) for fr in frames]
+        ctx.decode_crops_resized_mixed_device([desc] * n, [ptr(fr[0]) for fr in frames], cbs if any(cbs) else None,
+                                              [ptr(fr[2]) for fr in frames] if any(cbs) else None, windows, ow, oh, code,
+                                              TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
+                                              s.cuda_stream, antialias, max_prescale, orientations, interpolation, colors=color)
+        return out
     ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
                                     [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
                                     TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
@@ -284,7 +297,7 @@ def _raise_first_failed(decs, rcs):
 
 def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
                                    antialias=False, interpolation="bilinear", max_prescale=1, apply_orientation=False,
-                                   options=None, workers=1, stream=None, decoders=None):
+                                   options=None, workers=1, stream=None, decoders=None, color=None):
     """JPEG files of ANY sizes -> ONE dense resized-crop tensor (zj_decoder_finish_pixels_resized_crop_batch_device,
     DESIGN.md 3.10): blobs = a list of bytes-like JPEG files, windows = one (x, y, w, h) per file (displayed pixels with
     apply_orientation; None, or None in a file's place: the whole displayed image), size = (out_w, out_h).  Returns
@@ -306,6 +319,9 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     images are the resize of the box-replicated, colour-converted component planes, never prescaled, each
     finished through its single-file call; WITHOUT the flag the first kind is refused when it is prepared (DecodeError
     naming its index) and a stored-RGB file with ids 1..3 is shown through YCbCr -> RGB, with wrong colours.
+    color: one [3, 4] colour matrix per file (color_matrix; None in a file's place: the identity): each file's finished u8
+    image -- gray, CMYK, odd-sampled and turned files included -- under its matrix in front of the resize, clamped as an
+    8-bit image is (zj_decoder_finish_pixels_resized_crop_batch_colored_device).  None (default): none.
     The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
     the stream the output is allocated under, synchronised before the call writes it."""
     import torch
@@ -332,7 +348,7 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     rcs = finish_pixels_resized_crop_batch(decs, ctx, wins, size[0], size[1], code,
                                            TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(),
                                            out.numel() * out.element_size(), scale, bias, flips, antialias, max_prescale,
-                                           apply_orientation, interpolation)
+                                           apply_orientation, interpolation, colors=color)
     _raise_first_failed(decs, rcs)
     return out
 
@@ -511,6 +527,72 @@ def cmyk_to_rgb_tensor(ctx, images, planes, layout="HWC", inverted=None, stream=
     ctx.cmyk_to_rgb_device([im.data_ptr() for im in imgs], [k.data_ptr() for k in ks], sizes,
                            LAYOUT_CHW if layout == "CHW" else LAYOUT_HWC, [o.data_ptr() for o in outs], inverted, pitches,
                            kpitches, None, s.cuda_stream)
+    return outs
+
+
+_LUMA = (0.299, 0.587, 0.114)
+# RGB -> YIQ (NTSC): the rows of I and Q sum to 0, so the inverse's first column is ones and a gray pixel keeps its value
+_RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.595716, -0.274453, -0.321263), (0.211456, -0.522591, 0.311135))
+
+
+def color_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, contrast_center=128.0, grayscale=False, bgr=False):
+    """The float64 [3, 4] colour matrix of the colour stage: out[c] = m[c][0] R + m[c][1] G + m[c][2] B +
+    m[c][3], in grey levels 0..255.  The steps are affine maps composed WITHOUT clamps between them, in this order:
+    brightness b (b I), contrast c about contrast_center (c I, offset (1 - c) centre; Pillow's ImageEnhance.Contrast uses
+    int(mean of L + 0.5) of the image, which the caller passes: the stage makes no reduction), saturation s
+    (s I + (1 - s) W, every row of W the luma weights 0.299, 0.587, 0.114: ImageEnhance.Color, torchvision's
+    adjust_saturation), hue: a rotation by `hue` TURNS (1.0 = 360 degrees) of the I, Q plane of YIQ, I' = cos I - sin Q,
+    Q' = sin I + cos Q.  That is DALI's linear hue (hsv / color_twist), NOT torchvision's adjust_hue, which shifts H of HSV and
+    is not linear.  grayscale: saturation 0 (RandomGrayscale, Pillow's convert("L") in all three channels).  bgr: rows 0 and 2
+    swapped last (the output is B, G, R)."""
+    import math
+    import numpy as np
+    eye = np.eye(3)
+    lin, off = float(brightness) * eye, np.zeros(3)
+    lin, off = float(contrast) * lin, float(contrast) * off + (1.0 - float(contrast)) * float(contrast_center)
+    s = 0.0 if grayscale else float(saturation)
+    sat = s * eye + (1.0 - s) * np.tile(np.asarray(_LUMA, np.float64), (3, 1))
+    lin, off = sat @ lin, sat @ off
+    if hue != 0.0:
+        a = 2.0 * math.pi * float(hue)
+        t = np.asarray(_RGB_TO_YIQ, np.float64)
+        rot = np.array([[1.0, 0.0, 0.0], [0.0, math.cos(a), -math.sin(a)], [0.0, math.sin(a), math.cos(a)]])
+        h = np.linalg.inv(t) @ rot @ t
+        lin, off = h @ lin, h @ off
+    m = np.concatenate([lin, off[:, None]], axis=1)
+    if bgr:
+        m = m[::-1].copy()
+    return np.ascontiguousarray(m, np.float64)
+
+
+def color_twist_tensor(ctx, images, matrices, in_layout="HWC", inplace=False, stream=None):
+    """u8 CUDA images under one [3, 4] colour matrix each (zj_color_device): images = [H, W, 3] ("HWC") or
+    [3, H, W] ("CHW") uint8 tensors of their own sizes, rows may be strided; matrices = one per image (color_matrix; None: the
+    identity).  out[c] = clamp((q[c] . (R, G, B, 1) + 32768) >> 16, 0, 255) with q = floor(m 65536 + 1/2), exact integers.
+    Returns a list of new contiguous tensors in the same layout; inplace=True: the images themselves are written (each must
+    be usable as it is: unit stride inside a row, CHW planes H rows apart) and returned.  Streams as decode_to_tensor."""
+    import torch
+    if in_layout not in ("HWC", "CHW"):
+        raise ValueError("in_layout is 'HWC' or 'CHW'")
+    imgs, sizes, pitches, channels = _u8_images(images, in_layout)
+    if channels != 3:
+        raise ValueError("colour matrices map 3-channel images")
+    if len(matrices) != len(imgs):
+        raise ValueError("one colour matrix per image")
+    if inplace and any(a is not b for a, b in zip(imgs, images)):
+        raise ValueError("inplace needs images that are used as they are (3 dimensions, unit stride inside a row)")
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    if inplace:
+        outs, opitches = imgs, pitches
+    else:
+        with torch.cuda.stream(s):
+            outs = [torch.empty((3, h, w) if in_layout == "CHW" else (h, w, 3), dtype=torch.uint8, device=dev) for w, h in sizes]
+        opitches = None
+    _on_stream(s, cur, imgs)
+    ctx.color_device([im.data_ptr() for im in imgs], sizes, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC, matrices,
+                     [o.data_ptr() for o in outs], pitches, opitches, s.cuda_stream)
     return outs
 
 
