@@ -91,7 +91,7 @@ ZJ_HD uint32_t resize_bf16_bits(const float y)
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
-// float32 -> float16, nearest-even, overflow to inf (the emulation's; the kernel converts with v_cvt_f16_f32)
+// float32 -> float16, nearest-even, overflow to inf (the emulation's; the kernel converts with v_cvt_pk_f16_f32, resize_pack2)
 ZJ_HD uint32_t resize_f16_bits(const float y)
 {
     const uint32_t u = f32_bits(y);
@@ -182,7 +182,8 @@ ZJ_HD uint32_t resize_pack2(const float a, const float b)
         return __builtin_bit_cast(uint32_t, r);
     }
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const h2 r = {(_Float16)a, (_Float16)b}; // v_cvt_f16_f32 (nearest-even) x 2, packed
+    // v_cvt_pk_f16_f32: nearest-even, subnormal results kept (v_cvt_f16_f32 where one of the two is a constant)
+    const h2 r = {(_Float16)a, (_Float16)b};
     return __builtin_bit_cast(uint32_t, r);
 #endif
 }
