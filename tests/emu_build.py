@@ -1,4 +1,5 @@
 """The build step of the CPU emulation libraries (emu_c, emu_crop_c, emu_resize_c, emu_resize_aa_c, emu_scaled_c).  TEST ONLY."""
+import ctypes
 import fcntl
 import os
 import subprocess
@@ -20,3 +21,20 @@ def build(so, srcs, opt, extra=()):
                                        "-Wall", "-Wno-unknown-pragmas", "-o", tmp, srcs[0]])
                 os.replace(tmp, so)
     return so
+
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(os.path.dirname(HERE), "zune-jpeg_amd", "csrc")
+_LIBS = {}
+
+
+def load(folder, so, cpp, headers, opt, extra=(), bind=None):
+    """The emulation tests/<folder>/<cpp> as a ctypes library, loaded once: built into tests/<folder>/<so> when that is older
+    than the .cpp or one of `headers` (names under zune-jpeg_amd/csrc, or paths from tests/); bind(L) declares its functions."""
+    if so not in _LIBS:
+        srcs = [os.path.join(HERE, folder, cpp)] + [os.path.join(HERE if "/" in h else CSRC, h) for h in headers]
+        L = ctypes.CDLL(build(os.path.join(HERE, folder, so), srcs, opt, extra))
+        if bind:
+            bind(L)
+        _LIBS[so] = L
+    return _LIBS[so]

@@ -9,20 +9,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-static uint8_t* g_map = nullptr;     // one count per byte of [g_lo, g_hi)
-static uint64_t g_lo = 0, g_hi = 0;
-static long long g_outside = 0;
-template <typename T>
-static inline void emu_put(uint64_t a, T v)
-{
-    if (a < g_lo || a + sizeof(T) > g_hi) { g_outside++; return; }
-    memcpy(reinterpret_cast<void*>((uintptr_t)a), &v, sizeof(T));
-    for (size_t k = 0; k < sizeof(T); k++)
-        if (g_map[a - g_lo + k] < 255) g_map[a - g_lo + k]++;
-}
+#include "../emu_common/zj_emu_arena.h"
 #define ZJ_EXPAND_PUT(T, addr, v) emu_put<T>((addr), (v))
 
 #include "../../zune-jpeg_amd/csrc/zj_cmyk.h"
+#include "../../zune-jpeg_amd/csrc/zj_stage_pack.h"
 
 using namespace zj;
 
@@ -46,20 +37,13 @@ extern "C" long long zjck_combine(int n, const uint8_t* const* a, const uint8_t*
                                   const unsigned* k_pitch, int chw, const uint8_t* inverted, uint8_t* const* out,
                                   const unsigned* out_pitch, uint8_t* arena, size_t len, uint8_t* map)
 {
-    if (n <= 0) return -1;
-    g_map = map; g_lo = (uint64_t)(uintptr_t)arena; g_hi = g_lo + len; g_outside = 0;
-    for (int f0 = 0; f0 < n; f0 += CMYK_BATCH) {
-        CmykParams p{};
-        p.nimg = n - f0 < CMYK_BATCH ? n - f0 : CMYK_BATCH;
-        for (int i = 0; i < p.nimg; i++) {
-            const int f = f0 + i;
-            if (wh[2 * f] == 0 || wh[2 * f + 1] == 0 || wh[2 * f] > 65535 || wh[2 * f + 1] > 65535) return -1;
-            p.a[i] = (uint64_t)(uintptr_t)a[f]; p.k[i] = (uint64_t)(uintptr_t)k[f]; p.out[i] = (uint64_t)(uintptr_t)out[f];
-            p.wh[i] = wh[2 * f] | (wh[2 * f + 1] << 16);
-            p.a_pitch[i] = a_pitch[f]; p.k_pitch[i] = k_pitch[f]; p.out_pitch[i] = out_pitch[f];
-            if (inverted[f]) p.inverted[i >> 5] |= 1u << (i & 31);
-        }
+    if (n <= 0 || !stage_sizes((size_t)n, wh)) return -1;
+    emu_arena(arena, len, map);
+    CmykParams p{};
+    stage_batches<CMYK_BATCH>((size_t)n, [&](size_t f0, int m) {
+        pack_cmyk(p, a, k, wh, a_pitch, k_pitch, inverted, out, out_pitch, f0, m);
         if (chw) run<true>(p); else run<false>(p);
-    }
+        return 0;
+    });
     return g_outside;
 }

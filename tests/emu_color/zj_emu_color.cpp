@@ -9,17 +9,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-static uint8_t *g_wmap = nullptr, *g_rmap = nullptr; // one count per byte of [g_wlo, g_whi) / [g_rlo, g_rhi)
-static uint64_t g_wlo = 0, g_whi = 0, g_rlo = 0, g_rhi = 0;
-static long long g_outside = 0;
-template <typename T>
-static inline void emu_put(uint64_t a, T v)
-{
-    if (a < g_wlo || a + sizeof(T) > g_whi) { g_outside++; return; }
-    memcpy(reinterpret_cast<void*>((uintptr_t)a), &v, sizeof(T));
-    for (size_t k = 0; k < sizeof(T); k++)
-        if (g_wmap[a - g_wlo + k] < 255) g_wmap[a - g_wlo + k]++;
-}
+#include "../emu_common/zj_emu_arena.h"
+
+static uint8_t* g_rmap = nullptr; // one count per byte of [g_rlo, g_rhi)
+static uint64_t g_rlo = 0, g_rhi = 0;
 #define ZJ_EXPAND_PUT(T, addr, v) emu_put<T>((addr), (v))
 
 // a load of the kernel: the address it may read from, counted; outside the source arena: zeros, counted apart
@@ -39,6 +32,10 @@ static inline T* emu_at(uint64_t a)
 #undef ZJ_RZ_GLOBAL
 #define ZJ_RZ_GLOBAL(T, v) (emu_at<T>((uint64_t)(v)))
 #include "../../zune-jpeg_amd/csrc/zj_color.h"
+// (the other stages' headers, which come with zj_stage_pack.h and are not run here, load as they are written)
+#undef ZJ_RZ_GLOBAL
+#define ZJ_RZ_GLOBAL(T, v) (reinterpret_cast<T*>(v))
+#include "../../zune-jpeg_amd/csrc/zj_stage_pack.h"
 
 using namespace zj;
 
@@ -66,22 +63,14 @@ extern "C" long long zjcl_color(int n, const uint8_t* const* in, const unsigned*
                                 uint8_t* const* out, const unsigned* out_pitch, const uint8_t* src, size_t src_len, uint8_t* rmap,
                                 uint8_t* arena, size_t len, uint8_t* wmap)
 {
-    if (n <= 0) return -1;
-    g_wmap = wmap; g_wlo = (uint64_t)(uintptr_t)arena; g_whi = g_wlo + len;
+    if (n <= 0 || !stage_sizes((size_t)n, wh)) return -1;
+    emu_arena(arena, len, wmap);
     g_rmap = rmap; g_rlo = (uint64_t)(uintptr_t)src; g_rhi = g_rlo + src_len;
-    g_outside = 0;
-    for (int f0 = 0; f0 < n; f0 += COLOR_BATCH) {
-        ColorParams p{};
-        p.nimg = n - f0 < COLOR_BATCH ? n - f0 : COLOR_BATCH;
-        for (int i = 0; i < p.nimg; i++) {
-            const int f = f0 + i;
-            if (wh[2 * f] == 0 || wh[2 * f + 1] == 0 || wh[2 * f] > 65535 || wh[2 * f + 1] > 65535) return -1;
-            p.in[i] = (uint64_t)(uintptr_t)in[f]; p.out[i] = (uint64_t)(uintptr_t)out[f];
-            p.wh[i] = wh[2 * f] | (wh[2 * f + 1] << 16);
-            p.in_pitch[i] = in_pitch[f]; p.out_pitch[i] = out_pitch[f];
-            for (int k = 0; k < 12; k++) p.q[i][k] = q[12 * f + k];
-        }
+    ColorParams p{};
+    stage_batches<COLOR_BATCH>((size_t)n, [&](size_t f0, int m) {
+        pack_color(p, in, wh, in_pitch, q, out, out_pitch, f0, m);
         if (chw) run<true>(p); else run<false>(p);
-    }
+        return 0;
+    });
     return g_outside;
 }

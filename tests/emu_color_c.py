@@ -1,31 +1,22 @@
 """ctypes binding of the CPU emulation of the colour-matrix kernel (tests/emu_color).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = None
+
+def _bind(L):
+    L.zjcl_color.restype = C.c_longlong
+    L.zjcl_color.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.zjcl_fixed.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_color", "libzjemucolor.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_color", "zj_emu_color.cpp")] + [os.path.join(csrc, h) for h in (
-            "zj_color.h", "zj_color_fixed.h", "zj_cmyk.h", "zj_expand.h", "zj_resize.h", "zj_geom.h")]
-        emu_build.build(so, srcs, "-O2")
-        L = C.CDLL(so)
-        L.zjcl_color.restype = C.c_longlong
-        L.zjcl_color.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.zjcl_fixed.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_color", "libzjemucolor.so", "zj_emu_color.cpp",
+                          ("zj_stage_pack.h", "zj_color.h", "zj_color_fixed.h", "zj_cmyk.h", "zj_expand.h", "zj_resize.h", "zj_geom.h", "emu_common/zj_emu_arena.h"),
+                          "-O2", bind=_bind)
 
 
 def run():

@@ -1,30 +1,21 @@
 """ctypes binding of the CPU emulation of the gray-to-RGB kernel (tests/emu_expand).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = None
+
+def _bind(L):
+    L.zjex_expand.restype = C.c_longlong
+    L.zjex_expand.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_size_t, C.c_void_p]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_expand", "libzjemuexpand.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_expand", "zj_emu_expand.cpp"), os.path.join(csrc, "zj_expand.h"),
-                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-        emu_build.build(so, srcs, "-O2")
-        L = C.CDLL(so)
-        L.zjex_expand.restype = C.c_longlong
-        L.zjex_expand.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_size_t, C.c_void_p]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_expand", "libzjemuexpand.so", "zj_emu_expand.cpp",
+                          ("zj_stage_pack.h", "zj_expand.h", "zj_resize.h", "zj_geom.h", "emu_common/zj_emu_arena.h"),
+                          "-O2", bind=_bind)
 
 
 def run():

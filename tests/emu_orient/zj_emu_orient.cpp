@@ -11,20 +11,11 @@
 
 #include <vector>
 
-static uint8_t* g_map = nullptr;     // one count per byte of [g_lo, g_hi)
-static uint64_t g_lo = 0, g_hi = 0;
-static long long g_outside = 0;
-template <typename T>
-static inline void emu_put(uint64_t a, T v)
-{
-    if (a < g_lo || a + sizeof(T) > g_hi) { g_outside++; return; }
-    memcpy(reinterpret_cast<void*>((uintptr_t)a), &v, sizeof(T));
-    for (size_t k = 0; k < sizeof(T); k++)
-        if (g_map[a - g_lo + k] < 255) g_map[a - g_lo + k]++;
-}
+#include "../emu_common/zj_emu_arena.h"
 #define ZJ_ORIENT_PUT(T, addr, v) emu_put<T>((addr), (v))
 
 #include "../../zune-jpeg_amd/csrc/zj_orient.h"
+#include "../../zune-jpeg_amd/csrc/zj_stage_pack.h"
 
 using namespace zj;
 
@@ -51,26 +42,24 @@ extern "C" int zjeo_tile(void) { return ORIENT_T; }
 extern "C" int zjeo_batch(void) { return ORIENT_BATCH; }
 extern "C" int zjeo_lds_bytes(int bpp) { return bpp == 3 ? orient_lds_bytes<3>() : orient_lds_bytes<1>(); }
 
-// n images (n <= ORIENT_BATCH) as one launch; wh: STORED w, h pairs; every destination byte must lie in [arena, arena + len):
-// map gets the number of times each of them was stored; returns the stores that fell outside (not performed), < 0: arguments
+// n images as the launches of the library's call (ORIENT_BATCH images each); wh: STORED w, h pairs; every destination byte must
+// lie in [arena, arena + len): map gets the number of times each of them was stored; returns the stores that fell outside (not
+// performed), < 0: arguments
 extern "C" long long zjeo_orient(int n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int channels,
                                  int in_chw, const uint8_t* o, uint8_t* const* out, const unsigned* out_pitch, uint8_t* arena,
                                  size_t len, uint8_t* map)
 {
-    if (n <= 0 || n > ORIENT_BATCH) return -1;
-    OrientParams p{};
-    p.nimg = n;
-    for (int i = 0; i < n; i++) {
+    if (n <= 0 || (channels != 1 && channels != 3)) return -1;
+    for (int i = 0; i < n; i++)
         if (!orient_valid(o[i])) return -1;
-        p.in[i] = (uint64_t)(uintptr_t)in[i]; p.out[i] = (uint64_t)(uintptr_t)out[i];
-        p.wh[i] = wh[2 * i] | (wh[2 * i + 1] << 16);
-        p.in_pitch[i] = in_pitch[i]; p.out_pitch[i] = out_pitch[i];
-        p.o[i] = o[i];
-    }
-    g_map = map; g_lo = (uint64_t)(uintptr_t)arena; g_hi = g_lo + len; g_outside = 0;
-    if (channels == 1) run<1, false>(p);
-    else if (channels == 3 && in_chw) run<3, true>(p);
-    else if (channels == 3) run<3, false>(p);
-    else return -1;
+    emu_arena(arena, len, map);
+    OrientParams p{};
+    stage_batches<ORIENT_BATCH>((size_t)n, [&](size_t f0, int m) {
+        pack_orient(p, in, wh, in_pitch, o, out, out_pitch, f0, m);
+        if (channels == 1) run<1, false>(p);
+        else if (in_chw) run<3, true>(p);
+        else run<3, false>(p);
+        return 0;
+    });
     return g_outside;
 }

@@ -1,31 +1,22 @@
 """ctypes binding of the CPU emulation of the orientation kernel (tests/emu_orient).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = None
+
+def _bind(L):
+    L.zjeo_orient.restype = C.c_longlong
+    L.zjeo_orient.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.zjeo_lds_bytes.argtypes = [C.c_int]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_orient", "libzjemuorient.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_orient", "zj_emu_orient.cpp"), os.path.join(csrc, "zj_orient.h"),
-                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-        emu_build.build(so, srcs, "-O2")
-        L = C.CDLL(so)
-        L.zjeo_orient.restype = C.c_longlong
-        L.zjeo_orient.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.zjeo_lds_bytes.argtypes = [C.c_int]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_orient", "libzjemuorient.so", "zj_emu_orient.cpp",
+                          ("zj_stage_pack.h", "zj_orient.h", "zj_resize.h", "zj_geom.h", "emu_common/zj_emu_arena.h"),
+                          "-O2", bind=_bind)
 
 
 def tile():

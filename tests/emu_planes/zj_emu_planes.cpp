@@ -10,17 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-static uint8_t* g_map = nullptr;     // one count per byte of [g_lo, g_hi)
-static uint64_t g_lo = 0, g_hi = 0;
-static long long g_outside = 0;
-template <typename T>
-static inline void emu_put(uint64_t a, T v)
-{
-    if (a < g_lo || a + sizeof(T) > g_hi) { g_outside++; return; }
-    memcpy(reinterpret_cast<void*>((uintptr_t)a), &v, sizeof(T));
-    for (size_t k = 0; k < sizeof(T); k++)
-        if (g_map[a - g_lo + k] < 255) g_map[a - g_lo + k]++;
-}
+#include "../emu_common/zj_emu_arena.h"
 #define ZJ_EXPAND_PUT(T, addr, v) emu_put<T>((addr), (v))
 
 #include "../../zune-jpeg_amd/csrc/zj_expand.h"
@@ -31,7 +21,7 @@ static uint64_t g_rlo = 0, g_rhi = 0;
 static long long g_bad_reads = 0;
 alignas(16) static const uint8_t g_zero[16] = {0};
 template <typename T>
-static inline T* emu_get(uint64_t a)
+static inline T* emu_needed(uint64_t a)
 {
     bool ok = a >= g_rlo && a + sizeof(T) <= g_rhi;
     for (size_t k = 0; ok && k < sizeof(T); k++) ok = g_needed[a - g_rlo + k] != 0;
@@ -39,9 +29,13 @@ static inline T* emu_get(uint64_t a)
     return reinterpret_cast<T*>((uintptr_t)a);
 }
 #undef ZJ_RZ_GLOBAL
-#define ZJ_RZ_GLOBAL(T, v) (emu_get<T>(v))
+#define ZJ_RZ_GLOBAL(T, v) (emu_needed<T>(v))
 
 #include "../../zune-jpeg_amd/csrc/zj_planes.h"
+// (the other stages' headers, which come with zj_stage_pack.h and are not run here, load as they are written)
+#undef ZJ_RZ_GLOBAL
+#define ZJ_RZ_GLOBAL(T, v) (reinterpret_cast<T*>(v))
+#include "../../zune-jpeg_amd/csrc/zj_stage_pack.h"
 
 using namespace zj;
 
@@ -68,28 +62,25 @@ extern "C" long long zjpl_combine(int n, const uint8_t* const* planes, const uns
                                   int stored_rgb, int chw, uint8_t* const* out, const unsigned* out_pitch, uint8_t* arena, size_t len,
                                   uint8_t* map, const uint8_t* src, size_t src_len, const uint8_t* needed)
 {
-    if (n <= 0) return -1;
-    g_map = map; g_lo = (uint64_t)(uintptr_t)arena; g_hi = g_lo + len; g_outside = 0;
+    if (n <= 0 || !stage_sizes((size_t)n, wh)) return -1;
+    emu_arena(arena, len, map);
     g_needed = needed; g_rlo = (uint64_t)(uintptr_t)src; g_rhi = g_rlo + src_len; g_bad_reads = 0;
-    for (int f0 = 0; f0 < n; f0 += PLANES_BATCH) {
-        PlanesParams p{};
-        p.nimg = n - f0 < PLANES_BATCH ? n - f0 : PLANES_BATCH;
-        for (int i = 0; i < p.nimg; i++) {
-            const int f = f0 + i;
-            if (wh[2 * f] == 0 || wh[2 * f + 1] == 0 || wh[2 * f] > 65535 || wh[2 * f + 1] > 65535) return -1;
-            p.out[i] = (uint64_t)(uintptr_t)out[f];
-            p.wh[i] = wh[2 * f] | (wh[2 * f + 1] << 16);
-            p.out_pitch[i] = out_pitch[f];
-            for (int c = 0; c < 3; c++) {
-                const uint8_t* g = geo + 12 * f + 4 * c;
-                if ((g[0] != 1 && g[0] != 2 && g[0] != 4) || (g[1] != 1 && g[1] != 2 && g[1] != 4) || g[2] >= g[0] || g[3] >= g[1]) return -1;
-                p.p[c][i] = (uint64_t)(uintptr_t)planes[3 * f + c];
-                p.pitch[c][i] = pitch[3 * f + c];
-                p.geo[i] |= planes_geo(g[0] >> 1, g[1] >> 1, g[2], g[3]) << (8 * c);
-            }
+    std::vector<uint32_t> geos((size_t)n, 0);
+    for (int f = 0; f < n; f++)
+        for (int c = 0; c < 3; c++) {
+            const uint8_t* g = geo + 12 * f + 4 * c;
+            unsigned pw;
+            uint32_t bits;
+            if (!planes_component(wh[2 * f], g[0], g[1], g[2], g[3], pw, bits)) return -1;
+            geos[f] |= bits << (8 * c);
         }
+    const uint8_t* const* const of[3] = {planes, planes + 1, planes + 2};
+    PlanesParams p{};
+    stage_batches<PLANES_BATCH>((size_t)n, [&](size_t f0, int m) {
+        pack_planes(p, of, 3, pitch, wh, geos.data(), out, out_pitch, f0, m);
         if (chw) { if (stored_rgb) run<true, true>(p); else run<true, false>(p); }
         else { if (stored_rgb) run<false, true>(p); else run<false, false>(p); }
-    }
+        return 0;
+    });
     return g_outside;
 }

@@ -1,31 +1,22 @@
 """ctypes binding of the CPU emulation of the planes-to-RGB kernel (tests/emu_planes).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = None
+
+def _bind(L):
+    L.zjpl_combine.restype = C.c_longlong
+    L.zjpl_bad_reads.restype = C.c_longlong
+    L.zjpl_combine.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_planes", "libzjemuplanes.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_planes", "zj_emu_planes.cpp"), os.path.join(csrc, "zj_planes.h"),
-                os.path.join(csrc, "zj_expand.h"), os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-        emu_build.build(so, srcs, "-O2")
-        L = C.CDLL(so)
-        L.zjpl_combine.restype = C.c_longlong
-        L.zjpl_bad_reads.restype = C.c_longlong
-        L.zjpl_combine.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_planes", "libzjemuplanes.so", "zj_emu_planes.cpp",
+                          ("zj_stage_pack.h", "zj_planes.h", "zj_expand.h", "zj_resize.h", "zj_geom.h", "emu_common/zj_emu_arena.h"),
+                          "-O2", bind=_bind)
 
 
 def run():

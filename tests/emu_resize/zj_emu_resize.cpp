@@ -10,6 +10,8 @@
 
 #include "../../zune-jpeg_amd/csrc/zj_resize.h"
 
+#include "../../zune-jpeg_amd/csrc/zj_stage_pack.h"
+
 using namespace zj;
 
 extern "C" uint32_t zjer_tap(uint32_t i, uint32_t n, uint32_t m) { return resize_tap(i, n, m); }
@@ -55,28 +57,20 @@ static int run_dt(int dt, const ResizeParams& p)
     return -1;
 }
 
-// n images (n <= RESIZE_BATCH) as one launch; wh: w, h pairs; s / b: the kernel's factors (s_c = scale_c * 2^-16)
+// n images as the launches of the library's call (RESIZE_BATCH images each); wh: w, h pairs; s / b: the kernel's factors (s_c = scale_c * 2^-16)
 extern "C" int zjer_resize(int n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, int channels, int in_chw,
                            int out_w, int out_h, int dtype, int nhwc, const float* s, const float* b, const uint8_t* flip,
                            uint8_t* out)
 {
-    if (n <= 0 || n > RESIZE_BATCH) return -1;
+    if (n <= 0 || (channels != 1 && channels != 3) || !resize_elem_bytes(dtype)) return -1;
+    StageTensor t{out, (size_t)channels * out_w * out_h * (size_t)resize_elem_bytes(dtype), out_w, out_h, dtype, nhwc ? 1 : 0, {}, {}};
+    for (int k = 0; k < 3; k++) { t.s[k] = s[k]; t.b[k] = b[k]; }
     ResizeParams p{};
-    p.out_w = out_w; p.out_h = out_h; p.nimg = n;
-    p.groups = (out_w + RESIZE_GROUP - 1) / RESIZE_GROUP;
-    p.rows = RESIZE_ITEMS / p.groups;
-    if (p.rows < 1) p.rows = 1;
-    if (p.rows > out_h) p.rows = out_h;
-    p.out = (uint64_t)(uintptr_t)out;
-    for (int k = 0; k < 3; k++) { p.scale[k] = s[k]; p.bias[k] = b[k]; }
-    for (int i = 0; i < n; i++) {
-        p.in[i] = (uint64_t)(uintptr_t)in[i];
-        p.wh[i] = wh[2 * i] | (wh[2 * i + 1] << 16);
-        p.pitch[i] = pitch[i];
-        if (flip && flip[i]) p.flip[i >> 5] |= 1u << (i & 31);
-    }
-    if (channels == 1) return run_dt<false, 1, false>(dtype, p);
-    if (channels != 3) return -1;
-    if (in_chw) return nhwc ? run_dt<true, 3, true>(dtype, p) : run_dt<true, 3, false>(dtype, p);
-    return nhwc ? run_dt<false, 3, true>(dtype, p) : run_dt<false, 3, false>(dtype, p);
+    const int rc = stage_batches<RESIZE_BATCH>((size_t)n, [&](size_t f0, int m) {
+        pack_resize(p, in, wh, pitch, flip, t, 0, f0, m);
+        if (channels == 1) return run_dt<false, 1, false>(dtype, p);
+        if (in_chw) return nhwc ? run_dt<true, 3, true>(dtype, p) : run_dt<true, 3, false>(dtype, p);
+        return nhwc ? run_dt<false, 3, true>(dtype, p) : run_dt<false, 3, false>(dtype, p);
+    });
+    return rc;
 }

@@ -1,35 +1,25 @@
 """ctypes binding of the CPU emulation of the antialiased resize kernel (tests/emu_resize_aa).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = None
+
+def _bind(L):
+    L.zjea_weight.restype = C.c_uint32
+    L.zjea_weight.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
+    L.zjea_axis.restype = None
+    L.zjea_axis.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                            C.POINTER(C.c_ulonglong)]
+    L.zjea_resize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_resize_aa", "libzjemuresizeaa.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_resize_aa", "zj_emu_resize_aa.cpp"), os.path.join(csrc, "zj_resize_aa.h"),
-                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-
-        emu_build.build(so, srcs, "-O2", ["-ffp-contract=off"])
-        L = C.CDLL(so)
-        L.zjea_weight.restype = C.c_uint32
-        L.zjea_weight.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
-        L.zjea_axis.restype = None
-        L.zjea_axis.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                C.POINTER(C.c_ulonglong)]
-        L.zjea_resize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_resize_aa", "libzjemuresizeaa.so", "zj_emu_resize_aa.cpp",
+                          ("zj_stage_pack.h", "zj_resize_aa.h", "zj_resize.h", "zj_geom.h"),
+                          "-O2", extra=("-ffp-contract=off",), bind=_bind)
 
 
 def weights(i, n, m):

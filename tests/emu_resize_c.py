@@ -1,37 +1,28 @@
 """ctypes binding of the CPU emulation of the resize kernel (tests/emu_resize).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = None
+
+def _bind(L):
+    L.zjer_tap.restype = C.c_uint32
+    L.zjer_tap.argtypes = [C.c_uint32] * 3
+    L.zjer_f32.restype = C.c_float
+    L.zjer_f32.argtypes = [C.c_uint32, C.c_float, C.c_float]
+    L.zjer_f16.restype = C.c_uint32
+    L.zjer_f16.argtypes = [C.c_float]
+    L.zjer_bf16.restype = C.c_uint32
+    L.zjer_bf16.argtypes = [C.c_float]
+    L.zjer_resize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_resize", "libzjemuresize.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_resize", "zj_emu_resize.cpp"), os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-
-        emu_build.build(so, srcs, "-O1", ["-ffp-contract=off"])
-        L = C.CDLL(so)
-        L.zjer_tap.restype = C.c_uint32
-        L.zjer_tap.argtypes = [C.c_uint32] * 3
-        L.zjer_f32.restype = C.c_float
-        L.zjer_f32.argtypes = [C.c_uint32, C.c_float, C.c_float]
-        L.zjer_f16.restype = C.c_uint32
-        L.zjer_f16.argtypes = [C.c_float]
-        L.zjer_bf16.restype = C.c_uint32
-        L.zjer_bf16.argtypes = [C.c_float]
-        L.zjer_resize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_resize", "libzjemuresize.so", "zj_emu_resize.cpp",
+                          ("zj_stage_pack.h", "zj_resize.h", "zj_geom.h"),
+                          "-O1", extra=("-ffp-contract=off",), bind=_bind)
 
 
 def tap(i, n, m):

@@ -1,32 +1,24 @@
 """ctypes binding of the CPU emulation of the u8-images-to-tensor kernel (tests/emu_to_tensor).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 ELEM = {0: 4, 1: 2, 2: 2, 3: 1}
-_LIB = None
+
+
+def _bind(L):
+    L.zjtt_to_tensor.restype = C.c_int
+    L.zjtt_to_tensor.argtypes = [C.c_int, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                 C.c_void_p]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_to_tensor", "libzjemutotensor.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_to_tensor", "zj_emu_to_tensor.cpp"), os.path.join(csrc, "zj_to_tensor.h"),
-                os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-        emu_build.build(so, srcs, "-O2", extra=("-ffp-contract=off",))
-        L = C.CDLL(so)
-        L.zjtt_to_tensor.restype = C.c_int
-        L.zjtt_to_tensor.argtypes = [C.c_int, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                     C.c_void_p]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_to_tensor", "libzjemutotensor.so", "zj_emu_to_tensor.cpp",
+                          ("zj_stage_pack.h", "zj_to_tensor.h", "zj_resize.h", "zj_geom.h", "emu_common/zj_emu_arena.h"),
+                          "-O2", extra=("-ffp-contract=off",), bind=_bind)
 
 
 def run():

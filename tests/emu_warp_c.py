@@ -1,37 +1,29 @@
 """ctypes binding of the CPU emulation of the affine-warp kernels (tests/emu_warp).  TEST ONLY."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import emu_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 ELEM = {0: 4, 1: 2, 2: 2, 3: 1}
 FILL, REPLICATE = 0, 1
-_LIB = None
+
+
+def _bind(L):
+    L.zjew_fixed.restype = C.c_int
+    L.zjew_fixed.argtypes = [C.c_void_p, C.c_void_p]
+    L.zjew_window.restype = None
+    L.zjew_window.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+    L.zjew_warp.restype = C.c_int
+    L.zjew_warp.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                            C.c_void_p, C.c_void_p]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "emu_warp", "libzjemuwarp.so")
-        csrc = os.path.join(ROOT, "zune-jpeg_amd", "csrc")
-        srcs = [os.path.join(HERE, "emu_warp", "zj_emu_warp.cpp"), os.path.join(csrc, "zj_warp.h"),
-                os.path.join(csrc, "zj_warp_fixed.h"), os.path.join(csrc, "zj_resize.h"), os.path.join(csrc, "zj_geom.h")]
-        emu_build.build(so, srcs, "-O2", extra=("-ffp-contract=off",))
-        L = C.CDLL(so)
-        L.zjew_fixed.restype = C.c_int
-        L.zjew_fixed.argtypes = [C.c_void_p, C.c_void_p]
-        L.zjew_window.restype = None
-        L.zjew_window.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
-        L.zjew_warp.restype = C.c_int
-        L.zjew_warp.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                C.c_void_p, C.c_void_p]
-        _LIB = L
-    return _LIB
+    return emu_build.load("emu_warp", "libzjemuwarp.so", "zj_emu_warp.cpp",
+                          ("zj_stage_pack.h", "zj_warp.h", "zj_warp_fixed.h", "zj_resize.h", "zj_geom.h", "emu_common/zj_emu_arena.h"),
+                          "-O2", extra=("-ffp-contract=off",), bind=_bind)
 
 
 def group():

@@ -26,6 +26,7 @@
 #include "zj_resize_launch.h"
 #include "zj_rzgroup.h"
 #include "zj_scaled_launch.h"
+#include "zj_stage_pack.h"
 #include "zj_to_tensor_launch.h"
 #include "zj_warp_fixed.h"
 #include "zj_warp_launch.h"
@@ -826,38 +827,6 @@ int zjint_crop_zeros(zj_ctx* c, const zj_frame_desc* d, unsigned x, unsigned yy,
 
 /* ---- resize + normalise ---------------------------------------------------------- */
 namespace {
-bool finite_f32(float v) { return v - v == 0.f; }
-
-// The per-channel factors of the tensor kernels from the caller's scale / bias (nullptr: 1, 0; read for the first `channels`
-// only): s_c = scale_c * 2^-16 -- exact: a power of two, above float32's smallest normal for every |scale| >= 2^-110 -- and
-// b_c = bias_c.  false: a factor that is not finite.
-bool kernel_factors(const float* scale, const float* bias, int channels, float s[3], float b[3])
-{
-    for (int k = 0; k < 3; k++) {
-        const float sc = scale && k < channels ? scale[k] : 1.f, bi = bias && k < channels ? bias[k] : 0.f;
-        if (!finite_f32(sc) || !finite_f32(bi)) return false;
-        s[k] = sc * (1.f / 65536.f);
-        b[k] = bi;
-    }
-    return true;
-}
-
-// The images of a u8 stage call checked and their pitches resolved: image f is in_wh[2f] x in_wh[2f + 1] pixels of
-// row_channels bytes each in a row, its rows in_pitch[f] bytes apart (in_pitch nullptr or 0: tight)
-int stage_images(size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int row_channels,
-                 std::vector<unsigned>& pitch)
-{
-    pitch.resize(n);
-    for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_in[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
-        const size_t row = (size_t)w * row_channels;
-        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : (unsigned)row;
-        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
-    }
-    return ZJ_OK;
-}
-
 // The output side of a resized call, as every layer below the entry points takes it: the dense tensor at d_out, image i of
 // the call at d_out + i * img_bytes, flipped if flip[i] (nullptr: none).
 struct ResizeOut {
@@ -897,37 +866,28 @@ int resize_out_args(ResizeOut& o, int channels)
     return kernel_factors(o.scale, o.bias, channels, o.s, o.b) ? ZJ_OK : ZJ_ERR_ARG;
 }
 
+// the tensor of the stage records (zj_stage_pack.h) that o names
+StageTensor stage_tensor(const ResizeOut& o)
+{
+    StageTensor t{o.d_out, o.img_bytes, (int)o.out_w, (int)o.out_h, o.dtype, o.layout == ZJ_TENSOR_NHWC, {}, {}};
+    for (int k = 0; k < 3; k++) { t.s[k] = o.s[k]; t.b[k] = o.b[k]; }
+    return t;
+}
+
 // images [0, n) -> images [first, first + n) of the output, launches of up to RESIZE_BATCH images; wh[2i], wh[2i + 1]: image
 // i's size, pitch[i] (bytes between its rows) already resolved
 int resize_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const ResizeOut& o,
                     size_t first, hipStream_t st)
 {
-    const uint8_t* const flip = o.flip ? o.flip + first : nullptr;
-    const int nhwc = o.layout == ZJ_TENSOR_NHWC;
+    const StageTensor t = stage_tensor(o);
     ResizeParams p{};
-    p.out_w = (int)o.out_w; p.out_h = (int)o.out_h;
-    for (int k = 0; k < 3; k++) { p.scale[k] = o.s[k]; p.bias[k] = o.b[k]; }
-    p.groups = (int)((o.out_w + RESIZE_GROUP - 1) / RESIZE_GROUP);
-    p.rows = RESIZE_ITEMS / p.groups;
-    if (p.rows < 1) p.rows = 1;
-    if (p.rows > (int)o.out_h) p.rows = (int)o.out_h;
-    for (size_t f0 = 0; f0 < n; f0 += RESIZE_BATCH) {
-        const int m = (int)(n - f0 < (size_t)RESIZE_BATCH ? n - f0 : (size_t)RESIZE_BATCH);
-        p.nimg = m;
-        p.out = (uint64_t)(uintptr_t)(o.d_out + (first + f0) * o.img_bytes);
-        for (int k = 0; k < RESIZE_BATCH / 32; k++) p.flip[k] = 0;
-        for (int i = 0; i < RESIZE_BATCH; i++) {
-            const size_t f = f0 + i;
-            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
-            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
-            p.pitch[i] = i < m ? pitch[f] : 0;
-            if (i < m && flip && flip[f]) p.flip[i >> 5] |= 1u << (i & 31);
-        }
-        ZJ_HIP(c, o.filter == ZJ_RESIZE_BICUBIC_AA    ? launch_resize_bicubic(o.ch, o.chw, o.dtype, nhwc, p, st)
-                  : o.filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(o.ch, o.chw, o.dtype, nhwc, p, st)
-                                                      : launch_resize(o.ch, o.chw, o.dtype, nhwc, p, st));
-    }
-    return ZJ_OK;
+    return stage_batches<RESIZE_BATCH>(n, [&](size_t f0, int m) {
+        pack_resize(p, in, wh, pitch, o.flip ? o.flip + first : nullptr, t, first, f0, m);
+        ZJ_HIP(c, o.filter == ZJ_RESIZE_BICUBIC_AA    ? launch_resize_bicubic(o.ch, o.chw, o.dtype, t.nhwc, p, st)
+                  : o.filter == ZJ_RESIZE_BILINEAR_AA ? launch_resize_aa(o.ch, o.chw, o.dtype, t.nhwc, p, st)
+                                                      : launch_resize(o.ch, o.chw, o.dtype, t.nhwc, p, st));
+        return ZJ_OK;
+    });
 }
 
 // the crop buffer, at least `bytes`, free for writing on stream st: st waits for the last resize that read it (whichever
@@ -955,27 +915,28 @@ int resize_scratch_done(zj_ctx* c, hipStream_t st)
     return ZJ_OK;
 }
 
+// the end of a library-internal call of one image (zjint_*_one) on the context stream: the context's crop buffer counts as
+// read by it; synchronised
+int one_image_done(zj_ctx* c)
+{
+    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
+    const int rc = resize_scratch_done(c, c->stream);
+    if (rc) return rc;
+    ZJ_HIP(c, hipStreamSynchronize(c->stream));
+    return ZJ_OK;
+}
+
 // images [0, n) -> their displayed form, launches of up to ORIENT_BATCH images; wh: STORED w, h pairs, the
 // pitches resolved, every o[i] 1..8
 int orient_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int channels,
                     int in_chw, const uint8_t* o, uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
 {
     OrientParams p{};
-    for (size_t f0 = 0; f0 < n; f0 += ORIENT_BATCH) {
-        const int m = (int)(n - f0 < (size_t)ORIENT_BATCH ? n - f0 : (size_t)ORIENT_BATCH);
-        p.nimg = m;
-        for (int i = 0; i < ORIENT_BATCH; i++) {
-            const size_t f = f0 + i;
-            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
-            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
-            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
-            p.in_pitch[i] = i < m ? in_pitch[f] : 0;
-            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
-            p.o[i] = i < m ? o[f] : 1;
-        }
+    return stage_batches<ORIENT_BATCH>(n, [&](size_t f0, int m) {
+        pack_orient(p, in, wh, in_pitch, o, out, out_pitch, f0, m);
         ZJ_HIP(c, launch_orient(channels, in_chw, p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 
 // planes [0, n) -> 3-channel images with every channel the plane, launches of up to EXPAND_BATCH images; wh:
@@ -984,20 +945,11 @@ int expand_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigne
                     uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
 {
     ExpandParams p{};
-    for (size_t f0 = 0; f0 < n; f0 += EXPAND_BATCH) {
-        const int m = (int)(n - f0 < (size_t)EXPAND_BATCH ? n - f0 : (size_t)EXPAND_BATCH);
-        p.nimg = m;
-        for (int i = 0; i < EXPAND_BATCH; i++) {
-            const size_t f = f0 + i;
-            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
-            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
-            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
-            p.in_pitch[i] = i < m ? in_pitch[f] : 0;
-            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
-        }
+    return stage_batches<EXPAND_BATCH>(n, [&](size_t f0, int m) {
+        pack_expand(p, in, wh, in_pitch, out, out_pitch, f0, m);
         ZJ_HIP(c, launch_expand(out_chw, p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 
 // image pairs [0, n) -> out[c] = (a[c] * k + 127) / 255, launches of up to CMYK_BATCH pairs; wh: w, h pairs, the
@@ -1007,24 +959,11 @@ int cmyk_launches(zj_ctx* c, size_t n, const uint8_t* const* a, const uint8_t* c
                   hipStream_t st)
 {
     CmykParams p{};
-    for (size_t f0 = 0; f0 < n; f0 += CMYK_BATCH) {
-        const int m = (int)(n - f0 < (size_t)CMYK_BATCH ? n - f0 : (size_t)CMYK_BATCH);
-        p.nimg = m;
-        for (int i = 0; i < CMYK_BATCH / 32; i++) p.inverted[i] = 0;
-        for (int i = 0; i < CMYK_BATCH; i++) {
-            const size_t f = f0 + i;
-            p.a[i] = i < m ? (uint64_t)(uintptr_t)a[f] : 0;
-            p.k[i] = i < m ? (uint64_t)(uintptr_t)k[f] : 0;
-            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
-            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
-            p.a_pitch[i] = i < m ? a_pitch[f] : 0;
-            p.k_pitch[i] = i < m ? k_pitch[f] : 0;
-            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
-            if (i < m && inverted[f]) p.inverted[i >> 5] |= 1u << (i & 31);
-        }
+    return stage_batches<CMYK_BATCH>(n, [&](size_t f0, int m) {
+        pack_cmyk(p, a, k, wh, a_pitch, k_pitch, inverted, out, out_pitch, f0, m);
         ZJ_HIP(c, launch_cmyk(chw, p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 
 // images [0, n) under their colour matrices, launches of up to COLOR_BATCH images; wh: w, h pairs, the pitches
@@ -1033,21 +972,11 @@ int color_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned
                    const int32_t* q, uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
 {
     ColorParams p{};
-    for (size_t f0 = 0; f0 < n; f0 += COLOR_BATCH) {
-        const int m = (int)(n - f0 < (size_t)COLOR_BATCH ? n - f0 : (size_t)COLOR_BATCH);
-        p.nimg = m;
-        for (int i = 0; i < COLOR_BATCH; i++) {
-            const size_t f = f0 + i;
-            p.in[i] = i < m ? (uint64_t)(uintptr_t)in[f] : 0;
-            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
-            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
-            p.in_pitch[i] = i < m ? in_pitch[f] : 0;
-            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
-            for (int k = 0; k < 12; k++) p.q[i][k] = i < m ? q[12 * f + k] : 0;
-        }
+    return stage_batches<COLOR_BATCH>(n, [&](size_t f0, int m) {
+        pack_color(p, in, wh, in_pitch, q, out, out_pitch, f0, m);
         ZJ_HIP(c, launch_color(chw, p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 
 // the 12 integers of each of n matrices of doubles, 12 each
@@ -1060,29 +989,18 @@ int color_matrices(const double* matrices, size_t n, std::vector<int32_t>& q)
 }
 
 // images [0, n) -> their three component planes box-replicated and converted, launches of up to PLANES_BATCH
-// images; wh: w, h pairs of the outputs, geo: planes_geo of the three components, pitch: three per image, all resolved
+// images; wh: w, h pairs of the outputs, geo: planes_component of the three components, pitch: three per image, all resolved
 int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t* const* p1, const uint8_t* const* p2,
                     const unsigned* wh, const uint32_t* geo, const unsigned* pitch, int stored_rgb, int chw, uint8_t* const* out,
                     const unsigned* out_pitch, hipStream_t st)
 {
+    const uint8_t* const* const planes[3] = {p0, p1, p2};
     PlanesParams p{};
-    for (size_t f0 = 0; f0 < n; f0 += PLANES_BATCH) {
-        const int m = (int)(n - f0 < (size_t)PLANES_BATCH ? n - f0 : (size_t)PLANES_BATCH);
-        p.nimg = m;
-        for (int i = 0; i < PLANES_BATCH; i++) {
-            const size_t f = f0 + i;
-            p.p[0][i] = i < m ? (uint64_t)(uintptr_t)p0[f] : 0;
-            p.p[1][i] = i < m ? (uint64_t)(uintptr_t)p1[f] : 0;
-            p.p[2][i] = i < m ? (uint64_t)(uintptr_t)p2[f] : 0;
-            p.out[i] = i < m ? (uint64_t)(uintptr_t)out[f] : 0;
-            for (int k = 0; k < 3; k++) p.pitch[k][i] = i < m ? pitch[3 * f + k] : 0;
-            p.out_pitch[i] = i < m ? out_pitch[f] : 0;
-            p.wh[i] = i < m ? wh[2 * f] | (wh[2 * f + 1] << 16) : 0;
-            p.geo[i] = i < m ? geo[f] : 0;
-        }
+    return stage_batches<PLANES_BATCH>(n, [&](size_t f0, int m) {
+        pack_planes(p, planes, 1, pitch, wh, geo, out, out_pitch, f0, m);
         ZJ_HIP(c, launch_planes(chw, stored_rgb, p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 
 // The end of the launch group [g0, g1) of a resized call, its crops written into buf where `place` says (zj_rzgroup.h):
@@ -1185,7 +1103,7 @@ int zj_resize_filtered_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, c
     if (rc) return rc;
     const bool chw = ro.chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
     std::vector<unsigned> pitch;
-    if ((rc = stage_images(n, d_in, in_wh, in_pitch, chw ? 1 : channels, pitch))) return rc;
+    if (!stage_images(n, d_in, in_wh, in_pitch, chw ? 1 : channels, pitch)) return ZJ_ERR_ARG;
     for (size_t f = 0; chw && f < n; f++)
         if ((size_t)pitch[f] * in_wh[2 * f + 1] * 3 > ((size_t)1 << 31)) return ZJ_ERR_ARG; // (the kernel's plane offsets)
     ZJ_HIP(c, hipSetDevice(c->device));
@@ -1373,8 +1291,7 @@ int warp_tail_args(const uint8_t* fill, int edge, int channels, WarpTail& t)
 {
     if (edge != ZJ_WARP_FILL && edge != ZJ_WARP_REPLICATE) return ZJ_ERR_ARG;
     t.edge = edge;
-    t.fill = 0;
-    for (int k = 0; fill && k < channels; k++) t.fill |= (uint32_t)fill[k] << (8 * k);
+    t.fill = warp_fill(fill, channels);
     return ZJ_OK;
 }
 
@@ -1389,38 +1306,17 @@ int warp_matrices(const double* matrices, size_t n, std::vector<int64_t>& q)
 }
 
 // images [0, n) -> images [first, first + n) of the output, launches of up to WARP_BATCH images; wh[2i], wh[2i + 1]: image
-// i's size, pitch[i] resolved, q: its six integers.  wh[2i] == 0: no image at all -- every tap of the output is outside
-// (fill mode alone): the record is a 1 x 1 image that no lane loads from, under a map that sends every pixel to x0 = -4
+// i's size (wh[2i] == 0: no image at all, pack_warp), pitch[i] resolved, q: its six integers
 int warp_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const int64_t* q,
                   const ResizeOut& o, const WarpTail& t, size_t first, hipStream_t st)
 {
+    const StageTensor tensor = stage_tensor(o);
     WarpParams p{};
-    p.out_w = (int)o.out_w; p.out_h = (int)o.out_h; p.dtype = o.dtype; p.nhwc = o.layout == ZJ_TENSOR_NHWC;
-    p.fill = t.fill; p.edge = t.edge;
-    for (int k = 0; k < 3; k++) { p.scale[k] = o.s[k]; p.bias[k] = o.b[k]; }
-    for (size_t f0 = 0; f0 < n; f0 += WARP_BATCH) {
-        const int m = (int)(n - f0 < (size_t)WARP_BATCH ? n - f0 : (size_t)WARP_BATCH);
-        p.nimg = m;
-        p.out = (uint64_t)(uintptr_t)(o.d_out + (first + f0) * o.img_bytes);
-        for (int i = 0; i < WARP_BATCH; i++) {
-            const size_t f = f0 + i;
-            WarpImage& im = p.img[i];
-            im = WarpImage{};
-            if (i >= m) continue;
-            if (wh[2 * f] == 0) {
-                im.in = (uint64_t)(uintptr_t)o.d_out; // (never loaded from)
-                im.wh = 1u | 1u << 16; im.pitch = 1;
-                im.m[2] = im.m[5] = -((int64_t)4 << WARP_Q);
-                continue;
-            }
-            im.in = (uint64_t)(uintptr_t)in[f];
-            im.wh = wh[2 * f] | (wh[2 * f + 1] << 16);
-            im.pitch = pitch[f];
-            for (int k = 0; k < 6; k++) im.m[k] = q[6 * f + k];
-        }
+    return stage_batches<WARP_BATCH>(n, [&](size_t f0, int m) {
+        pack_warp(p, in, wh, pitch, q, t.fill, t.edge, tensor, first, f0, m);
         ZJ_HIP(c, launch_warp(o.ch, p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 } // namespace
 
@@ -1463,7 +1359,7 @@ int zj_warp_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsign
     std::vector<int64_t> q;
     if ((rc = warp_matrices(matrices, n, q))) return rc;
     std::vector<unsigned> pitch;
-    if ((rc = stage_images(n, d_in, in_wh, in_pitch, channels, pitch))) return rc;
+    if (!stage_images(n, d_in, in_wh, in_pitch, channels, pitch)) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return warp_launches(c, n, d_in, in_wh, pitch.data(), q.data(), ro, wt, 0, st);
@@ -2047,19 +1943,20 @@ int zj_orient_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsi
     if (channels != 1 && channels != 3) return ZJ_ERR_ARG;
     if (in_layout != ZJ_LAYOUT_HWC && in_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
     const bool chw = in_layout == ZJ_LAYOUT_CHW && channels == 3;
-    const unsigned bpp = chw ? 1 : (unsigned)channels;
-    std::vector<unsigned> ip(n), op(n);
+    const int bpp = chw ? 1 : channels;
+    std::vector<unsigned> ip, op;
     std::vector<uint8_t> o(n, 1);
+    if (!stage_images(n, d_in, in_wh, in_pitch, bpp, ip)) return ZJ_ERR_ARG;
     for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_in[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
         if (orientation) o[f] = orientation[f];
-        unsigned dw, dh;
-        if (!orient_size(o[f], w, h, &dw, &dh)) return ZJ_ERR_ARG;
-        ip[f] = in_pitch && in_pitch[f] ? in_pitch[f] : w * bpp;
-        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : dw * bpp;
-        if (ip[f] < w * bpp || op[f] < dw * bpp || ip[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
+        if (!orient_valid(o[f])) return ZJ_ERR_ARG;
     }
+    const auto shown_row = [&](size_t f) { // (the output's rows are the DISPLAYED width)
+        unsigned dw = 0, dh = 0;
+        orient_size(o[f], in_wh[2 * f], in_wh[2 * f + 1], &dw, &dh);
+        return (size_t)dw * bpp;
+    };
+    if (!stage_side(n, d_out, out_pitch, shown_row, op)) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return orient_launches(c, n, d_in, in_wh, ip.data(), channels, chw, o.data(), d_out, op.data(), st);
@@ -2071,15 +1968,9 @@ int zj_gray_to_rgb_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const
 {
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_out) return ZJ_ERR_ARG;
     if (out_layout != ZJ_LAYOUT_HWC && out_layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
-    const unsigned bpp = out_layout == ZJ_LAYOUT_CHW ? 1 : 3;
-    std::vector<unsigned> ip(n), op(n);
-    for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_in[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
-        ip[f] = in_pitch && in_pitch[f] ? in_pitch[f] : w;
-        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
-        if (ip[f] < w || op[f] < w * bpp || ip[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
-    }
+    const int bpp = out_layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> ip, op;
+    if (!stage_images(n, d_in, in_wh, in_pitch, 1, ip) || !stage_side(n, d_out, out_pitch, in_wh, bpp, op)) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return expand_launches(c, n, d_in, in_wh, ip.data(), out_layout == ZJ_LAYOUT_CHW, d_out, op.data(), st);
@@ -2092,11 +1983,7 @@ int zjint_gray_to_rgb_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, 
     if (!c) return ZJ_ERR_ARG;
     const unsigned wh[2] = {w, h};
     int rc = zj_gray_to_rgb_device(c, 1, &in, wh, nullptr, out_layout, &d_out, nullptr, nullptr);
-    if (rc) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 /* ---- CMYK to RGB ---------------------------------------------------------------- */
@@ -2106,21 +1993,14 @@ int zj_cmyk_to_rgb_device(zj_ctx* c, size_t n, const uint8_t* const* d_a, const 
 {
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_a || !d_k || !in_wh || !d_out) return ZJ_ERR_ARG;
     if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
-    const unsigned bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
-    std::vector<unsigned> ap(n), kp(n), op(n);
-    std::vector<uint8_t> inv(n, 0);
-    for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_a[f] || !d_k[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
-        ap[f] = a_pitch && a_pitch[f] ? a_pitch[f] : w * bpp;
-        kp[f] = k_pitch && k_pitch[f] ? k_pitch[f] : w;
-        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
-        if (ap[f] < w * bpp || kp[f] < w || op[f] < w * bpp || ap[f] > (1u << 24) || kp[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
-        if (inverted) inv[f] = inverted[f] ? 1 : 0;
-    }
+    const int bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> ap, kp, op;
+    if (!stage_images(n, d_a, in_wh, a_pitch, bpp, ap) || !stage_side(n, d_k, k_pitch, in_wh, 1, kp) ||
+        !stage_side(n, d_out, out_pitch, in_wh, bpp, op))
+        return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    return cmyk_launches(c, n, d_a, d_k, in_wh, ap.data(), kp.data(), layout == ZJ_LAYOUT_CHW, inv.data(), d_out, op.data(), st);
+    return cmyk_launches(c, n, d_a, d_k, in_wh, ap.data(), kp.data(), layout == ZJ_LAYOUT_CHW, inverted, d_out, op.data(), st);
 }
 
 // Library-internal (zj_jpeg.cpp: the single-file resized crop of a four-component file): one tight image combined in place with
@@ -2132,11 +2012,7 @@ int zjint_cmyk_to_rgb_one(zj_ctx* c, uint8_t* a, const uint8_t* k, unsigned w, u
     const uint8_t inv = inverted ? 1 : 0;
     const uint8_t* ca = a;
     int rc = zj_cmyk_to_rgb_device(c, 1, &ca, &k, wh, nullptr, nullptr, layout, &inv, &a, nullptr, nullptr);
-    if (rc) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 /* ---- colour matrices -------------------------------------------------------------- */
@@ -2154,15 +2030,9 @@ int zj_color_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsig
 {
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !matrices || !d_out) return ZJ_ERR_ARG;
     if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
-    const unsigned bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
-    std::vector<unsigned> ip(n), op(n);
-    for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_in[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
-        ip[f] = in_pitch && in_pitch[f] ? in_pitch[f] : w * bpp;
-        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
-        if (ip[f] < w * bpp || op[f] < w * bpp || ip[f] > (1u << 24) || op[f] > (1u << 24)) return ZJ_ERR_ARG;
-    }
+    const int bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
+    std::vector<unsigned> ip, op;
+    if (!stage_images(n, d_in, in_wh, in_pitch, bpp, ip) || !stage_side(n, d_out, out_pitch, in_wh, bpp, op)) return ZJ_ERR_ARG;
     std::vector<int32_t> q;
     int rc = color_matrices(matrices, n, q);
     if (rc) return rc;
@@ -2176,18 +2046,14 @@ int zj_color_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsig
 // synchronised
 int zjint_color_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int layout, const int32_t q[12])
 {
-    if (!c || !img || !q || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+    if (!c || !img || !q || !stage_size(w, h)) return ZJ_ERR_ARG;
     if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
     if (color_is_identity(q)) return ZJ_OK;
     const unsigned wh[2] = {w, h}, pitch = layout == ZJ_LAYOUT_CHW ? w : 3 * w;
     const uint8_t* in = img;
     ZJ_HIP(c, hipSetDevice(c->device));
     int rc = color_launches(c, 1, &in, wh, &pitch, layout == ZJ_LAYOUT_CHW, q, &img, &pitch, c->stream);
-    if (rc) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 /* ---- component planes to RGB ------------------------------------------------------ */
@@ -2198,25 +2064,21 @@ static int planes_to_rgb(zj_ctx* c, size_t n, const uint8_t* const* d_p0, const 
 {
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_p0 || !d_p1 || !d_p2 || !in_wh || !ratios || !d_out) return ZJ_ERR_ARG;
     if (layout != ZJ_LAYOUT_HWC && layout != ZJ_LAYOUT_CHW) return ZJ_ERR_ARG;
-    const unsigned bpp = layout == ZJ_LAYOUT_CHW ? 1 : 3;
-    std::vector<unsigned> pp(3 * n), op(n);
+    std::vector<unsigned> pp(3 * n), op;
     std::vector<uint32_t> geo(n);
+    if (!stage_sizes(n, in_wh) || !stage_side(n, d_out, out_pitch, in_wh, layout == ZJ_LAYOUT_CHW ? 1 : 3, op)) return ZJ_ERR_ARG;
     for (size_t f = 0; f < n; f++) {
-        const unsigned w = in_wh[2 * f], h = in_wh[2 * f + 1];
-        if (!d_p0[f] || !d_p1[f] || !d_p2[f] || !d_out[f] || w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+        if (!d_p0[f] || !d_p1[f] || !d_p2[f]) return ZJ_ERR_ARG;
         geo[f] = 0;
         for (int k = 0; k < 3; k++) {
-            const unsigned rx = ratios[6 * f + 2 * k], ry = ratios[6 * f + 2 * k + 1];
-            if ((rx != 1 && rx != 2 && rx != 4) || (ry != 1 && ry != 2 && ry != 4)) return ZJ_ERR_ARG;
-            const unsigned px = phases ? phases[6 * f + 2 * k] : 0, py = phases ? phases[6 * f + 2 * k + 1] : 0;
-            if (px >= rx || py >= ry) return ZJ_ERR_ARG;
-            const unsigned pw = (px + w + rx - 1) / rx; // samples of a row that the image shows
-            pp[3 * f + k] = pitches && pitches[3 * f + k] ? pitches[3 * f + k] : pw;
-            if (pp[3 * f + k] < pw || pp[3 * f + k] > (1u << 24)) return ZJ_ERR_ARG;
-            geo[f] |= planes_geo(rx >> 1, ry >> 1, (int)px, (int)py) << (8 * k); // (log2 of 1, 2, 4: 0, 1, 2)
+            const size_t r = 6 * f + 2 * k;
+            unsigned pw;
+            uint32_t g;
+            if (!planes_component(in_wh[2 * f], ratios[r], ratios[r + 1], phases ? phases[r] : 0, phases ? phases[r + 1] : 0, pw, g) ||
+                !stage_pitch(pitches, 3 * f + k, pw, pp[3 * f + k]))
+                return ZJ_ERR_ARG;
+            geo[f] |= g << (8 * k);
         }
-        op[f] = out_pitch && out_pitch[f] ? out_pitch[f] : w * bpp;
-        if (op[f] < w * bpp || op[f] > (1u << 24)) return ZJ_ERR_ARG;
     }
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -2241,11 +2103,7 @@ int zjint_planes_to_rgb_one(zj_ctx* c, const uint8_t* const planes[3], unsigned 
     const unsigned wh[2] = {w, h};
     int rc = planes_to_rgb(c, 1, &planes[0], &planes[1], &planes[2], wh, ratios, phases, nullptr, stored_rgb, layout, &d_out, nullptr,
                            nullptr);
-    if (rc) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 // Library-internal (zj_jpeg.cpp: the decoder's oriented outputs): one image turned on the context stream, tight on both
@@ -2256,11 +2114,7 @@ int zjint_orient_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int c
     const unsigned wh[2] = {w, h};
     const uint8_t oo = (uint8_t)o;
     int rc = zj_orient_device(c, 1, &in, wh, nullptr, channels, in_layout, &oo, &d_out, nullptr, nullptr);
-    if (rc) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 /* ---- reduced-size decode -------------------------------------------------------- */
@@ -2359,36 +2213,22 @@ int zj_to_tensor_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, unsigne
 {
     if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !d_out) return ZJ_ERR_ARG;
     if (!((in_channels == 1 && (channels == 1 || channels == 3)) || (in_channels == 3 && channels == 3))) return ZJ_ERR_ARG;
-    if (w == 0 || h == 0 || w > 65535 || h > 65535) return ZJ_ERR_ARG;
+    if (!stage_size(w, h)) return ZJ_ERR_ARG;
     const int E = resize_elem_bytes(dtype);
     if (!E || (out_layout != ZJ_TENSOR_NCHW && out_layout != ZJ_TENSOR_NHWC)) return ZJ_ERR_ARG;
     if ((uintptr_t)d_out % (uintptr_t)E) return ZJ_ERR_ARG; // (the kernel's blocks are counted from element boundaries)
-    ToTensorParams p{};
-    if (!kernel_factors(scale, bias, channels, p.scale, p.bias)) return ZJ_ERR_ARG;
-    const unsigned row = w * (unsigned)in_channels;
-    std::vector<unsigned> pitch(n);
-    for (size_t f = 0; f < n; f++) {
-        if (!d_in[f]) return ZJ_ERR_ARG;
-        pitch[f] = in_pitch && in_pitch[f] ? in_pitch[f] : row;
-        if (pitch[f] < row || pitch[f] > (1u << 24)) return ZJ_ERR_ARG;
-    }
+    StageTensor t{(uint8_t*)d_out, (size_t)channels * w * h * (size_t)E, (int)w, (int)h, dtype, out_layout == ZJ_TENSOR_NHWC, {}, {}};
+    if (!kernel_factors(scale, bias, channels, t.s, t.b)) return ZJ_ERR_ARG;
+    std::vector<unsigned> pitch;
+    if (!stage_side(n, d_in, in_pitch, [&](size_t) { return (size_t)w * in_channels; }, pitch)) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    p.w = (int)w; p.h = (int)h; p.cin = in_channels; p.cout = channels; p.dtype = dtype; p.nhwc = out_layout == ZJ_TENSOR_NHWC;
-    const size_t img_bytes = (size_t)channels * w * h * (size_t)E;
-    for (size_t f0 = 0; f0 < n; f0 += TT_BATCH) {
-        const int m = (int)(n - f0 < (size_t)TT_BATCH ? n - f0 : (size_t)TT_BATCH);
-        p.nimg = m;
-        p.out = (uint64_t)(uintptr_t)((uint8_t*)d_out + f0 * img_bytes);
-        for (int k = 0; k < TT_BATCH / 32; k++) p.flip[k] = 0;
-        for (int i = 0; i < TT_BATCH; i++) {
-            p.in[i] = i < m ? (uint64_t)(uintptr_t)d_in[f0 + i] : 0;
-            p.pitch[i] = i < m ? pitch[f0 + i] : 0;
-            if (i < m && flip && flip[f0 + i]) p.flip[i >> 5] |= 1u << (i & 31);
-        }
+    ToTensorParams p{};
+    return stage_batches<TT_BATCH>(n, [&](size_t f0, int m) {
+        pack_to_tensor(p, d_in, pitch.data(), flip, in_channels, channels, t, f0, m);
         ZJ_HIP(c, launch_to_tensor(p, st));
-    }
-    return ZJ_OK;
+        return ZJ_OK;
+    });
 }
 
 // Library-internal (zj_jpeg.cpp: the crop-tensor file calls of the files that pass through u8 stages): one tight image of the
@@ -2398,11 +2238,7 @@ int zjint_to_tensor_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, in
 {
     const uint8_t fl = flip ? 1 : 0;
     int rc = zj_to_tensor_device(c, 1, &in, w, h, nullptr, in_channels, channels, dtype, out_layout, scale, bias, &fl, d_out, nullptr);
-    if (rc) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 // ... and the warp of that image under the integers q; w == 0: there is no image, the output is all fill
@@ -2411,7 +2247,7 @@ int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int cha
                    void* d_out)
 {
     if (!c || !q || !d_out || (w != 0 && !in) || (channels != 1 && channels != 3)) return ZJ_ERR_ARG;
-    if (w != 0 && (h == 0 || w > 65535 || h > 65535)) return ZJ_ERR_ARG;
+    if (w != 0 && !stage_size(w, h)) return ZJ_ERR_ARG;
     ResizeOut ro = resize_out(out_w, out_h, dtype, out_layout, scale, bias, nullptr, ZJ_RESIZE_BILINEAR, d_out);
     int rc = resize_out_args(ro, channels);
     if (rc) return rc;
@@ -2421,11 +2257,8 @@ int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int cha
     if (w == 0 && edge != ZJ_WARP_FILL) return ZJ_ERR_ARG;
     ZJ_HIP(c, hipSetDevice(c->device));
     const unsigned wh[2] = {w, h}, pitch = w * (unsigned)channels;
-    if ((rc = warp_launches(c, 1, &in, wh, &pitch, q, ro, wt, 0, c->stream))) return rc;
-    if (!c->rz_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->rz_done, hipEventDisableTiming));
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    rc = warp_launches(c, 1, &in, wh, &pitch, q, ro, wt, 0, c->stream);
+    return rc ? rc : one_image_done(c);
 }
 
 int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int channels, int in_layout, unsigned out_w,
@@ -2436,10 +2269,7 @@ int zjint_resize_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned h, int c
     const uint8_t fl = flip ? 1 : 0;
     int rc = zj_resize_filtered_device(c, 1, &in, wh, nullptr, channels, in_layout, out_w, out_h, dtype, out_layout, scale,
                                        bias, &fl, filter, d_out, nullptr);
-    if (rc) return rc;
-    if ((rc = resize_scratch_done(c, c->stream))) return rc;
-    ZJ_HIP(c, hipStreamSynchronize(c->stream));
-    return ZJ_OK;
+    return rc ? rc : one_image_done(c);
 }
 
 int zj_time_decode_device(zj_ctx* c, const zj_frame_desc* d, size_t nframes, const int16_t* d_y,

@@ -576,6 +576,16 @@ def _floats(v):
     return (C.c_float * len(v))(*[float(x) for x in v]) if v is not None else None
 
 
+def _wh(sizes):
+    """(w, h) pairs as the unsigned array of a stage call"""
+    return (C.c_uint * (2 * len(sizes)))(*[int(v) for s in sizes for v in s])
+
+
+def _pit(v, n):
+    """one pitch for each of n images (None: all tight)"""
+    return (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+
+
 def _flips(v, n):
     if v is None:
         return None
@@ -751,10 +761,8 @@ class Context:
         n = len(d_in)
         if len(sizes) != n or (pitches is not None and len(pitches) != n):
             raise ValueError("one size (and pitch) per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
-        pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
-        args = (self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, in_layout, out_w, out_h, dtype, out_layout,
-                _floats(scale), _floats(bias), _flips(flips, n))
+        args = (self._h, n, (C.c_void_p * n)(*d_in), _wh(sizes), _pit(pitches, n), channels, in_layout, out_w, out_h, dtype,
+                out_layout, _floats(scale), _floats(bias), _flips(flips, n))
         if filt != RESIZE_BILINEAR:
             _check(lib().zj_resize_filtered_device(*args, filt, d_out, stream), "zj_resize_filtered_device", self._h)
         else:
@@ -768,10 +776,9 @@ class Context:
         n = len(d_in)
         if pitches is not None and len(pitches) != n:
             raise ValueError("one pitch per image")
-        pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
-        _check(lib().zj_to_tensor_device(self._h, n, (C.c_void_p * n)(*d_in), w, h, pit, in_channels, channels, dtype, out_layout,
-                                         _floats(scale), _floats(bias), _flips(flips, n), d_out, stream), "zj_to_tensor_device",
-               self._h)
+        _check(lib().zj_to_tensor_device(self._h, n, (C.c_void_p * n)(*d_in), w, h, _pit(pitches, n), in_channels, channels, dtype,
+                                         out_layout, _floats(scale), _floats(bias), _flips(flips, n), d_out, stream),
+               "zj_to_tensor_device", self._h)
 
     def warp_device(self, d_in, sizes, channels, matrices, out_w, out_h, dtype, out_layout, d_out, scale=None, bias=None,
                     fill=None, edge="fill", pitches=None, stream=None):
@@ -782,10 +789,9 @@ class Context:
         n = len(d_in)
         if len(sizes) != n or (pitches is not None and len(pitches) != n):
             raise ValueError("one size (and pitch) per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
-        pit = (C.c_uint * n)(*[int(v) for v in pitches]) if pitches is not None else None
-        _check(lib().zj_warp_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, _matrices(matrices, n), out_w, out_h,
-                                    dtype, out_layout, _floats(scale), _floats(bias), _fill(fill), warp_edge(edge), d_out, stream),
+        _check(lib().zj_warp_device(self._h, n, (C.c_void_p * n)(*d_in), _wh(sizes), _pit(pitches, n), channels, _matrices(matrices, n),
+                                    out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias), _fill(fill), warp_edge(edge),
+                                    d_out, stream),
                "zj_warp_device", self._h)
 
     def decode_crops_warped_device(self, desc, d_y, d_cb, d_cr, matrices, out_w, out_h, dtype, out_layout, d_out, scale=None,
@@ -809,11 +815,9 @@ class Context:
         n = len(d_in)
         if len(sizes) != n or len(d_out) != n or (orientations is not None and len(orientations) != n):
             raise ValueError("one size, orientation and output per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
-        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
         ori = (C.c_uint8 * n)(*[int(o) for o in orientations]) if orientations is not None else None
-        _check(lib().zj_orient_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), channels, in_layout, ori,
-                                      (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_orient_device", self._h)
+        _check(lib().zj_orient_device(self._h, n, (C.c_void_p * n)(*d_in), _wh(sizes), _pit(in_pitches, n), channels, in_layout, ori,
+                                      (C.c_void_p * n)(*d_out), _pit(out_pitches, n), stream), "zj_orient_device", self._h)
 
     def gray_to_rgb_device(self, d_in, sizes, out_layout, d_out, in_pitches=None, out_pitches=None, stream=None):
         """One u8 plane each -> a 3-channel u8 image with R = G = B (zj_gray_to_rgb_device): d_in = device
@@ -823,10 +827,8 @@ class Context:
         n = len(d_in)
         if len(sizes) != n or len(d_out) != n:
             raise ValueError("one size and output per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
-        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
-        _check(lib().zj_gray_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), out_layout,
-                                           (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_gray_to_rgb_device", self._h)
+        _check(lib().zj_gray_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_in), _wh(sizes), _pit(in_pitches, n), out_layout,
+                                           (C.c_void_p * n)(*d_out), _pit(out_pitches, n), stream), "zj_gray_to_rgb_device", self._h)
 
     def cmyk_to_rgb_device(self, d_a, d_k, sizes, layout, d_out, inverted=None, a_pitches=None, k_pitches=None, out_pitches=None,
                            stream=None):
@@ -838,11 +840,9 @@ class Context:
         n = len(d_a)
         if len(d_k) != n or len(sizes) != n or len(d_out) != n or (inverted is not None and len(inverted) != n):
             raise ValueError("one plane, size, inverted flag and output per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
-        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
         inv = (C.c_uint8 * n)(*[1 if v else 0 for v in inverted]) if inverted is not None else None
-        _check(lib().zj_cmyk_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_a), (C.c_void_p * n)(*d_k), wh, pit(a_pitches),
-                                           pit(k_pitches), layout, inv, (C.c_void_p * n)(*d_out), pit(out_pitches), stream),
+        _check(lib().zj_cmyk_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_a), (C.c_void_p * n)(*d_k), _wh(sizes), _pit(a_pitches, n),
+                                           _pit(k_pitches, n), layout, inv, (C.c_void_p * n)(*d_out), _pit(out_pitches, n), stream),
                "zj_cmyk_to_rgb_device", self._h)
 
     def color_device(self, d_in, sizes, layout, matrices, d_out, in_pitches=None, out_pitches=None, stream=None):
@@ -853,10 +853,9 @@ class Context:
         n = len(d_in)
         if len(sizes) != n or len(d_out) != n or matrices is None:
             raise ValueError("one size, matrix and output per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
-        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
-        _check(lib().zj_color_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), layout, _colors(matrices, n),
-                                     (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_color_device", self._h)
+        _check(lib().zj_color_device(self._h, n, (C.c_void_p * n)(*d_in), _wh(sizes), _pit(in_pitches, n), layout,
+                                     _colors(matrices, n), (C.c_void_p * n)(*d_out), _pit(out_pitches, n), stream),
+               "zj_color_device", self._h)
 
     def planes_to_rgb_device(self, d_p0, d_p1, d_p2, sizes, ratios, layout, d_out, stored_rgb=False, pitches=None,
                              out_pitches=None, stream=None):
@@ -869,15 +868,14 @@ class Context:
         n = len(d_p0)
         if len(d_p1) != n or len(d_p2) != n or len(sizes) != n or len(ratios) != n or len(d_out) != n:
             raise ValueError("three planes, a size, three ratio pairs and an output per image")
-        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
         flat = [int(v) for r in ratios for pair in r for v in pair]
         if len(flat) != 6 * n or any(v < 0 or v > 255 for v in flat):
             raise ValueError("ratios: three (rx, ry) pairs per image")
         rt = (C.c_uint8 * (6 * n))(*flat)
         pit = (C.c_uint * (3 * n))(*[int(v) for p in pitches for v in p]) if pitches is not None else None
-        opit = (C.c_uint * n)(*[int(x) for x in out_pitches]) if out_pitches is not None else None
         _check(lib().zj_planes_to_rgb_device(self._h, n, (C.c_void_p * n)(*d_p0), (C.c_void_p * n)(*d_p1), (C.c_void_p * n)(*d_p2),
-                                             wh, rt, pit, 1 if stored_rgb else 0, layout, (C.c_void_p * n)(*d_out), opit, stream),
+                                             _wh(sizes), rt, pit, 1 if stored_rgb else 0, layout, (C.c_void_p * n)(*d_out),
+                                             _pit(out_pitches, n), stream),
                "zj_planes_to_rgb_device", self._h)
 
     def decode_crops_resized_device(self, desc, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out, scale=None,
