@@ -45,9 +45,10 @@ class FrameDesc(C.Structure):  # zj_frame_desc (include/zjhip.h)
                 ("out_pitch", C.c_uint32)]
 
 
-def decode_planes(frame, planes, nframes=1, zero_fill=1, poison=0xAA, flags=0, out_layout=0, out_pitch=0):
+def decode_planes(frame, planes, nframes=1, zero_fill=1, poison=0xAA, flags=0, out_layout=0, out_pitch=0, out=None):
     """frame: the oracle's zjo_frame (or anything with the same leading fields); flags / out_layout / out_pitch are the
-    extension fields of zj_frame_desc.  With out_pitch the result has out_pitch bytes per row (the padding keeps `poison`)."""
+    extension fields of zj_frame_desc.  With out_pitch the result has out_pitch bytes per row (the padding keeps `poison`).
+    out: the caller's own buffer of that size, decoded into as it is (a far pitch: gigabytes, committed as they are touched)."""
     arrs = [np.ascontiguousarray(p, np.int16) for p in planes]
     while len(arrs) < 3:
         arrs.append(np.zeros(8, np.int16))
@@ -59,7 +60,10 @@ def decode_planes(frame, planes, nframes=1, zero_fill=1, poison=0xAA, flags=0, o
     frame = d
     w, h = frame.width, frame.height
     ncomp = {0: 3, 1: 1, 2: 3, 5: 4, 6: 4}[frame.out_colorspace]
-    out = np.full(nframes * (out_pitch * h * (3 if out_layout == 1 and ncomp == 3 else 1) if out_pitch else w * h * ncomp), poison, np.uint8)
+    nbytes = nframes * (out_pitch * h * (3 if out_layout == 1 and ncomp == 3 else 1) if out_pitch else w * h * ncomp)
+    if out is None:
+        out = np.full(nbytes, poison, np.uint8)
+    assert out.dtype == np.uint8 and out.size == nbytes and out.flags.c_contiguous
     rc = lib().zje_decode_planes(C.byref(frame), C.c_size_t(nframes), C.c_void_p(arrs[0].ctypes.data),
                                  C.c_void_p(arrs[1].ctypes.data), C.c_void_p(arrs[2].ctypes.data),
                                  C.c_void_p(out.ctypes.data), C.c_int(zero_fill))

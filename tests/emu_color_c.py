@@ -38,17 +38,18 @@ def fixed(m):
     return [int(v) for v in q] if ok else None
 
 
-def color(src, in_offsets, sizes, in_pitches, chw, qs, arena, out_offsets, out_pitches):
+def color(src, in_offsets, sizes, in_pitches, chw, qs, arena, out_offsets, out_pitches, zeros=np.zeros):
     """The launches of one call: inputs at src[in_offsets[i]:] (src may be the arena: in place), sizes = (w, h), qs = 12
     integers each, outputs at arena[out_offsets[i]:].  Returns (read map of src, write map of the arena, loads and stores that
     fell outside them)."""
+    # zeros: the allocator of the maps (far_cases.zeros for arenas of gigabytes: no huge pages)
     n = len(sizes)
     arr = lambda v: (C.c_uint * n)(*v)
     wh = (C.c_uint * (2 * n))(*[v for sz in sizes for v in sz])
     q = (C.c_int32 * (12 * n))(*[v for one in qs for v in one])
     ins = (C.c_void_p * n)(*[src.ctypes.data + off for off in in_offsets])
     outs = (C.c_void_p * n)(*[arena.ctypes.data + off for off in out_offsets])
-    rmap, wmap = np.zeros(src.size, np.uint8), np.zeros(arena.size, np.uint8)
+    rmap, wmap = zeros(src.size, np.uint8), zeros(arena.size, np.uint8)
     outside = lib().zjcl_color(n, ins, wh, arr(in_pitches), 1 if chw else 0, q, outs, arr(out_pitches), C.c_void_p(src.ctypes.data),
                                src.size, C.c_void_p(rmap.ctypes.data), C.c_void_p(arena.ctypes.data), arena.size,
                                C.c_void_p(wmap.ctypes.data))

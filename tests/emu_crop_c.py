@@ -44,20 +44,27 @@ def crop_out_len(d, w, h, out_pitch=0):
     return lib().zjec_crop_out_len(C.byref(d), w, h, out_pitch)
 
 
-def decode_crops(d, frames, origins, w, h, out_pitch=0, poison=0xAA, stage_poison=0x5C, guard=64):
+def decode_crops(d, frames, origins, w, h, out_pitch=0, poison=0xAA, stage_poison=0x5C, guard=64, outs=None):
     """frames: list of [y, cb, cr] int16 arrays; returns (rc, outs) -- outs[f] = the crop bytes (crop_out_len), with
-    `guard` poisoned bytes in front and behind checked untouched"""
+    `guard` poisoned bytes in front and behind checked untouched.  outs: the caller's own buffers of crop_out_len bytes,
+    decoded into as they are (a far pitch: gigabytes, committed as they are touched) and returned"""
     n = len(frames)
     arrs = [[np.ascontiguousarray(p, np.int16) for p in fr] + [np.zeros(8, np.int16)] * (3 - len(fr)) for fr in frames]
     ln = crop_out_len(d, w, h, out_pitch)
-    bufs = [np.full(max(ln, 1) + 2 * guard, poison, np.uint8) for _ in range(n)]
+    if outs is not None:
+        assert len(outs) == n and all(b.dtype == np.uint8 and b.size == ln and b.flags.c_contiguous for b in outs)
+        bufs, guard = outs, 0
+    else:
+        bufs = [np.full(max(ln, 1) + 2 * guard, poison, np.uint8) for _ in range(n)]
     ptr = lambda a, off=0: C.c_void_p(a.ctypes.data + off)
     P = C.c_void_p * n
     ys, cbs, crs = P(*[a[0].ctypes.data for a in arrs]), P(*[a[1].ctypes.data for a in arrs]), P(*[a[2].ctypes.data for a in arrs])
-    outs = P(*[b.ctypes.data + guard for b in bufs])
+    optr = P(*[b.ctypes.data + guard for b in bufs])
     org = (C.c_uint * (2 * n))(*[int(v) for xy in origins for v in xy])
-    rc = lib().zjec_decode_crops(C.byref(d), C.c_size_t(n), ys, cbs, crs, org, C.c_uint(w), C.c_uint(h), outs,
+    rc = lib().zjec_decode_crops(C.byref(d), C.c_size_t(n), ys, cbs, crs, org, C.c_uint(w), C.c_uint(h), optr,
                                  C.c_uint(out_pitch), C.c_int(stage_poison))
+    if outs is not None:
+        return rc, outs
     for b in bufs:
         assert (b[:guard] == poison).all() and (b[guard + ln:] == poison).all(), "a crop wrote outside its bytes"
     return rc, [b[guard:guard + ln] for b in bufs]

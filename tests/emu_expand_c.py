@@ -30,16 +30,17 @@ def params_bytes():
     return lib().zjex_params_bytes()
 
 
-def expand(in_addrs, sizes, in_pitches, out_chw, arena, out_offsets, out_pitches):
+def expand(in_addrs, sizes, in_pitches, out_chw, arena, out_offsets, out_pitches, zeros=np.zeros):
     """The launches of one call: in_addrs = addresses of the planes' first bytes, sizes = (w, h), outputs at
     arena[out_offsets[i]:] at out_pitches[i].  Returns (write map of the arena, stores that fell outside it)."""
+    # zeros: the allocator of the maps (far_cases.zeros for arenas of gigabytes: no huge pages)
     n = len(in_addrs)
     ins = (C.c_void_p * n)(*in_addrs)
     wh = (C.c_uint * (2 * n))(*[v for sz in sizes for v in sz])
     ip = (C.c_uint * n)(*in_pitches)
     op = (C.c_uint * n)(*out_pitches)
     outs = (C.c_void_p * n)(*[arena.ctypes.data + off for off in out_offsets])
-    wmap = np.zeros(arena.size, np.uint8)
+    wmap = zeros(arena.size, np.uint8)
     outside = lib().zjex_expand(n, ins, wh, ip, 1 if out_chw else 0, outs, op, C.c_void_p(arena.ctypes.data), arena.size,
                                 C.c_void_p(wmap.ctypes.data))
     assert outside >= 0, "the emulation refused its arguments"

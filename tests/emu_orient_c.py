@@ -27,9 +27,10 @@ def batch():
     return lib().zjeo_batch()
 
 
-def orient(images, sizes, in_pitches, channels, in_chw, orientations, arena, out_offsets, out_pitches):
+def orient(images, sizes, in_pitches, channels, in_chw, orientations, arena, out_offsets, out_pitches, zeros=np.zeros):
     """One launch: images = uint8 buffers (each in its layout at its pitch), sizes = STORED (w, h), outputs at
     arena[out_offsets[i]:] at out_pitches[i].  Returns (write map of the arena, stores that fell outside it)."""
+    # zeros: the allocator of the maps (far_cases.zeros for arenas of gigabytes: no huge pages)
     n = len(images)
     ins = (C.c_void_p * n)(*[im.ctypes.data for im in images])
     wh = (C.c_uint * (2 * n))(*[v for sz in sizes for v in sz])
@@ -37,7 +38,7 @@ def orient(images, sizes, in_pitches, channels, in_chw, orientations, arena, out
     op = (C.c_uint * n)(*out_pitches)
     oo = (C.c_uint8 * n)(*orientations)
     outs = (C.c_void_p * n)(*[arena.ctypes.data + off for off in out_offsets])
-    wmap = np.zeros(arena.size, np.uint8)
+    wmap = zeros(arena.size, np.uint8)
     outside = lib().zjeo_orient(n, ins, wh, ip, channels, 1 if in_chw else 0, oo, outs, op, C.c_void_p(arena.ctypes.data),
                                 arena.size, C.c_void_p(wmap.ctypes.data))
     assert outside >= 0, "the emulation refused its arguments"

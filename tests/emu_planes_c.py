@@ -31,10 +31,11 @@ def params_bytes():
     return lib().zjpl_params_bytes()
 
 
-def combine(src, needed, plane_offsets, plane_pitches, sizes, geos, stored_rgb, chw, arena, out_offsets, out_pitches):
+def combine(src, needed, plane_offsets, plane_pitches, sizes, geos, stored_rgb, chw, arena, out_offsets, out_pitches, zeros=np.zeros):
     """The launches of one call: planes at src[plane_offsets[i][c]:] at plane_pitches[i][c], sizes = (w, h) of the outputs,
     geos = ((rx, ry, px, py) x 3) each, outputs at arena[out_offsets[i]:] at out_pitches[i]; needed = the bytes of src that may
     be read.  Returns (write map of the arena, stores that fell outside it, loads that touched a byte not needed)."""
+    # zeros: the allocator of the maps (far_cases.zeros for arenas of gigabytes: no huge pages)
     n = len(sizes)
     planes = (C.c_void_p * (3 * n))(*[src.ctypes.data + o for offs in plane_offsets for o in offs])
     pit = (C.c_uint * (3 * n))(*[p for ps in plane_pitches for p in ps])
@@ -42,7 +43,7 @@ def combine(src, needed, plane_offsets, plane_pitches, sizes, geos, stored_rgb, 
     geo = (C.c_uint8 * (12 * n))(*[v for g in geos for comp in g for v in comp])
     outs = (C.c_void_p * n)(*[arena.ctypes.data + off for off in out_offsets])
     opit = (C.c_uint * n)(*out_pitches)
-    wmap = np.zeros(arena.size, np.uint8)
+    wmap = zeros(arena.size, np.uint8)
     need = np.ascontiguousarray(needed, np.uint8)
     outside = lib().zjpl_combine(n, planes, pit, wh, geo, 1 if stored_rgb else 0, 1 if chw else 0, outs, opit,
                                  C.c_void_p(arena.ctypes.data), arena.size, C.c_void_p(wmap.ctypes.data),

@@ -5,6 +5,7 @@
 // TEST INFRASTRUCTURE ONLY; nothing of HIP, never linked into libzjhip.so.  No pointer in here is ever followed.
 #define ZJ_EMU 1
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <cmath>
@@ -15,6 +16,7 @@
 using namespace zj;
 
 static int g_fail = 0;
+static unsigned g_pitch_max = 1u << 24; // argv[1]: the limit the tests assume
 #define CHECK(x)                                                                         \
     do {                                                                                 \
         if (!(x) && g_fail++ < 20) printf("FAILED line %d: %s\n", __LINE__, #x);         \
@@ -258,13 +260,13 @@ static void rules()
     CHECK(!stage_size(0, 1) && !stage_size(1, 0) && stage_size(1, 1) && stage_size(65535, 65535) && !stage_size(65536, 65535));
     // NULL behind a good image, on the side that reads and the side that writes
     CHECK(!stage_images(2, hole, w44, nullptr, 3, r) && !stage_side(2, hole, nullptr, w44, 3, r) && stage_side(2, two, nullptr, w44, 3, r));
-    // pitches: nullptr or 0 is tight, from a row up to 2^24
-    const unsigned p11[1] = {11}, p12[1] = {12}, p0[1] = {0}, p3[1] = {3}, p4[1] = {4}, top[1] = {1u << 24}, over[1] = {(1u << 24) + 1};
+    // pitches: nullptr or 0 is tight, from a row up to 2^24 (g_pitch_max: what the far-offset tests take the limit to be)
+    const unsigned p11[1] = {11}, p12[1] = {12}, p0[1] = {0}, p3[1] = {3}, p4[1] = {4}, top[1] = {g_pitch_max}, over[1] = {g_pitch_max + 1};
     CHECK(!stage_images(1, one, w44, p11, 3, r) && stage_images(1, one, w44, p12, 3, r) && r[0] == 12);
     CHECK(stage_images(1, one, w44, p0, 3, r) && r[0] == 12);
     CHECK(!stage_side(1, one, p11, w44, 3, r) && stage_side(1, one, p12, w44, 3, r));
     CHECK(!stage_side(1, one, p3, w44, 1, r) && stage_side(1, one, p4, w44, 1, r) && r[0] == 4); // (planes: a row is w bytes)
-    CHECK(stage_side(1, one, top, w44, 3, r) && r[0] == 1u << 24 && !stage_side(1, one, over, w44, 3, r));
+    CHECK(g_pitch_max == 1u << 24 && stage_side(1, one, top, w44, 3, r) && r[0] == g_pitch_max && !stage_side(1, one, over, w44, 3, r));
     const unsigned second[2] = {0, 11};
     CHECK(!stage_images(2, two, w44, second, 3, r)); // (behind a good image)
     // orient: the output's rows are the displayed width -- a 4 x 9 image turned on its side shows rows of 9
@@ -308,8 +310,9 @@ static void rules()
     CHECK(warp_fill(fill, 3) == 0x030201u && warp_fill(fill, 1) == 1u && warp_fill(nullptr, 3) == 0);
 }
 
-int main()
+int main(int argc, char** argv)
 {
+    if (argc > 1) g_pitch_max = (unsigned)strtoul(argv[1], nullptr, 10);
     sizes<ORIENT_BATCH>(orient);
     sizes<EXPAND_BATCH>(expand);
     sizes<CMYK_BATCH>(cmyk);
