@@ -30,6 +30,11 @@ def jitter():
 
 
 MATRICES = (cm.IDENTITY, cm.BGR, cm.GRAY, jitter(), cm.NEGATIVE)
+# the ends of what the stage takes: +-16 / +-4096 in every entry, and mixed signs beside entries of one unit of 1/65536 -- the
+# largest 24-bit products and sums color_mad (zj_color.h) forms
+EXTREMES = (np.array([[16, 16, 16, 4096]] * 3, float), np.array([[-16, -16, -16, -4096]] * 3, float),
+            np.array([[16, -16, 16, -4096], [-16, 16, -16, 4096], [1 / 65536, -1 / 65536, 0.5 / 65536, 0.5]], float))
+EXTREME_WIDTHS = (1, 15, 16, 17, 33)
 
 
 def matrix():

@@ -21,9 +21,9 @@ def aligned(n):
     return buf[off:off + n]
 
 
-def run_call(rng, cases, chw, in_place, first=0):
+def run_call(rng, cases, chw, in_place, first=0, matrices=cc.MATRICES):
     """one call over `cases`; returns the output arena"""
-    lay = cc.Layout(rng, cases, chw, in_place, first)
+    lay = cc.Layout(rng, cases, chw, in_place, first, matrices)
     arena = aligned(lay.arena_len)
     arena[:] = lay.arena0
     if in_place:
@@ -109,9 +109,7 @@ def test_every_byte_value_under_every_matrix():
     rows = [np.stack([v, v[::-1], np.roll(v, 77)], -1), np.stack([v, np.zeros_like(v), np.full_like(v, 255)], -1),
             np.stack([np.full_like(v, 255), v, v], -1), np.stack([np.zeros_like(v), np.zeros_like(v), v], -1)]
     img = np.stack(rows)                                    # [4, 256, 3]
-    extremes = [np.array([[16, 16, 16, 4096]] * 3, float), np.array([[-16, -16, -16, -4096]] * 3, float),
-                np.array([[16, -16, 16, -4096], [-16, 16, -16, 4096], [1 / 65536, -1 / 65536, 0.5 / 65536, 0.5]], float)]
-    for m in list(cc.MATRICES) + extremes:
+    for m in list(cc.MATRICES) + list(cc.EXTREMES):
         q = ce.fixed(m)
         assert q == cm.fixed(m)
         src = aligned(img.size)
@@ -121,6 +119,16 @@ def test_every_byte_value_under_every_matrix():
         _, wmap, outside = ce.color(src, [0], [(256, 4)], [768], False, [q], arena, [64], [768])
         assert outside == 0 and wmap[64:64 + img.size].min() == 1 == wmap.max() and wmap[:64].max() == 0 == wmap[-64:].max()
         assert np.array_equal(arena[64:64 + img.size].reshape(img.shape), cm.apply_fixed(q, img))
+
+
+@pytest.mark.parametrize("in_place", [False, True], ids=["apart", "in_place"])
+@pytest.mark.parametrize("chw", [False, True], ids=["HWC", "CHW"])
+def test_the_extreme_matrices_over_the_widths_the_gpu_test_runs(chw, in_place):
+    """test_gpu_color.py's layout of color_cases.EXTREMES, lane by lane: both ends of the clamp are reached"""
+    cases = [(w, 3, 1, 13, (3 * i + k) % 16, (5 * i + 7 * k) % 16) for i, w in enumerate(cc.EXTREME_WIDTHS) for k in range(3)]
+    lay, arena = run_call(np.random.default_rng(112 + chw + 2 * in_place), cases, chw, in_place, matrices=cc.EXTREMES)
+    out = arena[lay.inside]
+    assert (out == 0).any() and (out == 255).any() and ((out > 0) & (out < 255)).any()
 
 
 def test_the_host_rule_equals_the_model_and_the_package():

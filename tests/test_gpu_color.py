@@ -76,8 +76,8 @@ def aligned_cuda(torch, n):
     return t[off:off + n]
 
 
-def stage_call(zj, ctx, torch, rng, cases, chw, in_place):
-    lay = cc.Layout(rng, cases, chw, in_place)
+def stage_call(zj, ctx, torch, rng, cases, chw, in_place, matrices=cc.MATRICES):
+    lay = cc.Layout(rng, cases, chw, in_place, matrices=matrices)
     arena = aligned_cuda(torch, lay.arena_len)
     arena.copy_(torch.from_numpy(lay.arena0))
     if in_place:
@@ -112,6 +112,17 @@ def test_stage_equals_the_model(zj, ctx, torch, chw, in_place):
     cases = stage_cases()
     assert len(cases) == 64  # (two launches)
     stage_call(zj, ctx, torch, np.random.default_rng(41 + chw + 2 * in_place), cases, chw, in_place)
+
+
+@pytest.mark.parametrize("in_place", [False, True], ids=["apart", "in_place"])
+@pytest.mark.parametrize("chw", [False, True], ids=["HWC", "CHW"])
+def test_stage_operand_extremes_equal_the_model(zj, ctx, torch, chw, in_place):
+    """color_cases.EXTREMES (+-16 / +-4096 in every entry; mixed signs beside entries of 1/65536): color_mad is __mul24 on the
+    device and a plain product in the emulation, so only this run shows the instruction at the ends of its operands.  Widths 1,
+    15, 16, 17, 33, every width under each of the three matrices, against color_model.apply_fixed."""
+    cases = [(w, 3, 1, 13, (3 * i + k) % 16, (5 * i + 7 * k) % 16) for i, w in enumerate(cc.EXTREME_WIDTHS) for k in range(3)]
+    assert len(cases) == 15 and [c[0] for c in cases[::3]] == list(cc.EXTREME_WIDTHS)   # case 3i + k: width i under matrix k
+    stage_call(zj, ctx, torch, np.random.default_rng(112 + chw + 2 * in_place), cases, chw, in_place, matrices=cc.EXTREMES)
 
 
 @pytest.mark.parametrize("chw", [False, True], ids=["HWC", "CHW"])

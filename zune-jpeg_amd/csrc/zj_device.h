@@ -982,7 +982,8 @@ ZJ_DEV BlockLoc locate(const Params& p, const TileId t, const int b, char* lds)
     if (!C::CHROMA || b >= C::NBLK) return L;
     // chroma: the full blocks of Cb, the full blocks of Cr, then the halo blocks (both components) -- with TWC = 16
     // that fills waves 0-1 with luma, wave 2 with chroma and leaves the 8 halo blocks alone in the last wave, which
-    // then runs the single-column transform (idct_block_packed_halo) as a wave-uniform branch
+    // then runs the single-column transform one lane per block column (halo_pass1 / halo_pass2: the exact 24-bit form,
+    // no guard) as a wave-uniform branch
     const int cb_ = b - C::NYB;
     constexpr int NFULL = C::CBR * C::TWC; // full chroma blocks per component
     int comp, brow, j;
