@@ -41,6 +41,12 @@ pub const ZJ_RESIZE_BILINEAR_AA: c_int = 1;
 pub const ZJ_RESIZE_BICUBIC_AA: c_int = 4;
 pub const ZJ_WARP_FILL: c_int = 0;
 pub const ZJ_WARP_REPLICATE: c_int = 1;
+pub const ZJ_TONE_IDENTITY: i32 = 0;
+pub const ZJ_TONE_INVERT: i32 = 1;
+pub const ZJ_TONE_POSTERIZE: i32 = 2;
+pub const ZJ_TONE_SOLARIZE: i32 = 3;
+pub const ZJ_TONE_AUTOCONTRAST: i32 = 4;
+pub const ZJ_TONE_EQUALIZE: i32 = 5;
 
 /// `ColorSpace`, `src/misc.rs:88-106` (same discriminants).
 #[repr(i32)]
@@ -355,6 +361,30 @@ extern "C" {
                                                                       max_prescale_log2: c_int, apply_orientation: c_int,
                                                                       color: *const f64, d_out: *mut c_void, out_cap: usize,
                                                                       rcs: *mut c_int) -> c_int;
+    pub fn zj_histogram_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                               channels: c_int, layout: c_int, d_hist: *mut c_uint, stream: *mut c_void) -> c_int;
+    pub fn zj_tone_luts_device(ctx: *mut zj_ctx, n: usize, channels: c_int, ops: *const i32, d_hist: *const c_uint, d_luts: *mut u8,
+                               stream: *mut c_void) -> c_int;
+    pub fn zj_lut_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                         channels: c_int, layout: c_int, d_luts: *const u8, d_out: *const *mut u8, out_pitch: *const c_uint,
+                         stream: *mut c_void) -> c_int;
+    pub fn zj_tone_device(ctx: *mut zj_ctx, n: usize, d_in: *const *const u8, in_wh: *const c_uint, in_pitch: *const c_uint,
+                          channels: c_int, layout: c_int, ops: *const i32, d_out: *const *mut u8, out_pitch: *const c_uint,
+                          stream: *mut c_void) -> c_int;
+    pub fn zj_decode_crops_resized_mixed_toned_device(ctx: *mut zj_ctx, descs: *const zj_frame_desc, nframes: usize,
+                                                      d_y: *const *const i16, d_cb: *const *const i16, d_cr: *const *const i16,
+                                                      windows: *const c_uint, out_w: c_uint, out_h: c_uint, dtype: c_int,
+                                                      out_layout: c_int, scale: *const f32, bias: *const f32, flip: *const u8,
+                                                      filter: c_int, max_prescale_log2: c_int, orientation: *const u8,
+                                                      color: *const f64, tone: *const i32, d_out: *mut c_void,
+                                                      stream: *mut c_void) -> c_int;
+    pub fn zj_decoder_finish_pixels_resized_crop_batch_toned_device(ds: *const *mut zj_decoder, n: usize, ctx: *mut zj_ctx,
+                                                                    windows: *const c_uint, out_w: c_uint, out_h: c_uint,
+                                                                    dtype: c_int, out_layout: c_int, scale: *const f32,
+                                                                    bias: *const f32, flip: *const u8, filter: c_int,
+                                                                    max_prescale_log2: c_int, apply_orientation: c_int,
+                                                                    color: *const f64, tone: *const i32, d_out: *mut c_void,
+                                                                    out_cap: usize, rcs: *mut c_int) -> c_int;
     pub fn zj_decoder_orientation(d: *const zj_decoder) -> c_int;
     pub fn zj_decoder_adobe_transform(d: *const zj_decoder) -> c_int;
     pub fn zj_decoder_stored_rgb(d: *const zj_decoder) -> c_int;

@@ -636,6 +636,72 @@ ZJ_API int zj_decode_crops_resized_mixed_colored_device(zj_ctx *ctx, const zj_fr
                                                         int max_prescale_log2, const uint8_t *orientation,
                                                         const double *color /* 12 per frame, or NULL */, void *d_out,
                                                         void *stream);
+/* ---- tone curves: invert, posterize, solarize, autocontrast, equalize, a caller's own table -------------
+ * A tone op is two int32, `op` and `param`, applied per channel to 1-channel or 3-channel u8 images.  Every table is byte for
+ * byte Pillow's ImageOps (invert, posterize, solarize, autocontrast with cutoff 0 and no ignore / mask / preserve_tone,
+ * equalize without a mask).  The table t[0..255] of a channel with bins h[0..255]:
+ *   ZJ_TONE_IDENTITY      param 0               t[i] = i
+ *   ZJ_TONE_INVERT        param 0               t[i] = 255 - i
+ *   ZJ_TONE_POSTERIZE     param bits 1..8       t[i] = i & ~(2^(8 - bits) - 1)
+ *   ZJ_TONE_SOLARIZE      param threshold 0..256   t[i] = i < threshold ? i : 255 - i
+ *   ZJ_TONE_AUTOCONTRAST  param 0   lo, hi = the first and the last non-empty bin; hi <= lo: the identity; else
+ *                         scale = 255.0 / (hi - lo), offset = -lo * scale, t[i] = clamp((int)(i * scale + offset), 0, 255) in IEEE
+ *                         doubles, the product and the sum rounded separately, the conversion toward zero
+ *   ZJ_TONE_EQUALIZE      param 0   at most one non-empty bin: the identity; step = (sum of h - h[hi]) / 255 (integers); step 0:
+ *                         the identity; else n = step / 2, and for i = 0..255: t[i] = min(n / step, 255), n += h[i] (n in 64 bits)
+ * Any other (op, param) is ZJ_ERR_ARG, checked for all images before anything is launched. */
+#define ZJ_TONE_IDENTITY 0
+#define ZJ_TONE_INVERT 1
+#define ZJ_TONE_POSTERIZE 2
+#define ZJ_TONE_SOLARIZE 3
+#define ZJ_TONE_AUTOCONTRAST 4
+#define ZJ_TONE_EQUALIZE 5
+/* The histograms of n u8 images in device memory, each of its own size: d_hist[i][c][v] (unsigned [n][channels][256]: 32-bit
+ * counters in device memory, 4-byte aligned) = the pixels of image i whose channel c is v.  The table is overwritten: zeroed on the stream in
+ * front of the kernel.  channels 1 or 3; `layout` ZJ_LAYOUT_HWC or ZJ_LAYOUT_CHW (three planes, pitch x height apart; one
+ * channel: either); in_wh (width and height, 1..65535); in_pitch bytes between rows (NULL or 0: tight, up to 2^24; the padding
+ * is never read and never counted).  Any addresses and pitches.  Integer sums through atomics: the result does not depend on
+ * the order of arrival.  One launch per 128 images.  Asynchronous on `stream` (NULL: the context's). */
+ZJ_API int zj_histogram_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                               int channels, int layout, unsigned *d_hist, void *stream);
+/* The tables of n ops (host memory, op and param per image): d_luts[i][c][.] (uint8 [n][channels][256], device memory) from
+ * ops[2i], ops[2i + 1] and, for ZJ_TONE_AUTOCONTRAST and ZJ_TONE_EQUALIZE, the bins d_hist[i][c][.] (as zj_histogram_device
+ * leaves them; NULL when no op needs them, ZJ_ERR_ARG when one does).  The ops travel in the kernel arguments, 256 images per
+ * launch; nothing comes back to the host.  Asynchronous on `stream`. */
+ZJ_API int zj_tone_luts_device(zj_ctx *ctx, size_t n, int channels, const int32_t *ops /* 2 per image */, const unsigned *d_hist,
+                               uint8_t *d_luts, void *stream);
+/* n u8 images through their own tables: out[c] = d_luts[i][c][in[c]] (uint8 [n][channels][256], device memory: what
+ * zj_tone_luts_device wrote, or the caller's own -- gamma, any tone curve).  Sizes, layout and pitches as zj_histogram_device;
+ * d_out[i] == d_in[i] with equal pitches is allowed (a lane reads its run before it writes it); any other overlap of an
+ * output with an input is the caller's error.  One launch per 128 images.  Asynchronous on `stream`. */
+ZJ_API int zj_lut_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                         int channels, int layout, const uint8_t *d_luts, uint8_t *const *d_out, const unsigned *out_pitch,
+                         void *stream);
+/* n u8 images each under its own op: zj_histogram_device of the images whose op needs one, zj_tone_luts_device,
+ * zj_lut_device, all on `stream` with the histograms and tables in the context's own buffer -- the kernel boundaries are the
+ * only ordering, nothing is synchronised.  A ZJ_TONE_IDENTITY image that is its own output (same address, same pitch) is left
+ * out of every launch, and a call of such images alone launches nothing; with a separate output it is copied (the lookup
+ * under the identity table).  The context's buffer holds channels x 1280 bytes for EVERY image of the launches (bins and
+ * table, also where the op needs no bins): 3840 bytes an RGB image, about 4 GB at the 2^20 images a call may have. */
+ZJ_API int zj_tone_device(zj_ctx *ctx, size_t n, const uint8_t *const *d_in, const unsigned *in_wh, const unsigned *in_pitch,
+                          int channels, int layout, const int32_t *ops /* 2 per image */, uint8_t *const *d_out,
+                          const unsigned *out_pitch, void *stream);
+/* zj_decode_crops_resized_mixed_colored_device with frame f's image under the tone op tone[2f], tone[2f + 1] behind the
+ * colour matrix and in front of the resize.  DEFINITION: image f equals zj_resize_filtered_device applied to zj_tone_device
+ * of EXACTLY the u8 image the call without `tone` resizes -- after the crop or reduced decode, the turn, the gray expand and,
+ * if `color` is given, the colour matrix -- in place in the context's buffer.  The order is fixed, colour first, then tone;
+ * another order is the stages' to build.  The histogram is that of the CROP the resize reads, not of the whole file: Pillow
+ * on the crop is the reference.  tone NULL: the call IS zj_decode_crops_resized_mixed_colored_device, byte for byte and launch
+ * for launch; ZJ_TONE_IDENTITY frames are left out of the tone launches.  All ops are checked before anything is launched
+ * (ZJ_ERR_ARG).  A ZJ_CS_GRAYSCALE output takes a tone op as its one channel; only a non-NULL color stays
+ * ZJ_ERR_UNSUPPORTED there. */
+ZJ_API int zj_decode_crops_resized_mixed_toned_device(zj_ctx *ctx, const zj_frame_desc *descs /* [nframes] */, size_t nframes,
+                                                      const int16_t *const *d_y, const int16_t *const *d_cb,
+                                                      const int16_t *const *d_cr, const unsigned *windows, unsigned out_w,
+                                                      unsigned out_h, int dtype, int out_layout, const float *scale,
+                                                      const float *bias, const uint8_t *flip, int filter, int max_prescale_log2,
+                                                      const uint8_t *orientation, const double *color /* 12 per frame, or NULL */,
+                                                      const int32_t *tone /* 2 per frame, or NULL */, void *d_out, void *stream);
 /* Times zj_decode_planes_device with HIP events recorded on the launch stream: *ms_total = `iters`
  * back-to-back launches between one event pair; *ms_each (optional) = mean over `iters` launches
  * each bracketed by its own event pair; *kernel_name = the dominant kernel. */
@@ -910,6 +976,21 @@ ZJ_API int zj_decoder_finish_pixels_resized_crop_batch_colored_device(zj_decoder
                                                                       int max_prescale_log2, int apply_orientation,
                                                                       const double *color /* 12 per file, or NULL */,
                                                                       void *d_out, size_t out_cap, int *rcs);
+/* zj_decoder_finish_pixels_resized_crop_batch_colored_device with file k's image under the tone op tone[2k], tone[2k + 1]
+ * (the ops above) behind the colour matrix and in front of the resize: the op acts on exactly the u8 image the
+ * call without it resizes -- after the crop or reduced decode, the turn, the gray expand, the CMYK combine, the plane combine
+ * and the colour matrix -- in place; its histogram is that of this crop, not of the whole file.  tone NULL: the call above.
+ * An op the stage refuses gives rcs[k] = ZJ_ERR_ARG and the decoder's error text; that file's image is untouched and the
+ * others are decoded.  A decoder whose output has one channel takes its op as one channel (a non-NULL color stays
+ * ZJ_ERR_UNSUPPORTED for that file). */
+ZJ_API int zj_decoder_finish_pixels_resized_crop_batch_toned_device(zj_decoder *const *ds, size_t n, zj_ctx *ctx,
+                                                                    const unsigned *windows, unsigned out_w, unsigned out_h,
+                                                                    int dtype, int out_layout, const float *scale,
+                                                                    const float *bias, const uint8_t *flip, int filter,
+                                                                    int max_prescale_log2, int apply_orientation,
+                                                                    const double *color /* 12 per file, or NULL */,
+                                                                    const int32_t *tone /* 2 per file, or NULL */, void *d_out,
+                                                                    size_t out_cap, int *rcs);
 /* stage 2 of n decoders on one context: the scans left for the device are decoded together (zj_decode_scans), the rest
  * one by one; rcs[k] is what zj_decoder_finish_pixels[_device] would have returned for decoder k */
 ZJ_API int zj_decoder_finish_pixels_batch(zj_decoder *const *ds, size_t n, zj_ctx *ctx, uint8_t *const *outs,

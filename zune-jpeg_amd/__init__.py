@@ -17,4 +17,5 @@ from .host import (  # noqa: F401
     RESIZE_BILINEAR, RESIZE_BILINEAR_AA, RESIZE_BICUBIC_AA, resize_filter,
     WARP_FILL, WARP_REPLICATE, warp_edge, warp_fixed, warp_source_window, finish_pixels_warped_batch,
     color_fixed,
+    TONE_IDENTITY, TONE_INVERT, TONE_POSTERIZE, TONE_SOLARIZE, TONE_AUTOCONTRAST, TONE_EQUALIZE, TONE_OPS,
 )

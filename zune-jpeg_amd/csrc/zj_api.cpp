@@ -21,6 +21,7 @@
 #include "zj_expand_launch.h"
 #include "zj_cmyk_launch.h"
 #include "zj_color_launch.h"
+#include "zj_tone_launch.h"
 #include "zj_planes_launch.h"
 #include "zj_plan.h"
 #include "zj_resize_launch.h"
@@ -33,6 +34,9 @@
 
 using namespace zj;
 static_assert(SCATTER_MAX == ZJ_SCATTER_MAX, "include/zjhip.h and zj_device.h disagree");
+static_assert(ZJ_TONE_IDENTITY == TONE_IDENTITY && ZJ_TONE_INVERT == TONE_INVERT && ZJ_TONE_POSTERIZE == TONE_POSTERIZE &&
+                  ZJ_TONE_SOLARIZE == TONE_SOLARIZE && ZJ_TONE_AUTOCONTRAST == TONE_AUTOCONTRAST && ZJ_TONE_EQUALIZE == TONE_EQUALIZE,
+              "include/zjhip.h and zj_tone_ops.h disagree");
 static_assert(sizeof(CropParams) <= 4096 && sizeof(CropZero) <= 4096 && sizeof(ResizeParams) <= 4096, "kernel arguments: 4 KB");
 
 namespace {
@@ -96,6 +100,10 @@ struct zj_ctx {
     // resize that read it, recorded on whichever stream that call ran on (the next user waits for it on ITS stream)
     void* rz_buf = nullptr; size_t rz_cap = 0;
     hipEvent_t rz_done = nullptr; bool rz_used = false;
+    // the histograms and tables of the tone stage (zj_tone_device), and the event after the last lookup that
+    // read them, recorded on whichever stream that call ran on (rz_done's rule)
+    void* tone_buf = nullptr; size_t tone_cap = 0;
+    hipEvent_t tone_done = nullptr; bool tone_used = false;
     // mixed-geometry crops (zj_decode_crops_resized_mixed_device): the per-frame records of a launch group,
     // built in pinned staging and copied to the device table on the caller's stream.  mx_up: after the last copy out of the
     // staging (the host waits for it before writing the staging again); mx_done: after the last launch that read the device
@@ -241,6 +249,8 @@ void zj_ctx_destroy(zj_ctx* c)
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->rz_done) { if (c->rz_used) (void)hipEventSynchronize(c->rz_done); (void)hipEventDestroy(c->rz_done); }
     if (c->rz_buf) (void)hipFree(c->rz_buf);
+    if (c->tone_done) { if (c->tone_used) (void)hipEventSynchronize(c->tone_done); (void)hipEventDestroy(c->tone_done); }
+    if (c->tone_buf) (void)hipFree(c->tone_buf);
     if (c->mx_done) { if (c->mx_used) (void)hipEventSynchronize(c->mx_done); (void)hipEventDestroy(c->mx_done); }
     if (c->mx_up) (void)hipEventDestroy(c->mx_up);
     if (c->mx_dev) (void)hipFree(c->mx_dev);
@@ -988,6 +998,105 @@ int color_matrices(const double* matrices, size_t n, std::vector<int32_t>& q)
     return ZJ_OK;
 }
 
+/* ---- the tone stages' launches ---- */
+// images [0, n) counted into their tables hist[f] (uint32 [channels][256], zeroed on the stream in front of this), launches of
+// up to HIST_BATCH images; wh: w, h pairs, the pitches resolved
+int hist_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, int channels, int chw,
+                  const uint8_t* const* hist, hipStream_t st)
+{
+    HistParams p{};
+    return stage_batches<HIST_BATCH>(n, [&](size_t f0, int m) {
+        pack_hist(p, in, wh, pitch, hist, f0, m);
+        ZJ_HIP(c, launch_hist(channels, chw, p, st));
+        return ZJ_OK;
+    });
+}
+
+// the tables of n ops (op, param pairs, all valid) into luts, uint8 [n][channels][256]; hist: uint32 [n][channels][256], read
+// for the ops that need one (nullptr: none does)
+int tone_lut_launches(zj_ctx* c, size_t n, int channels, const int32_t* ops, const uint32_t* hist, uint8_t* luts, hipStream_t st)
+{
+    ToneLutParams p{};
+    return stage_batches<TONE_LUT_BATCH>(n, [&](size_t f0, int m) {
+        pack_tone_lut(p, ops, hist, luts, channels, f0, m);
+        ZJ_HIP(c, launch_tone_lut(p, st));
+        return ZJ_OK;
+    });
+}
+
+// images [0, n) through their tables luts[f][c][.], launches of up to LUT_BATCH images
+int lut_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int channels, int chw,
+                 const uint8_t* luts, uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
+{
+    LutParams p{};
+    return stage_batches<LUT_BATCH>(n, [&](size_t f0, int m) {
+        pack_lut(p, in, wh, in_pitch, luts, channels, out, out_pitch, f0, m);
+        ZJ_HIP(c, launch_lut(channels, chw, p, st));
+        return ZJ_OK;
+    });
+}
+
+// the tone stage's buffer, at least `bytes`, free for writing on stream st: resize_scratch's rule with the tone stage's event
+int tone_scratch(zj_ctx* c, size_t bytes, hipStream_t st, uint8_t** p)
+{
+    if (!c->tone_done) ZJ_HIP(c, hipEventCreateWithFlags(&c->tone_done, hipEventDisableTiming));
+    if (bytes > c->tone_cap) {
+        if (c->tone_used) ZJ_HIP(c, hipEventSynchronize(c->tone_done));
+        if (c->tone_buf) { ZJ_HIP(c, hipFree(c->tone_buf)); c->tone_buf = nullptr; c->tone_cap = 0; }
+        const size_t cap = bytes + bytes / 4 + 4096;
+        ZJ_HIP(c, hipMalloc(&c->tone_buf, cap));
+        c->tone_cap = cap;
+    } else if (c->tone_used) {
+        ZJ_HIP(c, hipStreamWaitEvent(st, c->tone_done, 0));
+    }
+    *p = (uint8_t*)c->tone_buf;
+    return ZJ_OK;
+}
+
+// n ops of two int32 each: all of them ones the stage takes
+bool tone_ops_valid(const int32_t* ops, size_t n)
+{
+    for (size_t f = 0; f < n; f++)
+        if (!tone_op_valid(ops[2 * f], ops[2 * f + 1])) return false;
+    return true;
+}
+
+// zj_tone_device behind its checks: images [0, n) under their ops (op, param pairs, all valid), every image of the list in
+// every launch it needs -- the histogram for the ops that need one, into the context's buffer, zeroed in front; the table
+// build; the lookup.  All on st: the kernel boundaries are the only ordering.
+int tone_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, int channels, int chw,
+                  const int32_t* ops, uint8_t* const* out, const unsigned* out_pitch, hipStream_t st)
+{
+    const size_t tab = (size_t)channels * 256, hist_bytes = n * tab * 4;
+    uint8_t* buf = nullptr;
+    int rc = tone_scratch(c, hist_bytes + n * tab, st, &buf);
+    if (rc) return rc;
+    uint32_t* const hist = (uint32_t*)buf;
+    uint8_t* const luts = buf + hist_bytes;
+    std::vector<const uint8_t*> hin, htab;
+    std::vector<unsigned> hwh, hp;
+    for (size_t f = 0; f < n; f++)
+        if (tone_needs_hist(ops[2 * f])) {
+            hin.push_back(in[f]); htab.push_back((const uint8_t*)(hist + f * tab));
+            hwh.push_back(wh[2 * f]); hwh.push_back(wh[2 * f + 1]);
+            hp.push_back(in_pitch[f]);
+        }
+    // (whatever was queued reads or writes the buffer: the event is recorded behind it on the error paths as well, so that
+    // the next user, on whichever stream, and a call that grows the buffer wait for it)
+    const auto queue = [&]() -> int {
+        if (!hin.empty()) {
+            ZJ_HIP(c, hipMemsetAsync(hist, 0, hist_bytes, st));
+            if (const int e = hist_launches(c, hin.size(), hin.data(), hwh.data(), hp.data(), channels, chw, htab.data(), st)) return e;
+        }
+        if (const int e = tone_lut_launches(c, n, channels, ops, hin.empty() ? nullptr : hist, luts, st)) return e;
+        return lut_launches(c, n, in, wh, in_pitch, channels, chw, luts, out, out_pitch, st);
+    };
+    rc = queue();
+    if (hipEventRecord(c->tone_done, st) == hipSuccess) c->tone_used = true;
+    else if (!rc) { c->last_error = "hipEventRecord(c->tone_done, st) failed"; rc = ZJ_ERR_HIP; }
+    return rc;
+}
+
 // images [0, n) -> their three component planes box-replicated and converted, launches of up to PLANES_BATCH
 // images; wh: w, h pairs of the outputs, geo: planes_component of the three components, pitch: three per image, all resolved
 int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t* const* p1, const uint8_t* const* p2,
@@ -1012,11 +1121,14 @@ int planes_launches(zj_ctx* c, size_t n, const uint8_t* const* p0, const uint8_t
 // lane loads from (warp_launches).  The resized calls refuse an empty window before they come here.
 // color_q (nullptr: none): frame f's image, the one the last stage reads, passes the colour stage in place
 // under the integers color_q[12f .. 12f + 11] first; a frame with the identity's integers is left out of the launch.
+// tone (nullptr: none): the same image then passes the tone stage in place under the op tone[2f], tone[2f + 1];
+// ZJ_TONE_IDENTITY frames are left out of its launches.  Colour first, then tone.
 int warp_launches(zj_ctx* c, size_t n, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const int64_t* q,
                   const ResizeOut& o, const WarpTail& t, size_t first, hipStream_t st);
 
 int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g0, size_t g1, uint8_t* buf, const ResizeOut& o,
-                    hipStream_t st, const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr, const int32_t* color_q = nullptr)
+                    hipStream_t st, const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr, const int32_t* color_q = nullptr,
+                    const int32_t* tone = nullptr)
 {
     // the images of one stage of the group, gathered
     struct Stage {
@@ -1035,8 +1147,8 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
     const size_t ng = g1 - g0;
     std::vector<const uint8_t*> in(ng);
     std::vector<unsigned> wh(2 * ng), pitch(ng);
-    Stage turn, turn_gray, expand, color; // (the gray frames of a 3-channel call are turned as the 1-channel images they still are)
-    std::vector<int32_t> cq;
+    Stage turn, turn_gray, expand, color, toned; // (the gray frames of a 3-channel call are turned as the 1-channel images they still are)
+    std::vector<int32_t> cq, tq;
     for (size_t f = g0; f < g1; f++) {
         const RzPlace& p = place[f];
         in[f - g0] = buf + p.in.off;
@@ -1047,6 +1159,10 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
         if (color_q && p.in.w && !color_is_identity(color_q + 12 * f)) {
             color.add(buf, p.in, p.in, 1);
             cq.insert(cq.end(), color_q + 12 * f, color_q + 12 * f + 12);
+        }
+        if (tone && p.in.w && tone[2 * f] != TONE_IDENTITY) {
+            toned.add(buf, p.in, p.in, 1);
+            tq.insert(tq.end(), tone + 2 * f, tone + 2 * f + 2);
         }
     }
     int rc;
@@ -1062,6 +1178,9 @@ int rz_finish_group(zj_ctx* c, const RzFrame* fr, const RzPlace* place, size_t g
         return rc;
     if (!color.in.empty() && (rc = color_launches(c, color.in.size(), color.in.data(), color.wh.data(), color.ip.data(), o.chw,
                                                   cq.data(), color.out.data(), color.op.data(), st)))
+        return rc;
+    if (!toned.in.empty() && (rc = tone_launches(c, toned.in.size(), toned.in.data(), toned.wh.data(), toned.ip.data(), o.ch, o.chw,
+                                                 tq.data(), toned.out.data(), toned.op.data(), st)))
         return rc;
     if ((rc = warp ? warp_launches(c, ng, in.data(), wh.data(), pitch.data(), warp_q + 6 * g0, o, *warp, g0, st)
                    : resize_launches(c, ng, in.data(), wh.data(), pitch.data(), o, g0, st)))
@@ -1532,7 +1651,8 @@ int mixed_host_end(zj_ctx* c, int rc)
 int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
                              const int16_t* const* d_cb, const int16_t* const* d_cr, bool host_planes, const unsigned* windows,
                              ResizeOut ro, int max_prescale_log2, const uint8_t* orientation, void* stream,
-                             const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr, const int32_t* color_q = nullptr)
+                             const WarpTail* warp = nullptr, const int64_t* warp_q = nullptr, const int32_t* color_q = nullptr,
+                             const int32_t* tone = nullptr)
 {
     if (!resize_filter_valid(ro.filter) || max_prescale_log2 < 0 || max_prescale_log2 > 3) return ZJ_ERR_ARG;
     if (!c || !descs || !windows || nframes == 0 || nframes > (size_t)1 << 20 || !d_y || !ro.d_out) return ZJ_ERR_ARG;
@@ -1601,7 +1721,7 @@ int crops_resized_mixed_impl(zj_ctx* c, const zj_frame_desc* descs, size_t nfram
             return e;
         });
         if (rc) return rc;
-        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, warp, warp_q, color_q))) return rc;
+        if ((rc = rz_finish_group(c, rzf.data(), place.data(), g0, g1, buf, ro, st, warp, warp_q, color_q, tone))) return rc;
     }
     return ZJ_OK;
 }
@@ -1660,6 +1780,43 @@ int zjint_crops_resized_mixed_colored_host(zj_ctx* c, const zj_frame_desc* descs
     const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
                                             resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
                                             max_prescale_log2, orientation, nullptr, nullptr, nullptr, color_q);
+    return mixed_host_end(c, rc);
+}
+
+/* ---- tone curves in the resized-crop calls ---------------------------------------- */
+// tone (nullptr: zj_decode_crops_resized_mixed_colored_device itself): an op of two int32 per frame, all checked before
+// anything is launched
+int zj_decode_crops_resized_mixed_toned_device(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* d_y,
+                                               const int16_t* const* d_cb, const int16_t* const* d_cr, const unsigned* windows,
+                                               unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                               const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                               const uint8_t* orientation, const double* color, const int32_t* tone, void* d_out,
+                                               void* stream)
+{
+    std::vector<int32_t> q;
+    if (color || tone) {
+        if (nframes == 0 || nframes > (size_t)1 << 20) return ZJ_ERR_ARG;
+        if (color)
+            if (const int rc = color_matrices(color, nframes, q)) return rc;
+        if (tone && !tone_ops_valid(tone, nframes)) return ZJ_ERR_ARG;
+    }
+    return crops_resized_mixed_impl(c, descs, nframes, d_y, d_cb, d_cr, false, windows,
+                                    resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
+                                    max_prescale_log2, orientation, stream, nullptr, nullptr, color ? q.data() : nullptr, tone);
+}
+
+// Library-internal (zj_jpeg.cpp: zj_decoder_finish_pixels_resized_crop_batch_toned_device): zjint_crops_resized_mixed_colored_host
+// with file f's image under the op tone[2f], tone[2f + 1] (nullptr: none; every op valid) behind the colour stage
+int zjint_crops_resized_mixed_toned_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                         const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
+                                         unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                         const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                         const uint8_t* orientation, const int32_t* color_q, const int32_t* tone, void* d_out)
+{
+    if (tone && (!nframes || !tone_ops_valid(tone, nframes))) return ZJ_ERR_ARG;
+    const int rc = crops_resized_mixed_impl(c, descs, nframes, y, cb, cr, true, windows,
+                                            resize_out(out_w, out_h, dtype, out_layout, scale, bias, flip, filter, d_out),
+                                            max_prescale_log2, orientation, nullptr, nullptr, nullptr, color_q, tone);
     return mixed_host_end(c, rc);
 }
 
@@ -2053,6 +2210,93 @@ int zjint_color_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int layout,
     const uint8_t* in = img;
     ZJ_HIP(c, hipSetDevice(c->device));
     int rc = color_launches(c, 1, &in, wh, &pitch, layout == ZJ_LAYOUT_CHW, q, &img, &pitch, c->stream);
+    return rc ? rc : one_image_done(c);
+}
+
+/* ---- tone curves: histogram, table build, lookup ----------------------------------- */
+static bool tone_layout_ok(int channels, int layout)
+{
+    return (channels == 1 || channels == 3) && (layout == ZJ_LAYOUT_HWC || layout == ZJ_LAYOUT_CHW);
+}
+// bytes of a pixel inside a row: three only for interleaved 3-channel images
+static int tone_bpp(int channels, int layout) { return channels == 3 && layout == ZJ_LAYOUT_HWC ? 3 : 1; }
+
+int zj_histogram_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int channels,
+                        int layout, unsigned* d_hist, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_hist || ((uintptr_t)d_hist & 3u)) return ZJ_ERR_ARG;
+    if (!tone_layout_ok(channels, layout)) return ZJ_ERR_ARG;
+    std::vector<unsigned> ip;
+    if (!stage_images(n, d_in, in_wh, in_pitch, tone_bpp(channels, layout), ip)) return ZJ_ERR_ARG;
+    std::vector<const uint8_t*> tabs(n);
+    for (size_t f = 0; f < n; f++) tabs[f] = (const uint8_t*)(d_hist + f * (size_t)channels * 256);
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    ZJ_HIP(c, hipMemsetAsync(d_hist, 0, n * (size_t)channels * 1024, st));
+    return hist_launches(c, n, d_in, in_wh, ip.data(), channels, layout == ZJ_LAYOUT_CHW, tabs.data(), st);
+}
+
+int zj_tone_luts_device(zj_ctx* c, size_t n, int channels, const int32_t* ops, const unsigned* d_hist, uint8_t* d_luts, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !ops || !d_luts || (channels != 1 && channels != 3)) return ZJ_ERR_ARG;
+    if (!tone_ops_valid(ops, n) || ((uintptr_t)d_hist & 3u)) return ZJ_ERR_ARG;
+    for (size_t f = 0; f < n; f++)
+        if (tone_needs_hist(ops[2 * f]) && !d_hist) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return tone_lut_launches(c, n, channels, ops, d_hist, d_luts, st);
+}
+
+int zj_lut_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int channels,
+                  int layout, const uint8_t* d_luts, uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !d_luts || !d_out) return ZJ_ERR_ARG;
+    if (!tone_layout_ok(channels, layout)) return ZJ_ERR_ARG;
+    const int bpp = tone_bpp(channels, layout);
+    std::vector<unsigned> ip, op;
+    if (!stage_images(n, d_in, in_wh, in_pitch, bpp, ip) || !stage_side(n, d_out, out_pitch, in_wh, bpp, op)) return ZJ_ERR_ARG;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return lut_launches(c, n, d_in, in_wh, ip.data(), channels, layout == ZJ_LAYOUT_CHW, d_luts, d_out, op.data(), st);
+}
+
+int zj_tone_device(zj_ctx* c, size_t n, const uint8_t* const* d_in, const unsigned* in_wh, const unsigned* in_pitch, int channels,
+                   int layout, const int32_t* ops, uint8_t* const* d_out, const unsigned* out_pitch, void* stream)
+{
+    if (!c || n == 0 || n > (size_t)1 << 20 || !d_in || !in_wh || !ops || !d_out) return ZJ_ERR_ARG;
+    if (!tone_layout_ok(channels, layout) || !tone_ops_valid(ops, n)) return ZJ_ERR_ARG;
+    const int bpp = tone_bpp(channels, layout);
+    std::vector<unsigned> ip, op;
+    if (!stage_images(n, d_in, in_wh, in_pitch, bpp, ip) || !stage_side(n, d_out, out_pitch, in_wh, bpp, op)) return ZJ_ERR_ARG;
+    // an identity image that is its own output is left out of every launch
+    std::vector<const uint8_t*> in;
+    std::vector<uint8_t*> out;
+    std::vector<unsigned> wh, gip, gop;
+    std::vector<int32_t> q;
+    for (size_t f = 0; f < n; f++) {
+        if (ops[2 * f] == TONE_IDENTITY && d_out[f] == d_in[f] && ip[f] == op[f]) continue;
+        in.push_back(d_in[f]); out.push_back(d_out[f]);
+        wh.push_back(in_wh[2 * f]); wh.push_back(in_wh[2 * f + 1]);
+        gip.push_back(ip[f]); gop.push_back(op[f]);
+        q.push_back(ops[2 * f]); q.push_back(ops[2 * f + 1]);
+    }
+    if (in.empty()) return ZJ_OK;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return tone_launches(c, in.size(), in.data(), wh.data(), gip.data(), channels, layout == ZJ_LAYOUT_CHW, q.data(), out.data(),
+                         gop.data(), st);
+}
+
+// Library-internal (zj_jpeg.cpp: the single-file resized crop under a tone op): one tight image mapped in place under the op
+// on the context stream (ZJ_TONE_IDENTITY: nothing is launched); the context's crop buffer counts as read by it; synchronised
+int zjint_tone_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int channels, int layout, const int32_t op[2])
+{
+    if (!c || !img || !op || !stage_size(w, h) || !tone_layout_ok(channels, layout) || !tone_op_valid(op[0], op[1])) return ZJ_ERR_ARG;
+    if (op[0] == TONE_IDENTITY) return ZJ_OK;
+    const unsigned wh[2] = {w, h}, pitch = w * (unsigned)tone_bpp(channels, layout);
+    const uint8_t* in = img;
+    ZJ_HIP(c, hipSetDevice(c->device));
+    int rc = tone_launches(c, 1, &in, wh, &pitch, channels, layout == ZJ_LAYOUT_CHW, op, &img, &pitch, c->stream);
     return rc ? rc : one_image_done(c);
 }
 

@@ -54,6 +54,8 @@ ZJINT_DECL int zjint_warp_one(zj_ctx* c, const uint8_t* in, unsigned w, unsigned
                               int edge, void* d_out);
 // ... and one image mapped in place under the 12 integers of a colour matrix (the identity's: no launch)
 ZJINT_DECL int zjint_color_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int layout, const int32_t q[12]);
+// ... and under a tone op of two int32 (ZJ_TONE_IDENTITY: no launch): channels 1 or 3
+ZJINT_DECL int zjint_tone_one(zj_ctx* c, uint8_t* img, unsigned w, unsigned h, int channels, int layout, const int32_t op[2]);
 
 // The mixed-geometry calls over several files' planes in HOST memory, each file of its own geometry; d_out: the first file's
 // image, the others behind it.  Synchronous: the planes may be reused when they return.
@@ -69,6 +71,13 @@ ZJINT_DECL int zjint_crops_resized_mixed_colored_host(zj_ctx* c, const zj_frame_
                                                       unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
                                                       const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
                                                       const uint8_t* orientation, const int32_t* color_q, void* d_out);
+// ... and under the op tone[2f], tone[2f + 1] behind that (nullptr: none)
+ZJINT_DECL int zjint_crops_resized_mixed_toned_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
+                                                    const int16_t* const* cb, const int16_t* const* cr, const unsigned* windows,
+                                                    unsigned out_w, unsigned out_h, int dtype, int out_layout, const float* scale,
+                                                    const float* bias, const uint8_t* flip, int filter, int max_prescale_log2,
+                                                    const uint8_t* orientation, const int32_t* color_q, const int32_t* tone,
+                                                    void* d_out);
 // ... the crop tensors, every window w x h
 ZJINT_DECL int zjint_crops_tensor_mixed_host(zj_ctx* c, const zj_frame_desc* descs, size_t nframes, const int16_t* const* y,
                                              const int16_t* const* cb, const int16_t* const* cr, const unsigned* origins, unsigned w,

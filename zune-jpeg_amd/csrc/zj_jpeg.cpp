@@ -36,6 +36,7 @@
 #include "zj_rzgroup.h"
 #include "zj_warp_fixed.h"
 #include "zj_color_fixed.h"
+#include "zj_tone_ops.h"
 #include "zj_huff.h"
 // the internal calls of the pixel path, weak here: this file is also built without them (zj_internal.h)
 #define ZJINT_DECL __attribute__((weak))
@@ -2934,6 +2935,8 @@ struct LastStage {
     int edge = 0;
     // a colour matrix in front of it: its 12 integers, the finished u8 image mapped in place; nullptr: none
     const int32_t* color_q = nullptr;
+    // a tone op behind that: op and param, the same image mapped in place; nullptr: none
+    const int32_t* tone = nullptr;
 };
 static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigned y, unsigned w, unsigned h, const LastStage& ls,
                           size_t out_cap, size_t* out_len, int o = 1);
@@ -3397,6 +3400,14 @@ static int color_stage(zj_decoder* d, zj_ctx* ctx, const LastStage& s, uint8_t* 
     return rc ? fail(d, rc, std::string("colour: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : (int)ZJ_OK;
 }
 
+// The tone stage behind it (LastStage.tone): the same image, of `channels` channels, mapped in place
+static int tone_stage(zj_decoder* d, zj_ctx* ctx, const LastStage& s, uint8_t* img, unsigned w, unsigned h, int channels, int layout)
+{
+    if (!s.tone) return ZJ_OK;
+    const int rc = zjint_tone_one(ctx, img, w, h, channels, layout, s.tone);
+    return rc ? fail(d, rc, std::string("tone: ") + zj_strerror(rc) + " " + zj_last_error(ctx)) : (int)ZJ_OK;
+}
+
 // finish_resized for a four-component file, its arguments checked: fa the descriptor of A (resized_checks),
 // x, y, w, h the stored window, win the window the crop stage writes (at scale k: of the reduced frame).  In the context's
 // buffer: the crop of A, the crop of K behind it, turned: their displayed forms behind both; A's displayed image combined in
@@ -3435,6 +3446,7 @@ static int finish_resized_four(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& 
     rc = zjint_cmyk_to_rgb_one(ctx, a, kk, dw, dh, layout, d->adobe_transform >= 0);
     if (rc) return fail(d, rc, std::string("CMYK to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     if ((rc = color_stage(d, ctx, ls, a, dw, dh, layout))) return rc;
+    if ((rc = tone_stage(d, ctx, ls, a, dw, dh, 3, layout))) return rc;
     return last_stage(d, ctx, ls, a, dw, dh, 3, 3, layout);
 }
 
@@ -3488,6 +3500,7 @@ static int finish_resized_odd(zj_decoder* d, zj_ctx* ctx, const zj_frame_desc& f
         e = buf + off_e2;
     }
     if ((rc = color_stage(d, ctx, ls, e, dw, dh, layout))) return rc;
+    if ((rc = tone_stage(d, ctx, ls, e, dw, dh, 3, layout))) return rc;
     return last_stage(d, ctx, ls, e, dw, dh, 3, 3, layout);
 }
 
@@ -3503,6 +3516,10 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
     if (ls.color_q) {
         if (!zjint_color_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
         if (ch != 3 || ls.to_tensor) return fail(d, ZJ_ERR_UNSUPPORTED, "a colour matrix maps the three channels of a resized crop");
+    }
+    if (ls.tone) {
+        if (!zjint_tone_one) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
+        if (ls.to_tensor) return fail(d, ZJ_ERR_UNSUPPORTED, "a tone op maps the u8 image of a resized crop");
     }
     if (d->odd) return finish_resized_odd(d, ctx, fd, x, y, w, h, o, ls);
     const unsigned full[4] = {x, y, w, h};
@@ -3539,6 +3556,7 @@ static int finish_resized(zj_decoder* d, zj_ctx* ctx, int k, unsigned x, unsigne
         if (rc) return fail(d, rc, std::string("gray to RGB: ") + zj_strerror(rc) + " " + zj_last_error(ctx));
     }
     if ((rc = color_stage(d, ctx, ls, crop + at.in.off, at.in.w, at.in.h, layout))) return rc;
+    if ((rc = tone_stage(d, ctx, ls, crop + at.in.off, at.in.w, at.in.h, ch, layout))) return rc;
     return last_stage(d, ctx, ls, crop + at.in.off, at.in.w, at.in.h, in_ch, ch, layout);
 }
 
@@ -3681,20 +3699,25 @@ int zj_decoder_finish_pixels_warped_batch_device(zj_decoder* const* ds, size_t n
 // color (nullptr: none): 12 doubles per file, file k's finished u8 image under matrix k in front of the resize.
 // A matrix the stage refuses is that file's ZJ_ERR_ARG and stops no other; the mixed runs go through
 // zjint_crops_resized_mixed_colored_host, the files that go alone through finish_resized with the integers in its LastStage.
+// tone (nullptr: none): an op of two int32 per file, the same image under it behind the colour stage; an op the
+// stage refuses is that file's ZJ_ERR_ARG and stops no other; the mixed runs go through zjint_crops_resized_mixed_toned_host.
 static int resized_crop_batch(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* windows, unsigned out_w, unsigned out_h,
                               int dtype, int out_layout, const float* scale, const float* bias, const uint8_t* flip, int filter,
-                              int max_prescale_log2, int apply_orientation, const double* color, void* d_out, size_t out_cap, int* rcs)
+                              int max_prescale_log2, int apply_orientation, const double* color, const int32_t* tone, void* d_out, size_t out_cap,
+                              int* rcs)
 {
     using namespace zj;
     if (!ds || !n || !ctx || !windows || !d_out || !rcs) return ZJ_ERR_ARG;
     if (!zjint_crops_resized_mixed_host) return ZJ_ERR_UNSUPPORTED; // (a build without the pixel path)
     if (color && (!zjint_crops_resized_mixed_colored_host || !zjint_color_one)) return ZJ_ERR_UNSUPPORTED;
+    if (tone && (!zjint_crops_resized_mixed_toned_host || !zjint_tone_one)) return ZJ_ERR_UNSUPPORTED;
     std::vector<int32_t> cq(color ? 12 * n : 0); // per file: the 12 integers of its matrix
     return file_batch(
         ds, n, resized_len(1, out_w, out_h, dtype), out_cap, rcs,
         [&](FileBatch& b, size_t k) -> int {
             zj_decoder* const d = ds[k];
             if (color && !color_fixed(color + 12 * k, cq.data() + 12 * k)) return fail(d, ZJ_ERR_ARG, "not a matrix the colour stage takes");
+            if (tone && !tone_op_valid(tone[2 * k], tone[2 * k + 1])) return fail(d, ZJ_ERR_ARG, "not an op the tone stage takes");
             if (max_prescale_log2 < 0 || max_prescale_log2 > 3 || !b.img) return FILE_SINGLE;
             const int o = apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1;
             unsigned x = windows[4 * k], y = windows[4 * k + 1], w = windows[4 * k + 2], h = windows[4 * k + 3];
@@ -3709,12 +3732,13 @@ static int resized_crop_batch(zj_decoder* const* ds, size_t n, zj_ctx* ctx, cons
         },
         [&](const FileBatch& b, size_t k) {
             const unsigned* const w = windows + 4 * k;
-            if (color) { // (the oriented / prescaled single-file call's body, with the integers in its last stage)
+            if (color || tone) { // (the oriented / prescaled single-file call's body, with the integers in its last stage)
                 zj_decoder* const d = ds[k];
                 if (max_prescale_log2 < 0 || max_prescale_log2 > 3) return fail(d, ZJ_ERR_ARG, "max_prescale_log2 is 0..3");
                 const int kk = out_w && out_h ? prescale_pick(w[2], w[3], out_w, out_h, max_prescale_log2) : 0;
                 LastStage ls{false, out_w, out_h, dtype, out_layout, scale, bias, flip ? flip[k] : 0, filter, (uint8_t*)d_out + k * b.img};
-                ls.color_q = cq.data() + 12 * k;
+                if (color) ls.color_q = cq.data() + 12 * k;
+                if (tone) ls.tone = tone + 2 * k;
                 return finish_resized(d, ctx, kk, w[0], w[1], w[2], w[3], ls, b.img, nullptr,
                                       apply_orientation && d->orientation >= 1 && d->orientation <= 8 ? d->orientation : 1);
             }
@@ -3723,6 +3747,13 @@ static int resized_crop_batch(zj_decoder* const* ds, size_t n, zj_ctx* ctx, cons
                 (uint8_t*)d_out + k * b.img, b.img, nullptr);
         },
         [&](const FileBatch& b, size_t k0, size_t k1) {
+            if (tone)
+                return zjint_crops_resized_mixed_toned_host(ctx, b.fds.data() + k0, k1 - k0, b.py.data() + k0, b.pcb.data() + k0,
+                                                            b.pcr.data() + k0, windows + 4 * k0, out_w, out_h, dtype, out_layout, scale,
+                                                            bias, flip ? flip + k0 : nullptr, filter, max_prescale_log2,
+                                                            apply_orientation ? b.ori.data() + k0 : nullptr,
+                                                            color ? cq.data() + 12 * k0 : nullptr, tone + 2 * k0,
+                                                            (uint8_t*)d_out + k0 * b.img);
             if (color)
                 return zjint_crops_resized_mixed_colored_host(ctx, b.fds.data() + k0, k1 - k0, b.py.data() + k0, b.pcb.data() + k0,
                                                               b.pcr.data() + k0, windows + 4 * k0, out_w, out_h, dtype, out_layout, scale,
@@ -3743,7 +3774,7 @@ int zj_decoder_finish_pixels_resized_crop_batch_device(zj_decoder* const* ds, si
                                                        int* rcs)
 {
     return resized_crop_batch(ds, n, ctx, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, max_prescale_log2,
-                              apply_orientation, nullptr, d_out, out_cap, rcs);
+                              apply_orientation, nullptr, nullptr, d_out, out_cap, rcs);
 }
 
 int zj_decoder_finish_pixels_resized_crop_batch_colored_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* windows,
@@ -3753,7 +3784,17 @@ int zj_decoder_finish_pixels_resized_crop_batch_colored_device(zj_decoder* const
                                                                void* d_out, size_t out_cap, int* rcs)
 {
     return resized_crop_batch(ds, n, ctx, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, max_prescale_log2,
-                              apply_orientation, color, d_out, out_cap, rcs);
+                              apply_orientation, color, nullptr, d_out, out_cap, rcs);
+}
+
+int zj_decoder_finish_pixels_resized_crop_batch_toned_device(zj_decoder* const* ds, size_t n, zj_ctx* ctx, const unsigned* windows,
+                                                             unsigned out_w, unsigned out_h, int dtype, int out_layout,
+                                                             const float* scale, const float* bias, const uint8_t* flip, int filter,
+                                                             int max_prescale_log2, int apply_orientation, const double* color,
+                                                             const int32_t* tone, void* d_out, size_t out_cap, int* rcs)
+{
+    return resized_crop_batch(ds, n, ctx, windows, out_w, out_h, dtype, out_layout, scale, bias, flip, filter, max_prescale_log2,
+                              apply_orientation, color, tone, d_out, out_cap, rcs);
 }
 
 // The whole displayed image of the prepared file, tight, in the decoder's colour space and layout: orientation 1 decodes

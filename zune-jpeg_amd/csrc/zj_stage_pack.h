@@ -16,6 +16,7 @@
 #include "zj_orient.h"
 #include "zj_planes.h"
 #include "zj_to_tensor.h"
+#include "zj_tone.h"
 #include "zj_warp.h"
 
 namespace zj {
@@ -101,6 +102,34 @@ inline void pack_color(ColorParams& p, const uint8_t* const* in, const unsigned*
         for (int k = 0; k < 12; k++) p.q[i][k] = 0;
     for (int i = 0; i < m; i++)
         for (int k = 0; k < 12; k++) p.q[i][k] = q[12 * (f0 + i) + k];
+}
+
+// the tone stages.  hist[f]: image f's table, uint32 [channels][256]
+inline void pack_hist(HistParams& p, const uint8_t* const* in, const unsigned* wh, const unsigned* pitch, const uint8_t* const* hist,
+                      size_t f0, int m)
+{
+    p.nimg = m;
+    stage_ptrs(p.in, in, 1, f0, m); stage_ptrs(p.hist, hist, 1, f0, m);
+    stage_whs(p.wh, wh, f0, m);
+    stage_slots(p.pitch, pitch, 1, f0, m);
+}
+
+// ops: op, param pairs; hist (nullptr: no op needs one): uint32 [n][channels][256], luts: uint8 [n][channels][256] of the call
+inline void pack_tone_lut(ToneLutParams& p, const int32_t* ops, const uint32_t* hist, uint8_t* luts, int channels, size_t f0, int m)
+{
+    p.nimg = m; p.channels = channels;
+    p.hist = hist ? stage_ptr(hist + f0 * (size_t)channels * 256) : 0;
+    p.luts = stage_ptr(luts + f0 * (size_t)channels * 256);
+    stage_slots(p.op, ops, 2, f0, m); stage_slots(p.param, ops + 1, 2, f0, m);
+}
+
+// luts: uint8 [n][channels][256] of the call
+inline void pack_lut(LutParams& p, const uint8_t* const* in, const unsigned* wh, const unsigned* in_pitch, const uint8_t* luts,
+                     int channels, const uint8_t* const* out, const unsigned* out_pitch, size_t f0, int m)
+{
+    p.nimg = m;
+    stage_in_out(p, in, wh, in_pitch, out, out_pitch, f0, m);
+    p.luts = stage_ptr(luts + f0 * (size_t)channels * 256);
 }
 
 // inverted[f] != 0: the samples are used as stored, else complemented first

@@ -204,6 +204,8 @@ ABI = [  # every symbol include/zjhip.h declares
     "zj_decoder_finish_pixels_warped_device", "zj_decoder_finish_pixels_warped_batch_device",
     "zj_color_fixed", "zj_color_device", "zj_decode_crops_resized_mixed_colored_device",
     "zj_decoder_finish_pixels_resized_crop_batch_colored_device",
+    "zj_histogram_device", "zj_tone_luts_device", "zj_lut_device", "zj_tone_device",
+    "zj_decode_crops_resized_mixed_toned_device", "zj_decoder_finish_pixels_resized_crop_batch_toned_device",
 ]
 SCATTER_MAX = 32  # ZJ_SCATTER_MAX: frames per launch of the scattered form
 
@@ -415,6 +417,15 @@ def lib():
     L.zj_decoder_finish_pixels_resized_crop_batch_colored_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int,
                                                                              vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, sz,
                                                                              C.POINTER(C.c_int)]
+    L.zj_histogram_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.zj_tone_luts_device.argtypes = [vp, sz, C.c_int, vp, vp, vp, vp]
+    L.zj_lut_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.zj_tone_device.argtypes = [vp, sz, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.zj_decode_crops_resized_mixed_toned_device.argtypes = [vp, C.POINTER(FrameDesc), sz, vp, vp, vp, vp, C.c_uint, C.c_uint,
+                                                             C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.zj_decoder_finish_pixels_resized_crop_batch_toned_device.argtypes = [vp, sz, vp, vp, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                                           vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz,
+                                                                           C.POINTER(C.c_int)]
     L.zj_pool_create_multi.restype = vp
     L.zj_pool_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(Options), C.POINTER(C.c_int)]
     L.zj_pool_devices.argtypes = [vp]
@@ -555,6 +566,21 @@ def _colors(matrices, n):
     if len(matrices) != n:
         raise ValueError("one colour matrix per image")
     return (C.c_double * (12 * n))(*[v for m in matrices for v in (IDENTITY_COLOR if m is None else _color_flat(m))])
+
+
+# ZJ_TONE_*: the ops of the tone stage
+TONE_IDENTITY, TONE_INVERT, TONE_POSTERIZE, TONE_SOLARIZE, TONE_AUTOCONTRAST, TONE_EQUALIZE = 0, 1, 2, 3, 4, 5
+TONE_OPS = {"identity": TONE_IDENTITY, "invert": TONE_INVERT, "posterize": TONE_POSTERIZE, "solarize": TONE_SOLARIZE,
+            "autocontrast": TONE_AUTOCONTRAST, "equalize": TONE_EQUALIZE}
+
+
+def _tones(ops, n):
+    """one tone op per image, (op, param) pairs or None (the identity), as 2 n int32; None: no tone stage"""
+    if ops is None:
+        return None
+    if len(ops) != n:
+        raise ValueError("one tone op per image")
+    return (C.c_int32 * (2 * n))(*[int(v) for op in ops for v in ((TONE_IDENTITY, 0) if op is None else tuple(op))])
 
 
 def _matrices(matrices, n):
@@ -857,6 +883,47 @@ class Context:
                                      _colors(matrices, n), (C.c_void_p * n)(*d_out), _pit(out_pitches, n), stream),
                "zj_color_device", self._h)
 
+    def histogram_device(self, d_in, sizes, channels, layout, d_hist, in_pitches=None, stream=None):
+        """The histograms of u8 images (zj_histogram_device): d_in = device pointers, sizes = one (w, h) each,
+        channels 1 or 3, layout LAYOUT_HWC or LAYOUT_CHW, d_hist = device pointer of uint32 [n][channels][256] (overwritten).
+        Asynchronous on `stream`."""
+        n = len(d_in)
+        if len(sizes) != n:
+            raise ValueError("one size per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = (C.c_uint * n)(*[int(x) for x in in_pitches]) if in_pitches is not None else None
+        _check(lib().zj_histogram_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit, channels, layout, d_hist, stream),
+               "zj_histogram_device", self._h)
+
+    def tone_luts_device(self, ops, channels, d_hist, d_luts, stream=None):
+        """The tables of tone ops (zj_tone_luts_device): ops = one (op, param) each, d_hist = device pointer of uint32
+        [n][channels][256] (None when no op is autocontrast or equalize), d_luts = device pointer of uint8 [n][channels][256]."""
+        n = len(ops)
+        _check(lib().zj_tone_luts_device(self._h, n, channels, _tones(ops, n), d_hist, d_luts, stream), "zj_tone_luts_device", self._h)
+
+    def lut_device(self, d_in, sizes, channels, layout, d_luts, d_out, in_pitches=None, out_pitches=None, stream=None):
+        """u8 images through their own tables, out[c] = luts[i][c][in[c]] (zj_lut_device): d_luts = device pointer of uint8
+        [n][channels][256]; d_out[i] may be d_in[i] with the same pitch.  Asynchronous on `stream`."""
+        n = len(d_in)
+        if len(sizes) != n or len(d_out) != n:
+            raise ValueError("one size and output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+        _check(lib().zj_lut_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), channels, layout, d_luts,
+                                   (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_lut_device", self._h)
+
+    def tone_device(self, d_in, sizes, channels, layout, ops, d_out, in_pitches=None, out_pitches=None, stream=None):
+        """u8 images each under its own tone op (zj_tone_device): ops = one (op, param) each (None: the
+        identity); histogram, table build and lookup on `stream`, nothing synchronised.  d_out[i] may be d_in[i] with the same
+        pitch; an identity image that is its own output costs no launch."""
+        n = len(d_in)
+        if len(sizes) != n or len(d_out) != n or ops is None:
+            raise ValueError("one size, op and output per image")
+        wh = (C.c_uint * (2 * n))(*[int(v) for s in sizes for v in s])
+        pit = lambda v: (C.c_uint * n)(*[int(x) for x in v]) if v is not None else None
+        _check(lib().zj_tone_device(self._h, n, (C.c_void_p * n)(*d_in), wh, pit(in_pitches), channels, layout, _tones(ops, n),
+                                    (C.c_void_p * n)(*d_out), pit(out_pitches), stream), "zj_tone_device", self._h)
+
     def planes_to_rgb_device(self, d_p0, d_p1, d_p2, sizes, ratios, layout, d_out, stored_rgb=False, pitches=None,
                              out_pitches=None, stream=None):
         """Three u8 component planes per image, each at its own resolution -> the 3-channel u8 image whose pixel (r, c) is
@@ -944,12 +1011,14 @@ class Context:
 
     def decode_crops_resized_mixed_device(self, descs, d_y, d_cb, d_cr, windows, out_w, out_h, dtype, out_layout, d_out,
                                           scale=None, bias=None, flips=None, stream=None, antialias=False, max_prescale=1,
-                                          orientations=None, interpolation="bilinear", colors=None):
+                                          orientations=None, interpolation="bilinear", colors=None, tones=None):
         """Resized crop windows of frames of MIXED geometry (zj_decode_crops_resized_mixed_device): descs = one FrameDesc
         per frame (sizes, sampling, tables, flags and in_components their own; out_colorspace and out_layout the same in
         all); the other arguments as decode_crops_resized_device.  Image f equals that call's for frame f alone.
         colors: one [3, 4] colour matrix per frame (None entries: the identity), the u8 image under it in front of the
         resize (zj_decode_crops_resized_mixed_colored_device); None: today's call.
+        tones: one (op, param) tone op per frame (None entries: the identity), the same image under it behind the colour
+        matrix (zj_decode_crops_resized_mixed_toned_device); None: no tone stage.
         Asynchronous on `stream`."""
         filt = resize_filter(antialias, interpolation)
         n = len(d_y)
@@ -958,6 +1027,12 @@ class Context:
         arr = lambda v: (C.c_void_p * n)(*v) if v is not None else None
         win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
         ori = (C.c_uint8 * n)(*[int(o) for o in orientations]) if orientations is not None else None
+        if tones is not None:
+            _check(lib().zj_decode_crops_resized_mixed_toned_device(
+                self._h, (FrameDesc * n)(*descs), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w, out_h, dtype, out_layout,
+                _floats(scale), _floats(bias), _flips(flips, n), filt, scale_log2(max_prescale), ori, _colors(colors, n),
+                _tones(tones, n), d_out, stream), "zj_decode_crops_resized_mixed_toned_device", self._h)
+            return
         if colors is not None:
             _check(lib().zj_decode_crops_resized_mixed_colored_device(
                 self._h, (FrameDesc * n)(*descs), n, arr(d_y), arr(d_cb), arr(d_cr), win, out_w, out_h, dtype, out_layout,
@@ -1410,13 +1485,15 @@ def finish_pixels_batch(decoders, ctx, outs=None, device_ptrs=None):
 
 def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype, out_layout, d_out, cap, scale=None, bias=None,
                                      flips=None, antialias=False, max_prescale=1, apply_orientation=False,
-                                     interpolation="bilinear", colors=None):
+                                     interpolation="bilinear", colors=None, tones=None):
     """zj_decoder_finish_pixels_resized_crop_batch_device over Decoder objects that went through prepare() or
     decode_coefficients(), each with a file of its own size: windows = one (x, y, w, h) per decoder (displayed pixels with
     apply_orientation), image k left at device pointer d_out + k * resized_out_len.  Returns the list of statuses: image k
     is Decoder.finish_pixels_resized_crop_device's for decoder k alone, a failed file's slot is untouched.
     colors: one [3, 4] colour matrix per decoder (None entries: the identity), each file's u8 image under its matrix in
-    front of the resize (zj_decoder_finish_pixels_resized_crop_batch_colored_device); None: no colour stage."""
+    front of the resize (zj_decoder_finish_pixels_resized_crop_batch_colored_device); None: no colour stage.
+    tones: one (op, param) tone op per decoder (None entries: the identity), the same image under it behind the colour matrix
+    (zj_decoder_finish_pixels_resized_crop_batch_toned_device); None: no tone stage."""
     filt = resize_filter(antialias, interpolation)
     n = len(decoders)
     if len(windows) != n:
@@ -1424,6 +1501,12 @@ def finish_pixels_resized_crop_batch(decoders, ctx, windows, out_w, out_h, dtype
     dptr = (C.c_void_p * n)(*[d._d for d in decoders])
     win = (C.c_uint * (4 * n))(*[int(v) for w in windows for v in w])
     rcs = (C.c_int * n)()
+    if tones is not None:
+        _check(lib().zj_decoder_finish_pixels_resized_crop_batch_toned_device(
+            dptr, n, ctx.handle, win, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias), _flips(flips, n), filt,
+            scale_log2(max_prescale), 1 if apply_orientation else 0, _colors(colors, n), _tones(tones, n), d_out, cap, rcs),
+            "zj_decoder_finish_pixels_resized_crop_batch_toned_device", ctx.handle)
+        return list(rcs)
     if colors is not None:
         _check(lib().zj_decoder_finish_pixels_resized_crop_batch_colored_device(
             dptr, n, ctx.handle, win, out_w, out_h, dtype, out_layout, _floats(scale), _floats(bias), _flips(flips, n), filt,

@@ -154,7 +154,7 @@ def _on_stream(s, cur, tensors):
 
 def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None, layout="NCHW", mean=None, std=None,
                                    flips=None, stream=None, antialias=False, max_prescale=1, orientations=None,
-                                   interpolation="bilinear", color=None):
+                                   interpolation="bilinear", color=None, tone=None):
     """Crop windows resized and normalised into ONE dense tensor (zj_decode_crops_resized_device): frames = a list of
     (Y, Cb, Cr) int16 CUDA tensors, one frame each (Cb / Cr may be None for GRAYSCALE output), windows = one (x, y, w, h)
     per frame (each its own size), size = (out_w, out_h).  Returns [N, C, out_h, out_w] ("NCHW") or [N, out_h, out_w, C]
@@ -174,7 +174,11 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     color: one [3, 4] colour matrix per frame (color_matrix; None in a frame's place: the identity), applied to the u8 image
     in front of the resize, clamped as an 8-bit image is; the call then goes through
     zj_decode_crops_resized_mixed_colored_device with the descriptor repeated.  None (default): none.  Needs a
-    three-channel output.  Stream and allocator rules as decode_to_tensor."""
+    three-channel output.
+    tone: one tone op per frame (tone_op; None in a frame's place: the identity) -- invert, posterize, solarize, autocontrast,
+    equalize, byte for byte Pillow's ImageOps on the u8 CROP the resize reads -- behind the colour matrix and
+    in front of the resize (zj_decode_crops_resized_mixed_toned_device).  None (default): none.  One-channel outputs take it
+    too.  Stream and allocator rules as decode_to_tensor."""
     import torch
     from .host import resize_filter, scale_log2
     scale_log2(max_prescale)
@@ -195,14 +199,15 @@ def decode_resized_crops_to_tensor(ctx, desc, frames, windows, size, dtype=None,
     out = _resized_out(n, channels, size, dtype, layout, dev, s)
     _on_stream(s, cur, [p for fr in frames for p in fr])
     ptr = lambda t: t.data_ptr() if t is not None else None
-    if color is not None:
-        if len(color) != n:
-            raise ValueError("one colour matrix per frame")
+    if color is not None or tone is not None:
+        if (color is not None and len(color) != n) or (tone is not None and len(tone) != n):
+            raise ValueError("one colour matrix / tone op per frame")
         cbs = [ptr(fr[1]) for fr in frames]
         ctx.decode_crops_resized_mixed_device([desc] * n, [ptr(fr[0]) for fr in frames], cbs if any(cbs) else None,
                                               [ptr(fr[2]) for fr in frames] if any(cbs) else None, windows, ow, oh, code,
                                               TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(), scale, bias, flips,
-                                              s.cuda_stream, antialias, max_prescale, orientations, interpolation, colors=color)
+                                              s.cuda_stream, antialias, max_prescale, orientations, interpolation, colors=color,
+                                              tones=tone)
         return out
     ctx.decode_crops_resized_device(desc, [ptr(fr[0]) for fr in frames], [ptr(fr[1]) for fr in frames],
                                     [ptr(fr[2]) for fr in frames], windows, ow, oh, code,
@@ -297,7 +302,7 @@ def _raise_first_failed(decs, rcs):
 
 def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout="NCHW", mean=None, std=None, flips=None,
                                    antialias=False, interpolation="bilinear", max_prescale=1, apply_orientation=False,
-                                   options=None, workers=1, stream=None, decoders=None, color=None):
+                                   options=None, workers=1, stream=None, decoders=None, color=None, tone=None):
     """JPEG files of ANY sizes -> ONE dense resized-crop tensor (zj_decoder_finish_pixels_resized_crop_batch_device,
     DESIGN.md 3.10): blobs = a list of bytes-like JPEG files, windows = one (x, y, w, h) per file (displayed pixels with
     apply_orientation; None, or None in a file's place: the whole displayed image), size = (out_w, out_h).  Returns
@@ -322,6 +327,10 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     color: one [3, 4] colour matrix per file (color_matrix; None in a file's place: the identity): each file's finished u8
     image -- gray, CMYK, odd-sampled and turned files included -- under its matrix in front of the resize, clamped as an
     8-bit image is (zj_decoder_finish_pixels_resized_crop_batch_colored_device).  None (default): none.
+    tone: one tone op per file (tone_op; None in a file's place: the identity): the same u8 image under it behind the colour
+    matrix -- invert, posterize, solarize, autocontrast and equalize as Pillow's ImageOps on the CROP the resize reads, not on
+    the whole file (zj_decoder_finish_pixels_resized_crop_batch_toned_device).  With color= and the warp this
+    reaches RandAugment's op set inside the call, Sharpness excepted.  None (default): none.
     The batch call runs on the context's stream and has finished when it returns; `stream` (None: torch's current) is
     the stream the output is allocated under, synchronised before the call writes it."""
     import torch
@@ -348,7 +357,7 @@ def decode_files_resized_to_tensor(ctx, blobs, windows, size, dtype=None, layout
     rcs = finish_pixels_resized_crop_batch(decs, ctx, wins, size[0], size[1], code,
                                            TENSOR_NCHW if layout == "NCHW" else TENSOR_NHWC, out.data_ptr(),
                                            out.numel() * out.element_size(), scale, bias, flips, antialias, max_prescale,
-                                           apply_orientation, interpolation, colors=color)
+                                           apply_orientation, interpolation, colors=color, tones=tone)
     _raise_first_failed(decs, rcs)
     return out
 
@@ -593,6 +602,107 @@ def color_twist_tensor(ctx, images, matrices, in_layout="HWC", inplace=False, st
     _on_stream(s, cur, imgs)
     ctx.color_device([im.data_ptr() for im in imgs], sizes, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC, matrices,
                      [o.data_ptr() for o in outs], pitches, opitches, s.cuda_stream)
+    return outs
+
+
+def tone_op(kind, param=0):
+    """The (op, param) pair of a tone op: kind = "identity", "invert", "posterize" (param: bits 1..8),
+    "solarize" (param: threshold 0..256), "autocontrast" or "equalize" (or the TONE_* code).  Each is Pillow's ImageOps
+    function of that name, byte for byte; autocontrast with cutoff 0, equalize without a mask."""
+    from .host import TONE_OPS, TONE_POSTERIZE, TONE_SOLARIZE
+    op = TONE_OPS[kind] if isinstance(kind, str) else int(kind)
+    param = int(param)
+    if op not in TONE_OPS.values():
+        raise ValueError("not a tone op")
+    lo, hi = {TONE_POSTERIZE: (1, 8), TONE_SOLARIZE: (0, 256)}.get(op, (0, 0))
+    if not lo <= param <= hi:
+        raise ValueError(f"this op's param is {lo}..{hi}")
+    return (op, param)
+
+
+def gamma_lut(gamma, gain=1.0):
+    """A uint8 [3, 256] table for lut_tensor: min(255, int(255 * gain * (i / 255) ** gamma + 0.5)) in every channel.  A
+    helper: the stage applies whatever table it is given."""
+    import numpy as np
+    i = np.arange(256, dtype=np.float64) / 255.0
+    t = np.minimum(255, (255.0 * float(gain) * i ** float(gamma) + 0.5).astype(np.int64))
+    return np.ascontiguousarray(np.tile(np.maximum(t, 0).astype(np.uint8), (3, 1)))
+
+
+def _tone_images(images, in_layout):
+    if in_layout not in ("HWC", "CHW"):
+        raise ValueError("in_layout is 'HWC' or 'CHW'")
+    return _u8_images(images, in_layout)
+
+
+def histogram_tensor(ctx, images, in_layout="HWC", stream=None):
+    """The histograms of u8 CUDA images (zj_histogram_device): images = [H, W, 3], [H, W, 1], [H, W] ("HWC")
+    or [3, H, W] ("CHW") uint8 tensors of their own sizes, rows may be strided.  Returns an int32 CUDA tensor
+    [N, channels, 256] (the counts are below 2^32; a count of 2^31 or more reads as negative).  Streams as decode_to_tensor."""
+    import torch
+    imgs, sizes, pitches, channels = _tone_images(images, in_layout)
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        hist = torch.empty((len(imgs), channels, 256), dtype=torch.int32, device=dev)
+    _on_stream(s, cur, imgs)
+    ctx.histogram_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC,
+                         hist.data_ptr(), pitches, s.cuda_stream)
+    return hist
+
+
+def _tone_outputs(torch, imgs, images, sizes, pitches, channels, in_layout, inplace, s):
+    if inplace:
+        if any(a is not b and a.data_ptr() != b.data_ptr() for a, b in zip(imgs, images)):
+            raise ValueError("inplace needs images that are used as they are (unit stride inside a row)")
+        return imgs, pitches
+    dev = imgs[0].device
+    with torch.cuda.stream(s):
+        outs = [torch.empty((3, h, w) if in_layout == "CHW" else (h, w, channels), dtype=torch.uint8, device=dev) for w, h in sizes]
+    return outs, None
+
+
+def lut_tensor(ctx, images, luts, in_layout="HWC", inplace=False, stream=None):
+    """u8 CUDA images through tables, out[c] = luts[i][c][in[c]] (zj_lut_device): luts = a uint8
+    [N, channels, 256] CUDA tensor or array, or one [channels, 256] table for every image (gamma_lut, any tone curve).
+    Returns new contiguous tensors in the same layout; inplace=True writes the images themselves.  Streams as
+    decode_to_tensor."""
+    import torch
+    imgs, sizes, pitches, channels = _tone_images(images, in_layout)
+    dev = imgs[0].device
+    cur = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else cur
+    with torch.cuda.stream(s):
+        t = torch.as_tensor(luts, dtype=torch.uint8).to(dev)
+        if t.dim() == 2:
+            t = t.unsqueeze(0).expand(len(imgs), -1, -1)
+        if tuple(t.shape) != (len(imgs), channels, 256):
+            raise ValueError("luts are [N, channels, 256] or [channels, 256]")
+        t = t.contiguous()
+    outs, opitches = _tone_outputs(torch, imgs, images, sizes, pitches, channels, in_layout, inplace, s)
+    _on_stream(s, cur, imgs)
+    ctx.lut_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC, t.data_ptr(),
+                   [o.data_ptr() for o in outs], pitches, opitches, s.cuda_stream)
+    t.record_stream(s)
+    return outs
+
+
+def tone_tensor(ctx, images, ops, in_layout="HWC", inplace=False, stream=None):
+    """u8 CUDA images each under its own tone op (zj_tone_device): ops = one tone_op each (None: the
+    identity).  Autocontrast and equalize use each image's own histogram, computed on the device; nothing is synchronised.
+    Returns new contiguous tensors in the same layout; inplace=True writes the images themselves (an identity image then
+    costs no launch).  Streams as decode_to_tensor."""
+    import torch
+    imgs, sizes, pitches, channels = _tone_images(images, in_layout)
+    if len(ops) != len(imgs):
+        raise ValueError("one tone op per image")
+    cur = torch.cuda.current_stream(imgs[0].device)
+    s = stream if stream is not None else cur
+    outs, opitches = _tone_outputs(torch, imgs, images, sizes, pitches, channels, in_layout, inplace, s)
+    _on_stream(s, cur, imgs)
+    ctx.tone_device([im.data_ptr() for im in imgs], sizes, channels, LAYOUT_CHW if in_layout == "CHW" else LAYOUT_HWC, ops,
+                    [o.data_ptr() for o in outs], pitches, opitches, s.cuda_stream)
     return outs
 
 
